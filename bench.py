@@ -2,7 +2,14 @@
 """bench.py -- QPS of the batched flat-NSW k-NN search on MI355X, one line per BASELINE.json configuration.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2-uint8|c3|c3-lowrank|c4|c5|c5-lowrank|c5-uint8]
-                  [--secondary-configs c4,c3-lowrank,c5,c5-lowrank | none] [--index-size n ...]
+                  [--dump-outputs DIR] [--full [--secondary-configs c4,c3-lowrank,c5,c5-lowrank | none]] [--index-size n ...]
+
+A plain run (no --full) does what the headline figure needs and nothing else: generate the data, build the index, the exact
+ground truth and the ef rule below, warm up, time ONE region of exactly --steps launches, write the outputs of the last timed
+step (--dump-outputs DIR: DIR/<name>.npy) and print the contract line.  `ms_per_step` = that region's wall time / --steps.
+Everything else this file measures -- roofline and gather ceiling, CPU baseline, host-buffer / pinned / multi-caller paths,
+two launches in flight, one query per call, sustained rate, fixed-ef lines, three timed regions, the further configurations
+and the full record -- runs with --full, as described below.
 
 One "step" = one pass of the hot path over one batch: `nq` queries (10 000) searched against an index resident in
 HBM; queries and result buffers are in HBM when the timed region starts; every step searches a DIFFERENT batch.
@@ -17,7 +24,7 @@ Configurations (BASELINE.json `configs`, generators of SURVEY.md 8d; no dataset 
 All with M=32, ef_construction=100, K=10.  The metric's rule: the smallest ef of the sweep with recall@10 >= 0.95,
 recall measured on all 10 000 queries of the first batch against exact brute force.
 
-Output (round 5).  stdout carries exactly ONE line, printed last by rank 0: the contract line of the main configuration
+Output with --full (round 5).  stdout carries exactly ONE line, printed last by rank 0: the contract line of the main configuration
 (c2 by default), at most 4 KB -- contract fields, `roofline` (dominant kernel; achieved = algorithmic bytes per launch /
 average launch duration from HIP events on the launch stream; `gather_ceiling` = what a pure random-row gather of this very
 vector table reaches, measured in the run), `cpu_baseline` (N=1: the CPU oracle timed on the host cores),
@@ -26,8 +33,9 @@ vector table reaches, measured in the run), `cpu_baseline` (N=1: the CPU oracle 
 `secondary`: one short row per fixed-ef line and per FURTHER CONFIGURATION.  Those run after the main one in the same
 process -- like the reference's harness, which runs a list of datasets and ef values in one invocation
 (experiments/run-benchmark.py:362-506, tools/query_npy.cpp:132-158) -- N = 1: c2-uint8, c4, c3-lowrank, c3, c5, c5-lowrank, c5-uint8;
-N > 1 GPUs: only c5, the configuration worded for 8 GPUs; `--secondary-configs none` turns them off, `--time-budget` skips
-what no longer fits.  The FULL record -- every configuration's whole entry (own recall / ef rule, roofline, counters,
+N > 1 GPUs: only c5, the configuration worded for 8 GPUs; `--secondary-configs none` turns them off, `--time-budget` (540 s)
+skips a configuration whose expected duration (EXPECTED_SECONDS) no longer fits, so that the whole run ends within ~10 minutes.
+The FULL record -- every configuration's whole entry (own recall / ef rule, roofline, counters,
 cpu_baseline with GPU ids == CPU ids, sustained and two-launches-in-flight rates, per-rank and broadcast reports) -- is
 written to bench_out/bench_full.json (`--full-record`) and, as one line, to stderr.
 Multi-GPU: one process per GPU; `--gpus N` without a torch.distributed environment spawns the N ranks itself.
@@ -83,6 +91,18 @@ CONFIGS = {
 }
 # world size -> configurations after the main one (else: "c5")
 SECONDARY_DEFAULT = {1: "c2-uint8,c4,c3-lowrank,c3,c5,c5-lowrank,c5-uint8"}
+# wall seconds of one further configuration at its full size on one MI355X (the slowest of the runs recorded under
+# profiles/, rounded up): with --time-budget it decides whether a configuration still fits
+EXPECTED_SECONDS = {"c2": 25, "c2-uint8": 10, "c4": 18, "c3-lowrank": 145, "c3": 117, "c5": 196, "c5-lowrank": 196,
+                    "c5-uint8": 176}
+
+
+def expected_seconds(name, n=0):
+    """Expected wall time of further configuration `name`, scaled down when --secondary-index-size shrinks it."""
+    full = EXPECTED_SECONDS.get(name, 200)
+    if n and n < CONFIGS[name]["n"]:
+        return max(5.0, full * n / CONFIGS[name]["n"])
+    return float(full)
 
 
 def log(*a):
@@ -125,12 +145,22 @@ def parse_args():
                          "top-level key (default: c4,c3-lowrank,c5,c5-lowrank on one GPU, c5 on several; 'none' = off)")
     ap.add_argument("--secondary-index-size", type=int, default=0,
                     help="node count of the secondary configurations (0 = each configuration's own; tests use small ones)")
-    ap.add_argument("--full-record", default="", help="where the full record goes (default: bench_out/bench_full.json)")
-    ap.add_argument("--regions", type=int, default=3,
-                    help="timed regions of --steps launches each per configuration; value = the median region's (min / max reported)")
-    ap.add_argument("--time-budget", type=float, default=1500.0,
-                    help="seconds after which no further secondary configuration is started")
-    return ap.parse_args()
+    ap.add_argument("--full-record", default="", help="where the full record goes (default with --full: bench_out/bench_full.json)")
+    ap.add_argument("--regions", type=int, default=0,
+                    help="timed regions of --steps launches each per configuration; value = the median region's (min / max "
+                         "reported); default: 1, with --full 3")
+    ap.add_argument("--time-budget", type=float, default=540.0,
+                    help="seconds within which the whole run should end: a further configuration is started only if its "
+                         "expected duration still fits")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline and gather ceiling, CPU baseline, host-buffer "
+                         "paths, sustained / pipelined / one-query rates, fixed-ef lines and the further configurations")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (distances, labels, counters) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.regions <= 0:
+        args.regions = 3 if args.full else 1
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -257,19 +287,22 @@ def main() -> None:
         names = SECONDARY_DEFAULT.get(world, "c5")
         if args.n or args.ef >= 0 or args.dtype != "float32" or args.no_secondary or args.opt:  # a reduced / special run is about its one configuration
             names = "none"
+    if not args.full:  # a plain run measures the headline figure only
+        names = "none"
     names = [] if names in ("none", "") else [n for n in names.split(",") if n and n != args.config]
     for name in names:
         if name not in CONFIGS:
             raise SystemExit("unknown configuration in --secondary-configs: %s" % name)
         # every rank must take the same decision: rank 0's clock decides
-        go = (time.time() - t_start) < args.time_budget
+        go = (time.time() - t_start) + expected_seconds(name, args.secondary_index_size) <= args.time_budget
         if dist is not None:
             flag = torch.tensor([1 if go else 0], device=ctx.dev_t)
             dist.broadcast(flag, src=0)
             go = bool(flag.item())
         if not go:
             if rank == 0:
-                out[name] = {"skipped": "time budget of %.0f s used up (%.0f s elapsed)" % (args.time_budget, time.time() - t_start)}
+                out[name] = {"skipped": "time budget of %.0f s: %.0f s elapsed, ~%.0f s expected" % (
+                    args.time_budget, time.time() - t_start, expected_seconds(name, args.secondary_index_size))}
                 out["secondary"].append({"config": name, "skipped": True})
             continue
         sub = argparse.Namespace(**vars(args))
@@ -310,7 +343,9 @@ def main() -> None:
         # and `cpu_baseline`, and one short row per further configuration (round 4's single 25 KB line was not parsed by
         # the driver).  The reference's harness likewise writes a small machine-readable metrics record
         # (experiments/run-benchmark.py:329-343).
-        full_path = write_full_record(compact(out), args.full_record)
+        full_path = None
+        if args.full or args.full_record:
+            full_path = write_full_record(compact(out), args.full_record)
         print(contract_line(out, names, args.config, full_path), flush=True)
 
 
@@ -344,9 +379,9 @@ def contract_line(out, names, main_name, full_path):
     (SURVEY 8d defines the metric on the call that includes the copies), the three timed regions behind `value`, and one
     short row per further configuration.  Never longer than CONTRACT_LINE_MAX bytes: optional parts are dropped, in a
     fixed order, until it fits (a CPU test builds a seven-configuration record and checks the size)."""
-    c, r = out["config"], out["roofline"]
+    c, r = out["config"], out.get("roofline")  # (no roofline in a plain run: --full measures it)
     launch = c.get("launch") or {}
-    traffic_rec = (r.get("traffic_recorded") or {}).get("hbm_bytes_per_launch_corrected")
+    traffic_rec = ((r or {}).get("traffic_recorded") or {}).get("hbm_bytes_per_launch_corrected")
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data")}
     # (VERDICT r5 #7) which rate `value` is, in the line itself: the contract's device-resident rate; SURVEY 8d words the metric
@@ -367,20 +402,22 @@ def contract_line(out, names, main_name, full_path):
         "queries_straight_to_exact_kernel": launch.get("tail_exact"),
         "launch": {k: launch.get(k) for k in ("kernel", "grid_blocks", "blocks_per_cu", "resident_per_cu", "lds_bytes", "visited_slots") if k in launch},
     }
-    line["roofline"] = {
-        "bound": r["bound"], "kernel": r["kernel"], "achieved": _sig(r["achieved"], 6), "peak": r["peak"], "unit": r["unit"],
-        "frac": _sig(r["frac"], 6), "gather_ceiling": _sig(r.get("gather_ceiling"), 6),
-        "frac_of_gather_ceiling": _sig(r.get("frac_of_gather_ceiling"), 4),
-        "algorithmic_bytes_per_launch": _sig(r["algorithmic_bytes_per_launch"], 7), "avg_kernel_ms": _sig(r["avg_kernel_ms"], 6),
-        "traffic": r.get("traffic"),
-        "traffic_recorded": traffic_rec,
-        "traffic_over_algorithmic": None if not traffic_rec else _sig(traffic_rec / r["algorithmic_bytes_per_launch"], 3),
-    }
+    if r:
+        line["roofline"] = {
+            "bound": r["bound"], "kernel": r["kernel"], "achieved": _sig(r["achieved"], 6), "peak": r["peak"], "unit": r["unit"],
+            "frac": _sig(r["frac"], 6), "gather_ceiling": _sig(r.get("gather_ceiling"), 6),
+            "frac_of_gather_ceiling": _sig(r.get("frac_of_gather_ceiling"), 4),
+            "algorithmic_bytes_per_launch": _sig(r["algorithmic_bytes_per_launch"], 7), "avg_kernel_ms": _sig(r["avg_kernel_ms"], 6),
+            "traffic": r.get("traffic"),
+            "traffic_recorded": traffic_rec,
+            "traffic_over_algorithmic": None if not traffic_rec else _sig(traffic_rec / r["algorithmic_bytes_per_launch"], 3),
+        }
     cpu = out.get("cpu_baseline")
     if cpu:
         line["cpu_baseline"] = {"value": _sig(cpu["value"], 6), "unit": cpu["unit"], "cores": cpu["cores"], "kind": cpu["kind"],
                                 "sample": cpu.get("sample_short") or cpu["sample"][:160]}
-    line["value_pcie_inclusive"] = c.get("host_buffer_qps_pcie_inclusive")
+    if "host_buffer_qps_pcie_inclusive" in c:
+        line["value_pcie_inclusive"] = c.get("host_buffer_qps_pcie_inclusive")
     if c.get("host_buffer_qps_pinned_caller_zero_copy"):
         line["value_pcie_inclusive_pinned_caller"] = c["host_buffer_qps_pinned_caller_zero_copy"]  # (zero-copy: the caller's arrays are pinned)
     line["timed_regions"] = {k: (_sig(v) if not isinstance(v, list) else [_sig(x, 4) for x in v])
@@ -463,12 +500,15 @@ def summary_row(name, e):
     """'<config>: ef=.. recall=.. (min over batches ..) <queries/s> frac=.. of 8 TB/s (.. of the gather ceiling) cpu=..'"""
     if "skipped" in e:
         return "%s: skipped (%s)" % (name, e["skipped"])
-    c, r = e["config"], e["roofline"]
+    c, r = e["config"], e.get("roofline")
     cpu = e.get("cpu_baseline")
-    return ("%s: ef=%d recall@10=%.4f (min over %d batches %.4f) %.4g queries/s kernel %.4g ms frac=%.3f of 8 TB/s (%.2f of its gather "
-            "ceiling) %d/CU (%d resident) cpu=%s"
-            % (name, c["ef_search"], c["recall_at_10"], c["recall_all_timed_batches"]["batches"], c["recall_all_timed_batches"]["min"],
-               e["value"], r["avg_kernel_ms"], r["frac"], r["frac_of_gather_ceiling"], c["launch"]["blocks_per_cu"],
+    row = ("%s: ef=%d recall@10=%.4f (min over %d batches %.4f) %.4g queries/s"
+           % (name, c["ef_search"], c["recall_at_10"], c["recall_all_timed_batches"]["batches"], c["recall_all_timed_batches"]["min"],
+              e["value"]))
+    if not r:  # a plain run: no roofline, no CPU baseline (--full)
+        return row
+    return (row + " kernel %.4g ms frac=%.3f of 8 TB/s (%.2f of its gather ceiling) %d/CU (%d resident) cpu=%s"
+            % (r["avg_kernel_ms"], r["frac"], r["frac_of_gather_ceiling"], c["launch"]["blocks_per_cu"],
                c["launch"].get("resident_per_cu", c["launch"]["blocks_per_cu"]),
                "-" if not cpu else "%.4g q/s on %d threads" % (cpu["value"], cpu["cores"])))
 
@@ -483,6 +523,92 @@ def compact(obj, top=True):
     if isinstance(obj, float) and obj == obj and abs(obj) not in (0.0, float("inf")):
         return float("%.6g" % obj)
     return obj
+
+
+def workload_text(config, cfg, N, DT, metric, args, EF):
+    return ("%s [%s]: %d x %d %s %s, M=%d, ef_construction=%d, ef_search=%d, K=%d, %d batched queries per GPU per step (a "
+            "different batch every step), index in HBM" % (config, cfg["title"], N, cfg["dim"], DT, "L2" if metric == "l2" else
+                                                           "inner product", args.M, args.efc, EF, args.K, args.nq))
+
+
+def ef_selection_text(NQ, sweep_rec, sweep_min):
+    if not sweep_rec:
+        return "fixed (configuration / --ef)"
+    return ("smallest ef of the sweep with recall@10 >= 0.95 on all %d queries of batch 0 AND of every other timed batch "
+            "(SURVEY.md 8d); batch-0 recalls: %s; lowest batch at the efs that passed on batch 0: %s" % (NQ, sweep_rec, sweep_min))
+
+
+def plain_entry(args, config, cfg, N, DT, metric, EF, data_note, build_note, world, m, per_rank_s, recalls, sweep_rec,
+                sweep_min, nb, geom, info, replay, bcast):
+    """The entry of a plain run (no --full): the contract fields, meaning what they mean in the full entry, and what the
+    library reports about the last timed launch -- nothing that takes a launch or a measurement of its own."""
+    rec_min, rec_mean, rec_list = recalls
+    geom["resident_per_cu"] = resident_per_cu(geom["blocks_per_cu"], geom["lds_bytes"])
+    return {
+        "metric": "qps_at_recall10_ge_0.95",
+        "value": m["qps"],
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": m["elapsed"] / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if DT == "float32" else "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": workload_text(config, cfg, N, DT, metric, args, EF),
+            "recall_at_10": round(rec_list[0], 4),
+            "recall_queries": args.nq,
+            "recall_all_timed_batches": {"min": round(rec_min, 4), "mean": round(rec_mean, 4), "batches": nb,
+                                         "queries_per_batch": args.nq},
+            "ef_search": EF,
+            "ef_selection": ef_selection_text(args.nq, sweep_rec, sweep_min),
+            "data_note": data_note,
+            "index_build": build_note,
+            "parallelism": "index replicated x%d, queries sharded" % world,
+            "multi_gpu": None if world == 1 else {
+                "per_rank_queries_per_s": [args.nq * args.steps / t for t in per_rank_s],
+                "per_rank_seconds": per_rank_s,
+                "index_broadcast": bcast,
+                "note": "value = all ranks' queries / the slowest rank's seconds"},
+            "launch": geom,
+            "kernel_variant": info["variant"],
+            "exploratory_timed_launches": m["explored"],
+            "queries_replayed_by_exact_kernel": replay["total"],
+            "measured_in_this_run": "value and ms_per_step (%d timed region(s) of --steps launches), recall; roofline, CPU "
+                                    "baseline, host-buffer paths, fixed-ef lines and further configurations: --full" % args.regions,
+        },
+        "timed_regions": {"n": len(m["regions_qps"]), "min": min(m["regions_qps"]), "median": m["qps"],
+                          "max": max(m["regions_qps"]), "kernel_ms": m["regions_kernel_ms"],
+                          "note": "value / ms_per_step are the median region's (each region: --steps launches)"},
+        "secondary": [],
+    }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: the arrays the last timed step handed its caller, one DIR/<name>.npy each -- distances as float32,
+    labels / result counts / per-query n_dist and n_hops as float64 (exact: all below 2^53).  The inputs depend on the
+    arguments only (seeded generators, deterministic device builder), so two builds can be compared file by file.  Past
+    DUMP_MAX_BYTES a fixed, seeded sample of the queries is written, and its row numbers as query_rows.npy."""
+    arrays = {"distances": last["distances"].astype(np.float32)}
+    for k in ("labels", "result_counts", "n_dist", "n_hops"):
+        arrays[k] = last[k].astype(np.float64)
+    nq = arrays["distances"].shape[0]
+    per_query = sum(a.nbytes for a in arrays.values()) / max(nq, 1)
+    if per_query * nq > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, int(DUMP_MAX_BYTES // (per_query + 8)), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log("[bench] outputs of the last timed step (batch %d) written to %s: %s" % (
+        last["batch"], path, ", ".join("%s %s" % (k, list(a.shape)) for k, a in arrays.items())))
 
 
 def run_config(ctx, args, config, main_line):
@@ -613,6 +739,7 @@ def run_config(ctx, args, config, main_line):
     # ---- ef_search: fixed by the configuration, or the metric's rule (rank 0 decides) ----------------------------
     sweep_rec = {}
     sweep_min = {}  # ef -> lowest recall over the batches, for the efs whose batch 0 passed
+    sweep_all = {}  # ef -> recall_all(ef), for the same efs
     EF = cfg["ef"] if args.ef < 0 else args.ef
     sweep = [int(x) for x in args.ef_sweep.split(",")] if args.ef_sweep else cfg["sweep"]
     if EF == 0:
@@ -622,7 +749,8 @@ def run_config(ctx, args, config, main_line):
                 sweep_rec[ef] = round(recall_at(ef), 4)
                 ok = sweep_rec[ef] >= 0.95
                 if ok:  # the rule holds on batch 0: it has to hold on every batch that will be timed
-                    sweep_min[ef] = round(recall_all(ef)[0], 4)
+                    sweep_all[ef] = recall_all(ef)
+                    sweep_min[ef] = round(sweep_all[ef][0], 4)
                     ok = sweep_min[ef] >= 0.95
             if dist is not None:
                 flag = torch.tensor([1 if ok else 0], device=dev_t)
@@ -642,9 +770,11 @@ def run_config(ctx, args, config, main_line):
 
     tuned = {}
     per_rank = []  # seconds each rank measured for the most recent timed region (N > 1)
+    last_step = {}  # what the last timed step of the main measurement returned (--dump-outputs)
 
-    def run(ef, steps, warmup, min_seconds=0.0):
-        """Times `steps` launches (batch i mod nb each); returns (elapsed, kernel_ms list, steps done)."""
+    def run(ef, steps, warmup, min_seconds=0.0, keep=False):
+        """Times `steps` launches (batch i mod nb each); returns (elapsed, kernel_ms list, steps done).  `keep`: copy the
+        output buffers of the last step to the host afterwards."""
         def step(i):
             dev.search_device(dq[i % nb].data_ptr(), NQ, K, ef, 100, d_dist.data_ptr(), d_lab.data_ptr(),
                               d_cnt.data_ptr(), d_nd.data_ptr(), d_nh.data_ptr(), stream=stream.cuda_stream)
@@ -681,6 +811,9 @@ def run_config(ctx, args, config, main_line):
         if launches["timed_end"] is None or launches["timed_open"]:
             launches["timed_end"] = launches["n"]  # (the main measurement's last timed region ends here)
         dev.status()
+        if keep:  # (untimed) the caller's view of step i - 1: results, result counts, per-query counters
+            last_step.update(batch=(i - 1) % nb, distances=d_dist.cpu().numpy(), labels=d_lab.cpu().numpy(),
+                             result_counts=d_cnt.cpu().numpy(), n_dist=d_nd.cpu().numpy(), n_hops=d_nh.cpu().numpy())
         per_rank.clear()
         if dist is not None:
             mine = torch.tensor([elapsed], dtype=torch.float64, device=dev_t)
@@ -708,30 +841,44 @@ def run_config(ctx, args, config, main_line):
             nhs.append(nh.mean())
         return tot / len(batches), tot_rows / len(batches), float(np.mean(nds)), float(np.mean(nhs))
 
-    def measure(ef, steps, warmup, min_seconds=0.0, regions=1):
+    def measure(ef, steps, warmup, min_seconds=0.0, regions=1, keep=False):
         """`regions` timed regions of `steps` launches each (each bracketed by its own barriers; the warm-up precedes the
         first); the numbers are the MEDIAN region's, `regions_qps` lists all of them (round 5: one region of 10-20 launches
-        is 10-20 ms -- box-to-box and run-to-run differences of 5-10 % were larger than what a round gained)."""
+        is 10-20 ms -- box-to-box and run-to-run differences of 5-10 % were larger than what a round gained).  The byte
+        counts behind the roofline take launches of their own: --full only."""
         runs = []
         for g in range(max(1, regions)):
-            elapsed, kms, done, explored = run(ef, steps, warmup if g == 0 else 0, min_seconds)
+            elapsed, kms, done, explored = run(ef, steps, warmup if g == 0 else 0, min_seconds, keep=keep and g == regions - 1)
             runs.append((NQ * world * done / elapsed, elapsed, kms, done, explored, list(per_rank)))
         order = sorted(range(len(runs)), key=lambda j: runs[j][0])
         qps, elapsed, kms, done, explored, pr = runs[order[len(order) // 2]]
         per_rank[:] = pr
         used = sorted(set(i % nb for i in range(done)))
-        byts, row_byts, nd_mean, nh_mean = launch_bytes(ef, used[:8])
+        byts, row_byts, nd_mean, nh_mean = launch_bytes(ef, used[:8]) if args.full else (None, None, None, None)
         avg_kernel_s = float(np.mean(kms)) / 1e3
         return dict(elapsed=elapsed, steps=done, qps=qps, bytes=byts, row_bytes=row_byts, nd=nd_mean,
-                    nh=nh_mean, kernel_ms=avg_kernel_s * 1e3, achieved=byts / avg_kernel_s / 1e9,
+                    nh=nh_mean, kernel_ms=avg_kernel_s * 1e3, achieved=None if byts is None else byts / avg_kernel_s / 1e9,
                     explored=sum(r[4] for r in runs), regions_qps=[r[0] for r in runs],
                     regions_kernel_ms=[float(np.mean(r[2])) for r in runs])
 
     launches["timed_end"], launches["timed_open"] = None, True
-    main_m = measure(EF, args.steps, args.warmup, regions=args.regions)
+    main_m = measure(EF, args.steps, args.warmup, regions=args.regions, keep=main_line and bool(args.dump_outputs))
     launches["timed_open"] = False
     main_per_rank = list(per_rank)
+    if rank == 0 and last_step:
+        dump_outputs(args.dump_outputs, last_step)
     out = None
+    if not args.full:  # a plain run: the headline figure and what its line states, from what has been measured already
+        if rank == 0:
+            out = plain_entry(args, config, cfg, N, DT, metric, EF, data.note, build_note, world, main_m, main_per_rank,
+                              sweep_all[EF] if EF in sweep_all else recall_all(EF), sweep_rec, sweep_min, nb,
+                              dev.launch_geometry(), dev.launch_info(), dev.replayed_queries(), bcast)
+        dev.search_device, dev.search, dev.search_into = _sd, _sh, _si
+        dev.close()
+        del dev, index, dq, d_dist, d_lab, d_cnt, d_nd, d_nh, gts, data, Q_all, Q_rank
+        gc.collect()
+        torch.cuda.empty_cache()
+        return out
     if rank == 0:
         rec_min, rec_mean, rec_list = recall_all(EF)
         recall = rec_list[0]
@@ -877,19 +1024,13 @@ def run_config(ctx, args, config, main_line):
             "dtype": "f32" if DT == "float32" else "u8",
             "data": "synthetic",
             "config": {
-                "workload": "%s [%s]: %d x %d %s %s, M=%d, ef_construction=%d, ef_search=%d, K=%d, %d batched queries "
-                            "per GPU per step (a different batch every step), index in HBM"
-                            % (config, cfg["title"], N, DIM, DT, "L2" if metric == "l2" else "inner product", M,
-                               args.efc, EF, K, NQ),
+                "workload": workload_text(config, cfg, N, DT, metric, args, EF),
                 "recall_at_10": round(recall, 4),
                 "recall_queries": NQ,
                 "recall_all_timed_batches": {"min": round(rec_min, 4), "mean": round(rec_mean, 4), "batches": nb,
                                              "queries_per_batch": NQ},
                 "ef_search": EF,
-                "ef_selection": ("fixed (configuration / --ef)" if not sweep_rec else
-                                 "smallest ef of the sweep with recall@10 >= 0.95 on all %d queries of batch 0 AND of every "
-                                 "other timed batch (SURVEY.md 8d); batch-0 recalls: %s; lowest batch at the efs that "
-                                 "passed on batch 0: %s" % (NQ, sweep_rec, sweep_min)),
+                "ef_selection": ef_selection_text(NQ, sweep_rec, sweep_min),
                 "data_note": data.note,
                 "index_build": build_note,
                 "parallelism": "index replicated x%d, queries sharded" % world,

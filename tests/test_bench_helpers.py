@@ -164,3 +164,57 @@ def test_resident_per_cu_follows_the_measured_lds_granules():
     for lds, api, resident in measured:
         assert bench.resident_per_cu(api, lds) == resident, (lds, api, resident)
     assert bench.resident_per_cu(16, 7680) == 16  # registers / the grid limit first
+
+
+def test_plain_run_line_carries_the_contract_fields_only():
+    # a plain run (no --full) has no roofline, CPU baseline, host-buffer rate or further configuration: the line and the summary
+    # row are built from what it has, with the contract fields unchanged
+    e = _full_entry("c2")
+    for k in ("roofline", "cpu_baseline", "sustained", "pipelined", "single_query"):
+        e.pop(k)
+    for k in ("host_buffer_qps_pcie_inclusive", "host_buffer_qps_two_caller_threads", "host_buffer_qps_four_caller_threads"):
+        e["config"].pop(k)
+    e["timed_regions"] = {"n": 1, "min": e["value"], "median": e["value"], "max": e["value"], "kernel_ms": [1.03], "note": "n"}
+    d = json.loads(bench.contract_line(e, [], "c2", None))
+    assert d["value"] == e["value"] and d["ms_per_step"] == e["ms_per_step"] and d["metric"] == "qps_at_recall10_ge_0.95"
+    assert "roofline" not in d and "cpu_baseline" not in d and "value_pcie_inclusive" not in d and d["secondary"] == []
+    assert d["timed_regions"]["n"] == 1 and d["full_record"] is None
+    assert bench.summary_row("c2", e) == "c2: ef=1600 recall@10=0.9511 (min over 20 batches 0.9507) 9.635e+06 queries/s"
+
+
+def test_time_budget_keeps_a_full_run_within_ten_minutes():
+    # --full at the default sizes: a further configuration starts only if its expected duration still fits the budget
+    names = bench.SECONDARY_DEFAULT[1].split(",")
+    assert set(bench.EXPECTED_SECONDS) == set(bench.CONFIGS)
+    elapsed, ran = bench.EXPECTED_SECONDS["c2"], []
+    for name in names:
+        if elapsed + bench.expected_seconds(name) <= 540.0:
+            elapsed += bench.expected_seconds(name)
+            ran.append(name)
+    assert elapsed <= 540.0 and ran[:3] == ["c2-uint8", "c4", "c3-lowrank"]
+    assert bench.expected_seconds("c5", 40000) == 5.0 and bench.expected_seconds("c4", 0) == bench.EXPECTED_SECONDS["c4"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    rng = np.random.default_rng(3)
+    last = {"batch": 2, "distances": rng.random((500, 10), dtype=np.float32), "labels": rng.integers(0, 10 ** 6, (500, 10)).astype(np.int32),
+            "result_counts": np.full(500, 10, np.int32), "n_dist": rng.integers(0, 2 ** 40, 500), "n_hops": rng.integers(0, 99, 500)}
+    bench.dump_outputs(str(tmp_path / "a"), last)
+    for k, v in last.items():
+        if k == "batch":
+            continue
+        a = np.load(str(tmp_path / "a" / (k + ".npy")))
+        assert a.dtype == (np.float32 if k == "distances" else np.float64) and np.array_equal(a, v), k
+    assert not (tmp_path / "a" / "query_rows.npy").exists()
+    # past the limit: a fixed, seeded sample of the queries, the same in every run, and its row numbers
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20000)
+    bench.dump_outputs(str(tmp_path / "b"), last)
+    bench.dump_outputs(str(tmp_path / "c"), last)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= 20000 + 128 * len(files)  # (+ .npy headers)
+    rows = np.load(str(tmp_path / "b" / "query_rows.npy")).astype(np.int64)
+    assert 0 < len(rows) < 500 and np.array_equal(np.load(str(tmp_path / "b" / "labels.npy")), last["labels"][rows])
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f)))

@@ -10,7 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--index-size", "60000", "--nq", "2000", "--steps", "2", "--warmup", "1"]
+SMALL = ["--index-size", "60000", "--nq", "2000", "--steps", "2", "--warmup", "1", "--full"]  # (roofline, CPU baseline, ...: --full)
 
 
 def _last_json(out):
@@ -58,6 +58,38 @@ def test_single_gpu_line_has_the_contract_fields(tmp_path):
     t = d["timed_regions"]
     assert t["n"] == 3 and t["min"] <= t["median"] <= t["max"] and abs(t["median"] - d["value"]) < 1e-4 * d["value"]
     assert full["value"] == d["value"] and full["ms_per_step"] == d["ms_per_step"] and d["value_pcie_inclusive"] > 0
+
+
+def test_plain_run_times_exactly_steps_and_dumps_its_outputs(tmp_path):
+    # without --full: one timed region of exactly --steps launches, the contract fields and nothing measured beyond them;
+    # --dump-outputs writes what the last timed step returned -- the same bits in two runs with the same arguments
+    import numpy as np
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--index-size", "60000", "--nq", "2000", "--steps", "3", "--warmup", "1"]
+    lines = []
+    for run in range(2):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / ("run%d" % run))], capture_output=True, text=True,
+                             timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(_last_json(out.stdout))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["metric"] == "qps_at_recall10_ge_0.95" and d["unit"] == "queries/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["timed_regions"]["n"] == 1 and d["dtype"] == "f32"
+    assert abs(d["value"] - 2000 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]  # value and ms_per_step: the same 3 steps
+    assert d["config"]["recall_at_10"] >= 0.95 and d["config"]["recall_min_over_timed_batches"] >= 0.95
+    assert "roofline" not in d and "cpu_baseline" not in d and d["secondary"] == [] and d["full_record"] is None
+    assert lines[1]["config"]["ef_search"] == d["config"]["ef_search"]
+    for name, dtype, shape in (("distances", np.float32, (2000, 10)), ("labels", np.float64, (2000, 10)),
+                               ("result_counts", np.float64, (2000,)), ("n_dist", np.float64, (2000,)),
+                               ("n_hops", np.float64, (2000,))):
+        a, b = (np.load(str(tmp_path / ("run%d" % r) / (name + ".npy"))) for r in range(2))
+        assert a.dtype == dtype and a.shape == shape, (name, a.dtype, a.shape)
+        assert np.array_equal(a, b), name
+    labels = np.load(str(tmp_path / "run0" / "labels.npy"))
+    assert labels.min() >= 0 and labels.max() < 60000
+    assert (np.diff(np.load(str(tmp_path / "run0" / "distances.npy")), axis=1) >= 0).all()
 
 
 def test_default_run_carries_the_other_configurations(tmp_path):
@@ -134,7 +166,7 @@ def test_bench_spawns_its_own_ranks_and_runs_other_configs(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c4", "--index-size", "50000",
-           "--nq", "1000", "--steps", "2", "--warmup", "1", "--no-secondary"]
+           "--nq", "1000", "--steps", "2", "--warmup", "1", "--no-secondary", "--full"]
     d, full = _run(cmd, tmp_path, env=env)
     assert d["n_gpus"] == 2 and d["config"]["workload"].startswith("c4 ") and d["value"] > 0
     assert d["roofline"]["frac_of_gather_ceiling"] > 0 and d["roofline"]["frac"] > 0  # (a 25 MB table gathers from L2: ceiling > HBM peak)

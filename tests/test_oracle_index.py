@@ -42,22 +42,32 @@ def test_save_load_identical_search(oracle_mod, tmp_path, metric, dt):
     assert np.array_equal(d1, d2) and np.array_equal(l1, l2)
 
 
-def test_search_on_reference_distance_kernels_is_identical_on_integer_data(oracle_mod, ref):
+def test_search_on_reference_distance_kernels_is_identical_on_integer_data(oracle_mod, ref_answers):
+    import hashlib
+
+    def packed(d, l, st, blob):  # distance bits, ids, counters and the graph's SHA-256 as one uint64 vector
+        return np.concatenate([d.view(np.uint32).ravel().astype(np.uint64), l.astype(np.int64).ravel().view(np.uint64),
+                               st["n_dist"].astype(np.uint64).ravel(), st["n_hops"].astype(np.uint64).ravel(),
+                               np.frombuffer(hashlib.sha256(np.ascontiguousarray(blob).tobytes()).digest(), dtype=np.uint64)])
+
     X, Q = ds.sift_like(4000, 200)
     ix = oracle_mod.OracleIndex.create("l2", 128, 4000, 32)
     ix.add(X, 100)
     blob_own = ix.blob().copy()
     d1, l1, s1 = ix.search(Q, 10, 100, stats=True)
-    # same graph, reference's compiled AVX-512 kernel as the distance
-    assert ix.use_reference_distance(True)
-    d2, l2, s2 = ix.search(Q, 10, 100, stats=True)
-    assert np.array_equal(d1, d2) and np.array_equal(l1, l2)
-    assert np.array_equal(s1["n_dist"], s2["n_dist"]) and np.array_equal(s1["n_hops"], s2["n_hops"])
-    # and the single-thread BUILD is identical too (construction goes through the same distances)
-    ix3 = oracle_mod.OracleIndex.create("l2", 128, 4000, 32)
-    ix3.use_reference_distance(True)
-    ix3.add(X, 100)
-    assert np.array_equal(ix3.blob(), blob_own)
+
+    def on_reference_distance(_):
+        # same graph, reference's compiled AVX-512 kernel as the distance ...
+        assert ix.use_reference_distance(True)
+        d2, l2, s2 = ix.search(Q, 10, 100, stats=True)
+        # ... and the single-thread BUILD on it (construction goes through the same distances)
+        ix3 = oracle_mod.OracleIndex.create("l2", 128, 4000, 32)
+        ix3.use_reference_distance(True)
+        ix3.add(X, 100)
+        return packed(d2, l2, s2, ix3.blob())
+
+    want = ref_answers("oracle_index/reference_distance/sift_like_4000", on_reference_distance)
+    assert np.array_equal(packed(d1, l1, s1, blob_own), want)
 
 
 def test_recall_and_counters(oracle_mod):

@@ -1,5 +1,6 @@
 """The cereal-free parts of the reference that the product re-implements on the host, pinned against the EXECUTED reference
-(oracle/_ref = the reference's own headers compiled where they lie, oracle/ref_cereal_free.cpp):
+(oracle/_ref = the reference's own headers compiled where they lie, oracle/ref_cereal_free.cpp; its answers on these inputs
+are stored in tests/golden/reference/answers.npz, see conftest.ReferenceAnswers):
 
   * include/flatnav/util/Reordering.h  gOrder / rcmOrder  == reference Reordering.h:27-200 + GorderPriorityQueue.h:14-109 --
     the SAME PERMUTATION, element for element, ties in score / degree included ("pinned, not isomorphic");
@@ -64,23 +65,30 @@ def _random_graph(rng, kind):
 KINDS = ["regular", "ragged", "ring", "sparse", "dupes"]
 
 
-def test_gorder_and_rcm_return_the_references_permutation(own, ref):
-    if not hasattr(ref, "ref_gorder"):
-        pytest.skip("oracle/_ref predates round 6 (rebuild it in the dev container: make -C oracle ref)")
+def _ref_orders(ref, flat, offsets, n, ws):
+    """The reference's gOrder(table, w) for every w of `ws`, then its rcmOrder(table): one row each."""
+    out = np.empty((len(ws) + 1, n), np.uint32)
+    for j, w in enumerate(ws):
+        ref.ref_gorder(flat.ctypes.data, offsets.ctypes.data, n, w, out[j].ctypes.data)
+    ref.ref_rcm(flat.ctypes.data, offsets.ctypes.data, n, out[-1].ctypes.data)
+    return out
+
+
+def test_gorder_and_rcm_return_the_references_permutation(own, ref_answers):
     rng = np.random.default_rng(60)
     checked = 0
+    WS = (5, 1, 0, 2, 17)  # Index.h:418,429 uses w = 5
     for trial in range(60):
         table = _random_graph(rng, KINDS[trial % len(KINDS)])
         n = len(table)
         flat, offsets = _csr(table)
-        for w in (5, 1, 0, 2, 17):  # Index.h:418,429 uses w = 5
-            a, b = np.empty(n, np.uint32), np.empty(n, np.uint32)
-            ref.ref_gorder(flat.ctypes.data, offsets.ctypes.data, n, w, a.ctypes.data)
+        want = ref_answers("reordering/random_graph/%d" % trial, lambda ref: _ref_orders(ref, flat, offsets, n, WS))
+        for j, w in enumerate(WS):
+            a, b = want[j], np.empty(n, np.uint32)
             own.own_gorder(flat.ctypes.data, offsets.ctypes.data, n, w, b.ctypes.data)
             assert np.array_equal(a, b), (trial, KINDS[trial % len(KINDS)], n, w)
             assert sorted(a.tolist()) == list(range(n))
-        a, b = np.empty(n, np.uint32), np.empty(n, np.uint32)
-        ref.ref_rcm(flat.ctypes.data, offsets.ctypes.data, n, a.ctypes.data)
+        a, b = want[-1], np.empty(n, np.uint32)
         own.own_rcm(flat.ctypes.data, offsets.ctypes.data, n, b.ctypes.data)
         assert np.array_equal(a, b), (trial, KINDS[trial % len(KINDS)], n)
         assert sorted(a.tolist()) == list(range(n))
@@ -88,10 +96,8 @@ def test_gorder_and_rcm_return_the_references_permutation(own, ref):
     assert checked == 60
 
 
-def test_gorder_and_rcm_on_a_real_index_graph(own, ref, oracle_mod):
+def test_gorder_and_rcm_on_a_real_index_graph(own, ref_answers, oracle_mod):
     # the out-degree table of a built index (Index.h:240-260: links that are not self-loops), 3000 nodes, M = 16
-    if not hasattr(ref, "ref_gorder"):
-        pytest.skip("oracle/_ref predates round 6")
     from flatnav_amd import datasets as ds
 
     X, _ = ds.sift_like(3000, 1)
@@ -101,57 +107,69 @@ def test_gorder_and_rcm_on_a_real_index_graph(own, ref, oracle_mod):
     links = blob[:, ix.data_size:ix.data_size + 64].copy().view(np.uint32)
     table = [[int(v) for v in links[u] if v != u] for u in range(3000)]
     flat, offsets = _csr(table)
-    for fn_ref, fn_own, args in ((ref.ref_gorder, own.own_gorder, (5,)), (ref.ref_rcm, own.own_rcm, ())):
-        a, b = np.empty(3000, np.uint32), np.empty(3000, np.uint32)
-        fn_ref(flat.ctypes.data, offsets.ctypes.data, 3000, *args, a.ctypes.data)
+    want = ref_answers("reordering/index_graph_3000", lambda ref: _ref_orders(ref, flat, offsets, 3000, (5,)))
+    for a, fn_own, args in ((want[0], own.own_gorder, (5,)), (want[1], own.own_rcm, ())):
+        b = np.empty(3000, np.uint32)
         fn_own(flat.ctypes.data, offsets.ctypes.data, 3000, *args, b.ctypes.data)
         assert np.array_equal(a, b)
 
 
-def test_execute_in_parallel_covers_every_index_once(own, ref):
-    if not hasattr(ref, "ref_execute_in_parallel"):
-        pytest.skip("oracle/_ref predates round 6")
+def test_execute_in_parallel_covers_every_index_once(own, ref_answers):
+    def run(fn, start, end, threads, extra):  # -> [return code] + the hit count of every index
+        hits = np.zeros(max(1, end - start), dtype=np.uint32)
+        return np.concatenate([[fn(start, end, threads, extra, hits.ctypes.data)], hits]).astype(np.int64)
+
     for start, end, threads, extra in ((0, 1000, 4, 0), (7, 8, 3, 2), (5, 5, 2, 0), (9, 3, 2, 1), (0, 50000, 8, 3), (0, 13, 1, 0)):
         n = max(0, end - start)
-        got = []
-        for fn in (ref.ref_execute_in_parallel, own.own_execute_in_parallel):
-            hits = np.zeros(max(1, n), dtype=np.uint32)
-            assert fn(start, end, threads, extra, hits.ctypes.data) == 0
-            got.append(hits)
+        args = (start, end, threads, extra)
+        got = [ref_answers("execute_in_parallel/%d_%d_%d_%d" % args, lambda ref: run(ref.ref_execute_in_parallel, *args)),
+               run(own.own_execute_in_parallel, *args)]
+        assert got[0][0] == 0 and got[1][0] == 0
         assert np.array_equal(got[0], got[1])
-        assert (got[1][:n] == 1 + extra).all()  # each index handed out exactly once, the extra argument forwarded by value
-    z = np.zeros(4, dtype=np.uint32)
-    assert ref.ref_execute_in_parallel(0, 4, 0, 0, z.ctypes.data) == 1  # Multithreading.h:22-24
-    assert own.own_execute_in_parallel(0, 4, 0, 0, z.ctypes.data) == 1
-    assert not z.any()
+        assert (got[1][1:n + 1] == 1 + extra).all()  # each index handed out exactly once, the extra argument forwarded by value
+    # Multithreading.h:22-24: zero threads -> an error, nothing run
+    assert ref_answers("execute_in_parallel/zero_threads", lambda ref: run(ref.ref_execute_in_parallel, 0, 4, 0, 0)).tolist() == [1, 0, 0, 0, 0]
+    assert run(own.own_execute_in_parallel, 0, 4, 0, 0).tolist() == [1, 0, 0, 0, 0]
 
 
-def test_datatype_ordinals_names_and_sizes(own, ref):
-    if not hasattr(ref, "ref_datatype_name"):
-        pytest.skip("oracle/_ref predates round 6")
+LABELS = ("uint8", "uint16", "uint32", "uint64", "int8", "int16", "int32", "int64", "float16", "float32", "float64", "undefined",
+          "bfloat16", "")
+
+
+def _datatype_numbers(L, p):
+    """enum size, then size / ctype bytes of ordinals 0..13, then the ordinal of every label -- of the reference (p = "ref_")
+    or of the product's header (p = "own_")."""
+    f = lambda name: getattr(L, p + name)  # noqa: E731
+    return np.array([f("datatype_enum_bytes")()] + [v for o in range(14) for v in (f("datatype_size")(o), f("datatype_ctype_bytes")(o))] +
+                    [f("datatype_ordinal")(label.encode()) for label in LABELS], dtype=np.int64)
+
+
+def _datatype_names(L, p):
+    return np.array([getattr(L, p + "datatype_name")(o) or b"<null>" for o in range(14)])
+
+
+def test_datatype_ordinals_names_and_sizes(own, ref_answers):
     from flatnav_amd import hip
     from oracle import oracle as orc
 
-    assert ref.ref_datatype_enum_bytes() == own.own_datatype_enum_bytes() == 4  # the int32 at offset 0 of an index file
-    for ordinal in range(0, 14):
-        assert ref.ref_datatype_name(ordinal) == own.own_datatype_name(ordinal), ordinal
-        assert ref.ref_datatype_size(ordinal) == own.own_datatype_size(ordinal), ordinal
-        assert ref.ref_datatype_ctype_bytes(ordinal) == own.own_datatype_ctype_bytes(ordinal), ordinal
-    for label in ("uint8", "uint16", "uint32", "uint64", "int8", "int16", "int32", "int64", "float16", "float32", "float64",
-                  "undefined", "bfloat16", ""):
-        assert ref.ref_datatype_ordinal(label.encode()) == own.own_datatype_ordinal(label.encode()), label
+    want_numbers = ref_answers("datatype/numbers", lambda ref: _datatype_numbers(ref, "ref_"))
+    want_names = ref_answers("datatype/names", lambda ref: _datatype_names(ref, "ref_"))
+    assert want_numbers[0] == 4  # the int32 at offset 0 of an index file
+    assert np.array_equal(_datatype_numbers(own, "own_"), want_numbers)
+    assert np.array_equal(_datatype_names(own, "own_"), want_names)
     # the three index element types: the ordinals the oracle, the ctypes binding and the C ABI use are the reference's
+    ordinal_of = dict(zip(LABELS, want_numbers[1 + 2 * 14:].tolist()))
     for label, ordinal in (("uint8", 0), ("int8", 4), ("float32", 9)):
-        assert ref.ref_datatype_ordinal(label.encode()) == ordinal == orc.DTYPE_ORD[label] == hip.DTYPE_ORD[label]
+        assert ordinal_of[label] == ordinal == orc.DTYPE_ORD[label] == hip.DTYPE_ORD[label]
 
 
 @pytest.mark.parametrize("methods", [["gorder"], ["rcm"], ["gorder", "rcm"]], ids=["gorder", "rcm", "gorder+rcm"])
-def test_index_reorder_applies_the_references_permutation(ref, methods):
+def test_index_reorder_applies_the_references_permutation(ref_answers, methods):
     # The whole product path Index::doGraphReordering -> relabel (reference Index.h:412-440, 872-926) through the Python
     # surface: after reorder(methods) node u sits at P[u] with every link rewritten through P and its label travelling along,
     # where P is what the REFERENCE's gOrder(table, 5) / rcmOrder(table) return on the table before.  No GPU involved.
-    if not hasattr(ref, "ref_gorder"):
-        pytest.skip("oracle/_ref predates round 6")
+    import hashlib
+
     from flatnav_amd import build_host
 
     build_host.build()
@@ -173,11 +191,10 @@ def test_index_reorder_applies_the_references_permutation(ref, methods):
         table = ix.get_graph_outdegree_table()
         assert table == [[int(v) for v in links[u] if v != u] for u in range(N)]  # Index.h:240-260
         flat, offsets = _csr(table)
-        P = np.empty(N, np.uint32)
-        if method == "gorder":
-            ref.ref_gorder(flat.ctypes.data, offsets.ctypes.data, N, 5, P.ctypes.data)
-        else:
-            ref.ref_rcm(flat.ctypes.data, offsets.ctypes.data, N, P.ctypes.data)
+        # (keyed by the table itself: a stored permutation only ever answers the table it was computed on)
+        key = hashlib.sha256(flat.tobytes() + offsets.tobytes()).hexdigest()[:16]
+        P = ref_answers("reordering/index_reorder/%s/%s" % (method, key),
+                        lambda ref: _ref_orders(ref, flat, offsets, N, (5,))[0 if method == "gorder" else 1])
         want_vec, want_links, want_labels = np.empty_like(vec), np.empty_like(links), np.empty_like(labels)
         want_vec[P], want_links[P], want_labels[P] = vec, P[links], labels
         ix.reorder([method])

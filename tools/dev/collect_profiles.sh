@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the round's profile set on the GPU box into gpurun_out/profile_set (run through gpurun from the repo root):
-#   1. the default bench invocation (the contract line + every further configuration);
+#   1. the full bench invocation (--full: the contract line + every further configuration);
 #   2. per configuration, at the ef that run selected: rocprofv3 --kernel-trace --stats of a bench command (the timed
 #      region's launches), and separate --pmc passes for HBM traffic (FETCH_SIZE / WRITE_SIZE);
 #   3. SQ instruction-mix / wait counters for the float32 headline and the two uint8 indexes.
@@ -18,7 +18,7 @@ if [ ! -s $O/bench.json ] && [ -s $R/profiles/${PROFILE_TAG:-r6}_bench.json ] &&
 fi
 if [ ! -s $O/bench.json ]; then
   # (round 5: stdout is the <= 4 KB contract line; the full record -- what the steps below read -- goes to --full-record)
-  python $R/bench.py --steps 20 --warmup 5 --full-record $O/bench.json > $O/bench_line.json 2> $O/bench.log
+  python $R/bench.py --steps 20 --warmup 5 --full --time-budget 3600 --full-record $O/bench.json > $O/bench_line.json 2> $O/bench.log
 fi
 cd /tmp && export TMPDIR=/tmp
 for C in $CONFIGS; do
@@ -28,7 +28,7 @@ d = json.load(open('$O/bench.json'))
 e = d if '$C' == 'c2' else d['$C']
 print(e['config']['ef_search'])")
   STEPS=20; case $C in c3*|c5*) STEPS=6;; esac
-  ARGS="--config $C --ef $EF --no-cpu-baseline --no-secondary --sustain-seconds 0 --warmup 3 --regions 1"
+  ARGS="--config $C --ef $EF --full --no-cpu-baseline --no-secondary --sustain-seconds 0 --warmup 3 --regions 1"
   echo "== $C ef=$EF"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$C -o bench -- python3 $R/bench.py $ARGS --steps $STEPS --full-record $O/trace_$C.json > /dev/null 2> $O/trace_$C.log
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch_$C -o bench -- python3 $R/bench.py $ARGS --steps 3 --full-record $O/fetch_$C.json > /dev/null 2>&1
