@@ -34,8 +34,8 @@ if _core is not None:
         from ._core.data_type import DataType
 
     class _IndexModule:
-        from ._core.index import (IndexIPFloat, IndexIPInt8, IndexIPUint8, IndexL2Float, IndexL2Int8, IndexL2Uint8,
-                                  create)
+        from ._core.index import (IndexIPFloat, IndexIPFloat16, IndexIPInt8, IndexIPUint8, IndexL2Float, IndexL2Float16,
+                                  IndexL2Int8, IndexL2Uint8, create)
 
     index = _IndexModule
     _sys.modules[__name__ + ".index"] = _IndexModule

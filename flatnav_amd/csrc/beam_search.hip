@@ -70,7 +70,15 @@ int fail(int code, const std::string& msg) {
       return fail(FNV_ERR_NO_DEVICE, std::string(#expr) + " failed: " + hipGetErrorString(_e));        \
   } while (0)
 
-size_t dtype_size(int dt) { return dt == FNV_DTYPE_FLOAT32 ? 4 : (dt == FNV_DTYPE_UINT8 || dt == FNV_DTYPE_INT8) ? 1 : 0; }
+size_t dtype_size(int dt) {
+  switch (dt) {
+    case FNV_DTYPE_FLOAT32: return 4;
+    case FNV_DTYPE_FLOAT16: return 2;
+    case FNV_DTYPE_UINT8:
+    case FNV_DTYPE_INT8: return 1;
+    default: return 0;
+  }
+}
 
 // Every entry point works on its index's device and gives the calling thread its current device back on every exit
 // path: a library call must not move a torch (or any other HIP) caller's allocations to another GPU.
@@ -152,7 +160,7 @@ const KernelTable& kernel_table(int, int) {
 #else
 // Product builds: the instantiations live in kernel_inst.hip objects (one per family x element type x metric).
 const KernelTable& kernel_table(int dtype, int metric) {
-  static KernelTable tables[6];
+  static KernelTable tables[8];
   static std::once_flag once;
   std::call_once(once, [] {
     int i = 0;
@@ -171,7 +179,14 @@ const KernelTable& kernel_table(int dtype, int metric) {
     FNV_FOR_EACH_TYPE_METRIC(FNV_FILL)
 #undef FNV_FILL
   });
-  const int t = dtype == FNV_DTYPE_FLOAT32 ? 0 : dtype == FNV_DTYPE_UINT8 ? 1 : 2;  // order of FNV_FOR_EACH_TYPE_METRIC
+  int t;  // order of FNV_FOR_EACH_TYPE_METRIC; every caller has passed validate_geometry (dtype_size != 0)
+  switch (dtype) {
+    case FNV_DTYPE_FLOAT32: t = 0; break;
+    case FNV_DTYPE_UINT8: t = 1; break;
+    case FNV_DTYPE_INT8: t = 2; break;
+    case FNV_DTYPE_FLOAT16: t = 3; break;
+    default: fprintf(stderr, "flatnav_hip: kernel_table(%d): unsupported data type\n", dtype); abort();  // (unreachable)
+  }
   return tables[2 * t + (metric == FNV_METRIC_IP ? 1 : 0)];
 }
 #endif

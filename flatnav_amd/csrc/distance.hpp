@@ -64,6 +64,49 @@ struct Dist<float, METRIC> {
   static __device__ __forceinline__ float finish(float s) { return METRIC == FNV_METRIC_L2 ? s : 1.0f - s; }
 };
 
+// float16 rows (IEEE binary16, 8 elements per chunk): every element is widened exactly to f32 and the sums are the float
+// path's f32 arithmetic on the widened values -- nothing is ever rounded to f16.  L2: one v_fma_mix_f32 per element gives
+// fma(x, 1.0, -y) = the f32 difference of the widened operands (one rounding, as v_sub_f32 of the converted values), then
+// v_pk_fma_f32 squares and accumulates: 8 + 4 VALU per chunk instead of 16 conversions + 4 v_pk_add_f32 + 4 v_pk_fma_f32
+// (hipcc does not form the mixed instruction from fpext + fsub by itself).  IP: v_dot2_f32_f16 (products of two binary16
+// values are exact in f32), 4 per chunk into two accumulators.
+template <int METRIC>
+struct Dist<_Float16, METRIC> {
+  typedef f32x2 acc_t;
+  typedef int qacc_t;  // unused for float rows
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  static __device__ __forceinline__ f32x2 zero() { return f32x2{0.f, 0.f}; }
+  static __device__ __forceinline__ int qzero() { return 0; }
+  static __device__ __forceinline__ int qchunk(int q, const uint4&) { return q; }
+  // {lo(x) - lo(y), hi(x) - hi(y)} in f32 from two packed pairs
+  static __device__ __forceinline__ f32x2 diff(uint32_t x, uint32_t y) {
+    f32x2 t;
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[1,0,1]" : "=v"(t.x) : "v"(x), "v"(y));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(t.y) : "v"(x), "v"(y));
+    return t;
+  }
+  static __device__ __forceinline__ float dot(uint32_t x, uint32_t y, float c) {
+    return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, x), __builtin_bit_cast(h2, y), c, false);
+  }
+  static __device__ __forceinline__ f32x2 chunk(f32x2 acc, const uint4& x, const uint4& y) {
+    if (METRIC == FNV_METRIC_L2) {
+      const f32x2 t0 = diff(x.x, y.x), t1 = diff(x.y, y.y), t2 = diff(x.z, y.z), t3 = diff(x.w, y.w);
+      acc = __builtin_elementwise_fma(t0, t0, acc);
+      acc = __builtin_elementwise_fma(t1, t1, acc);
+      acc = __builtin_elementwise_fma(t2, t2, acc);
+      acc = __builtin_elementwise_fma(t3, t3, acc);
+    } else {
+      acc.x = dot(x.x, y.x, acc.x);
+      acc.y = dot(x.y, y.y, acc.y);
+      acc.x = dot(x.z, y.z, acc.x);
+      acc.y = dot(x.w, y.w, acc.y);
+    }
+    return acc;
+  }
+  static __device__ __forceinline__ float lane_sum(f32x2 a, int) { return a.x + a.y; }
+  static __device__ __forceinline__ float finish(float s) { return METRIC == FNV_METRIC_L2 ? s : 1.0f - s; }
+};
+
 // 1-byte element types: four products per instruction (v_dot4_u32_u8 / v_dot4_i32_i8), exact int32 accumulation --
 // the arithmetic of the reference's AVX-512 uint8 path (SquaredL2SimdExtensions.h:32-76: widen, multiply, add into
 // 32-bit lanes) and, while sums stay below 2^24, of its scalar float loops (L2DistanceDispatcher.h:10-17,

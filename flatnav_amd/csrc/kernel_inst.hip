@@ -3,7 +3,7 @@
 // families: 0 exact two-heap kernel + entry scan, 3 wiring kernels, 4 merged beam (<= 256 entries in registers),
 // 5 merged beam (<= 64 entries in registers), 6 merged beam (LDS, any width), 7 merged beam (<= 128 in registers), 8-11 the
 // DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS).  flatnav_amd/build.py compiles the
-// 60 combinations in parallel and links them with beam_search.hip.
+// 80 combinations in parallel and links them with beam_search.hip.
 #include <hip/hip_runtime.h>
 
 #include "kernel_table.h"

@@ -50,7 +50,8 @@ struct KernelTable {
 
 // X(element type, type tag, metric ordinal, metric tag)
 #define FNV_FOR_EACH_TYPE_METRIC(X) \
-  X(float, f32, 0, l2) X(float, f32, 1, ip) X(uint8_t, u8, 0, l2) X(uint8_t, u8, 1, ip) X(int8_t, i8, 0, l2) X(int8_t, i8, 1, ip)
+  X(float, f32, 0, l2) X(float, f32, 1, ip) X(uint8_t, u8, 0, l2) X(uint8_t, u8, 1, ip) X(int8_t, i8, 0, l2) X(int8_t, i8, 1, ip) \
+  X(_Float16, f16, 0, l2) X(_Float16, f16, 1, ip)
 
 // one filler per kernel family and (type, metric), each defined by one compilation of kernel_inst.hip
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag)             \

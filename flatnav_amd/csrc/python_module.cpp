@@ -2,7 +2,7 @@
 //
 // Python surface of the reference's `flatnav._core` (python-bindings/src/flatnav/bindings.cpp:
 // 426-539): submodules `index` (create(), IndexL2Float / IndexIPFloat / IndexL2Uint8 /
-// IndexIPUint8 / IndexL2Int8 / IndexIPInt8) and `data_type` (DataType), enum MetricType,
+// IndexIPUint8 / IndexL2Int8 / IndexIPInt8, and IndexL2Float16 / IndexIPFloat16) and `data_type` (DataType), enum MetricType,
 // __version__.  Methods, argument names, defaults, returned dtypes/shapes and raised exception
 // types follow the reference; `search` hands the whole batch to the GPU in one call
 // (flatnav::Index::searchBatch -> C ABI fnv_search_batch) instead of looping on the host.
@@ -44,6 +44,15 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
   int _next_label = 0;
   std::unique_ptr<index_t> _index;
 
+  // `a` as a C-contiguous array of the index element type.  float16 goes through numpy (pybind11 has no half type):
+  // np.ascontiguousarray(a, float16) rounds float32 / float64 to nearest even, as forcecast turns float64 into float32.
+  static py::array elements(const py::array& a) {
+    if constexpr (kType == DataType::float16)
+      return py::module_::import("numpy").attr("ascontiguousarray")(a, "float16").cast<py::array>();
+    else
+      return a.cast<dense_array<element_t>>();
+  }
+
  public:
   explicit PyIndex(std::unique_ptr<index_t> loaded) : _dim(static_cast<int>(loaded->dataDimension())), _index(std::move(loaded)) {}
 
@@ -61,7 +70,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
   // device=True (extension): the insertions' beam searches run on the GPU in batches (Index::addBatchDevice).
   void add(const py::array& data_any, int ef_construction, int num_initializations, py::object labels, bool device,
            uint32_t device_max_batch, bool device_wiring, uint32_t device_bootstrap) {
-    dense_array<element_t> data = data_any.cast<dense_array<element_t>>();
+    py::array data = elements(data_any);
     if (data.ndim() != 2 || data.shape(1) != _dim)
       throw std::invalid_argument("Data has incorrect dimensions. data.ndim() = `" + std::to_string(data.ndim()) +
                                   "`. Expected 2D array with dimensions (num_vectors, dim).");
@@ -78,7 +87,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
       }
       if (ids.size() != count) throw std::invalid_argument("Incorrect number of labels.");
     }
-    void* raw = const_cast<element_t*>(data.data());
+    void* raw = const_cast<void*>(data.data());
     py::gil_scoped_release release;  // the builder spawns its own threads
     if (device) {
       typename index_t::DeviceBuildOptions opt;
@@ -93,7 +102,18 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
 
   // allocate_nodes(data) -> self   [bindings.cpp:308-324]: vectors only, no edges (used before
   // build_graph_links); labels continue from the wrapper's own counter.
-  std::shared_ptr<PyIndex> allocateNodes(const dense_array<float>& data) {
+  std::shared_ptr<PyIndex> allocateNodes(const py::array& data_any) {
+    if constexpr (kType == DataType::float16) {  // rows are stored as float16 (the other types keep the reference's float rows)
+      py::array data = elements(data_any);
+      if (data.ndim() != 2 || data.shape(1) != _dim) throw std::invalid_argument("Data has incorrect dimensions.");
+      for (py::ssize_t row = 0; row < data.shape(0); ++row) {
+        uint32_t node;
+        int label = _next_label++;
+        _index->allocateNode(const_cast<void*>(data.data(row, 0)), label, node);
+      }
+      return this->shared_from_this();
+    }
+    dense_array<float> data = data_any.cast<dense_array<float>>();
     if (data.ndim() != 2 || data.shape(1) != _dim) throw std::invalid_argument("Data has incorrect dimensions.");
     for (py::ssize_t row = 0; row < data.shape(0); ++row) {
       uint32_t node;
@@ -105,7 +125,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
 
   // search(queries, K, ef_search, num_initializations=100) -> (float32[Q,K], int32[Q,K])
   py::tuple search(const py::array& queries_any, int K, int ef_search, int num_initializations) {
-    dense_array<element_t> queries = queries_any.cast<dense_array<element_t>>();
+    py::array queries = elements(queries_any);
     if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
     if (K <= 0) throw std::invalid_argument("K must be positive.");
     const py::ssize_t nq = queries.shape(0);
@@ -113,7 +133,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
     std::vector<int32_t> counts(static_cast<size_t>(nq));
     {
-      const element_t* qptr = queries.data();
+      const void* qptr = queries.data();
       float* dptr = dist.mutable_data();
       int* lptr = labels.mutable_data();
       py::gil_scoped_release release;  // the GPU works; other Python threads may run
@@ -128,7 +148,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
 
   // search_single(query, K, ef_search, num_initializations=100) -> (float32[K], int32[K])
   py::tuple searchSingle(const py::array& query_any, int K, int ef_search, int num_initializations) {
-    dense_array<element_t> query = query_any.cast<dense_array<element_t>>();
+    py::array query = elements(query_any);
     if (query.ndim() != 1 || query.shape(0) != _dim) throw std::invalid_argument("Query has incorrect dimensions.");
     auto top = _index->search(query.data(), K, ef_search, num_initializations);
     if (static_cast<int>(top.size()) != K)  // bindings.cpp:134-137
@@ -254,6 +274,7 @@ PYBIND11_MODULE(_core, m) {
       .value("float32", DataType::float32)
       .value("int8", DataType::int8)
       .value("uint8", DataType::uint8)
+      .value("float16", DataType::float16)
       .export_values();
 
   py::enum_<MetricType>(m, "MetricType").value("L2", MetricType::L2).value("IP", MetricType::IP);
@@ -265,6 +286,8 @@ PYBIND11_MODULE(_core, m) {
   bindIndex<InnerProductDistance<DataType::float32>, DataType::float32>(index, "IndexIPFloat");
   bindIndex<InnerProductDistance<DataType::int8>, DataType::int8>(index, "IndexIPInt8");
   bindIndex<InnerProductDistance<DataType::uint8>, DataType::uint8>(index, "IndexIPUint8");
+  bindIndex<SquaredL2Distance<DataType::float16>, DataType::float16>(index, "IndexL2Float16");
+  bindIndex<InnerProductDistance<DataType::float16>, DataType::float16>(index, "IndexIPFloat16");
 
   index.def(
       "create",
@@ -277,6 +300,8 @@ PYBIND11_MODULE(_core, m) {
             return makeIndex<DataType::int8>(distance_type, dim, dataset_size, max_edges_per_node, verbose, collect_stats);
           case DataType::uint8:
             return makeIndex<DataType::uint8>(distance_type, dim, dataset_size, max_edges_per_node, verbose, collect_stats);
+          case DataType::float16:
+            return makeIndex<DataType::float16>(distance_type, dim, dataset_size, max_edges_per_node, verbose, collect_stats);
           default:
             throw std::runtime_error("Unsupported data type");
         }

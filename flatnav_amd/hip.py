@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLATNAV_HIP_LIB") or os.path.join(HERE, "libflatnav_hip.so")
 
 FNV_OK, FNV_ERR_INVALID, FNV_ERR_RUNTIME, FNV_ERR_NO_DEVICE, FNV_ERR_CAPACITY = 0, 1, 2, 3, 4
-DTYPE_ORD = {"float32": 9, "uint8": 0, "int8": 4}
+DTYPE_ORD = {"float32": 9, "uint8": 0, "int8": 4, "float16": 8}
 ORD_DTYPE = {v: k for k, v in DTYPE_ORD.items()}
 METRIC_ORD = {"l2": 0, "angular": 1, "ip": 1}
 
@@ -119,7 +119,7 @@ def device_count() -> int:
 
 
 def _np_dtype(name: str):
-    return {"float32": np.float32, "uint8": np.uint8, "int8": np.int8}[name]
+    return {"float32": np.float32, "uint8": np.uint8, "int8": np.int8, "float16": np.float16}[name]
 
 
 def search_multi(indexes, queries, K: int, ef_search: int, num_initializations: int = 100, stats: bool = False):

@@ -11,6 +11,9 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
+
+#include <flatnav/util/Datatype.h>
 
 namespace flatnav::util::host {
 
@@ -43,6 +46,23 @@ inline float innerProductDistance(const float* a, const float* b, std::size_t di
     for (int l = 0; l < 16; ++l) lanes[l] += a[i + l] * b[i + l];
   for (int l = 0; i < dim; ++i, ++l) lanes[l] += a[i] * b[i];
   return 1.0f - fold16(lanes);
+}
+
+// float16: both operands are widened exactly to float and the float kernels above run on them, so a float16 index
+// builds the same graph as a float32 index of the widened data.
+inline const float* widened(const float16_t* v, std::size_t dim, int which) {
+  thread_local std::vector<float> buf[2];
+  buf[which].resize(dim);
+  widen(v, buf[which].data(), dim);
+  return buf[which].data();
+}
+
+inline float squaredL2(const float16_t* a, const float16_t* b, std::size_t dim) {
+  return squaredL2(widened(a, dim, 0), widened(b, dim, 1), dim);
+}
+
+inline float innerProductDistance(const float16_t* a, const float16_t* b, std::size_t dim) {
+  return innerProductDistance(widened(a, dim, 0), widened(b, dim, 1), dim);
 }
 
 // Exact integer accumulation; equal to the reference's float / int32 accumulation whenever the

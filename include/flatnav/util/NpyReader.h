@@ -1,7 +1,7 @@
 // flatnav/util/NpyReader.h -- minimal reader / writer for NumPy .npy files (format versions 1.0 - 3.0), enough for the
 // ann-benchmarks style inputs of the command-line tools (reference: tools/construct_npy.cpp, tools/query_npy.cpp load
 // 2-D float32 / int32 arrays with the third-party cnpy; this is an own, dependency-free reader).
-// Supported: little-endian or single-byte dtypes ('<f4', '<i4', '<u4', '<i8', '<f8', '|u1', '|i1'), C order.
+// Supported: little-endian or single-byte dtypes ('<f2', '<f4', '<i4', '<u4', '<i8', '<f8', '|u1', '|i1'), C order.
 #pragma once
 
 #include <cstdint>
@@ -9,7 +9,10 @@
 #include <fstream>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
+
+#include <flatnav/util/Datatype.h>
 
 namespace flatnav::util {
 
@@ -29,20 +32,30 @@ struct NpyArray {
     if (sizeof(T) != word_size) throw std::runtime_error("npy: element size mismatch for dtype " + dtype);
     return reinterpret_cast<T*>(bytes.data());
   }
-  // Values converted to T (e.g. int64 ground truth -> int32).
+  // Values converted to T (e.g. int64 ground truth -> int32; any type -> float16_t rounds to nearest even via float).
   template <typename T>
   std::vector<T> as() const {
     std::vector<T> out(numValues());
-    const char* p = bytes.data();
-    for (size_t i = 0; i < out.size(); ++i, p += word_size) {
-      if (dtype == "<f4") { float v; std::memcpy(&v, p, 4); out[i] = static_cast<T>(v); }
-      else if (dtype == "<f8") { double v; std::memcpy(&v, p, 8); out[i] = static_cast<T>(v); }
-      else if (dtype == "<i4") { int32_t v; std::memcpy(&v, p, 4); out[i] = static_cast<T>(v); }
-      else if (dtype == "<u4") { uint32_t v; std::memcpy(&v, p, 4); out[i] = static_cast<T>(v); }
-      else if (dtype == "<i8") { int64_t v; std::memcpy(&v, p, 8); out[i] = static_cast<T>(v); }
-      else if (dtype == "|u1") { out[i] = static_cast<T>(static_cast<uint8_t>(*p)); }
-      else if (dtype == "|i1") { out[i] = static_cast<T>(static_cast<int8_t>(*p)); }
-      else throw std::runtime_error("npy: unsupported dtype " + dtype);
+    if constexpr (std::is_same_v<T, float16_t>) {
+      if (dtype == "<f2") {
+        std::memcpy(out.data(), bytes.data(), bytes.size());
+      } else {
+        const std::vector<float> f = as<float>();
+        narrow(f.data(), out.data(), f.size());
+      }
+    } else {
+      const char* p = bytes.data();
+      for (size_t i = 0; i < out.size(); ++i, p += word_size) {
+        if (dtype == "<f4") { float v; std::memcpy(&v, p, 4); out[i] = static_cast<T>(v); }
+        else if (dtype == "<f2") { float16_t v; std::memcpy(&v, p, 2); out[i] = static_cast<T>(widen(v)); }
+        else if (dtype == "<f8") { double v; std::memcpy(&v, p, 8); out[i] = static_cast<T>(v); }
+        else if (dtype == "<i4") { int32_t v; std::memcpy(&v, p, 4); out[i] = static_cast<T>(v); }
+        else if (dtype == "<u4") { uint32_t v; std::memcpy(&v, p, 4); out[i] = static_cast<T>(v); }
+        else if (dtype == "<i8") { int64_t v; std::memcpy(&v, p, 8); out[i] = static_cast<T>(v); }
+        else if (dtype == "|u1") { out[i] = static_cast<T>(static_cast<uint8_t>(*p)); }
+        else if (dtype == "|i1") { out[i] = static_cast<T>(static_cast<int8_t>(*p)); }
+        else throw std::runtime_error("npy: unsupported dtype " + dtype);
+      }
     }
     return out;
   }

@@ -57,8 +57,13 @@ enum {
   FNV_ERR_CAPACITY = 4   /* a per-query on-device structure overflowed its spill area         */
 };
 
-/* flatnav::util::DataType ordinals (include/flatnav/util/Datatype.h:11-24); also the file format's. */
-enum { FNV_DTYPE_UINT8 = 0, FNV_DTYPE_INT8 = 4, FNV_DTYPE_FLOAT32 = 9 };
+/* flatnav::util::DataType ordinals (include/flatnav/util/Datatype.h:11-24); also the file format's.
+ * Element types of an index: uint8 / int8 (1 byte), float16 (IEEE binary16, 2 bytes), float32 (4 bytes); data_size = dim x
+ * that, and queries passed to a search are rows of the SAME element type.  Distances (float32): L2 = sum (x-y)^2, IP =
+ * 1 - sum x*y.  1-byte types accumulate exactly in int32.  float16: every element is widened exactly to float32 and the sums
+ * are float32 arithmetic on the widened values (no intermediate is rounded to float16), so a float16 index answers like a
+ * float32 index of the widened data up to summation order -- bit for bit on integer-valued data (|v| <= 2048, sums < 2^24). */
+enum { FNV_DTYPE_UINT8 = 0, FNV_DTYPE_INT8 = 4, FNV_DTYPE_FLOAT16 = 8, FNV_DTYPE_FLOAT32 = 9 };
 /* flatnav::distances::MetricType (include/flatnav/distances/DistanceInterface.h:14). */
 enum { FNV_METRIC_L2 = 0, FNV_METRIC_IP = 1 };
 

@@ -3,7 +3,7 @@
 //   construct <quantize> <metric> <data> <M> <ef_construction> <build_num_threads> <outfile> [--device]
 // (<quantize> must be 0: product quantisation is outside this build's scope).  --device builds on the GPU in batches
 // (Index::addBatchDevice: same insertion rule, deterministic); default is the host builder like the reference.
-// The .npy may hold float32 (any metric), uint8 or int8 rows; the index takes the file's element type.
+// The .npy may hold float32 (any metric), float16, uint8 or int8 rows; the index takes the file's element type.
 #include <chrono>
 #include <iostream>
 #include <numeric>
@@ -50,7 +50,7 @@ int main(int argc, char** argv) {
     std::clog << "Usage:\nconstruct <quantize> <metric> <data> <M> <ef_construction> <build_num_threads> <outfile> [--device]\n"
                  "\t <quantize> int, must be 0 (no quantization)\n"
                  "\t <metric> int, 0 for L2, 1 for inner product (angular)\n"
-                 "\t <data> npy file (2-D float32 / uint8 / int8)\n"
+                 "\t <data> npy file (2-D float32 / float16 / uint8 / int8)\n"
                  "\t <M>: int\n\t <ef_construction>: int\n\t <build_num_threads>: int\n"
                  "\t <outfile>: where to stash the index\n"
                  "\t --device: insert on the GPU in batches instead of on the host threads" << std::endl;
@@ -69,6 +69,7 @@ int main(int argc, char** argv) {
     if (file.shape.size() != 2) return -1;
     std::clog << "Loading " << file.shape[1] << "-dimensional dataset with N = " << file.shape[0] << " (" << file.dtype << ")" << std::endl;
     if (file.dtype == "<f4") return dispatch<float, DataType::float32>(file, metric, M, efc, threads, out, device);
+    if (file.dtype == "<f2") return dispatch<flatnav::util::float16_t, DataType::float16>(file, metric, M, efc, threads, out, device);
     if (file.dtype == "|u1") return dispatch<uint8_t, DataType::uint8>(file, metric, M, efc, threads, out, device);
     if (file.dtype == "|i1") return dispatch<int8_t, DataType::int8>(file, metric, M, efc, threads, out, device);
     std::cerr << "unsupported element type " << file.dtype << std::endl;

@@ -1,10 +1,11 @@
 // flatnav_query -- load a saved index, answer a query file on the GPU, report recall and time per query.
 // Same positional command line and output lines as the reference's tools/query_npy.cpp:25-160
-//   query <space> <index> <queries> <gtruth> <ef_search,ef_search,...> <k> <reorder> <quantized> [--per-query] [--dtype f32|u8|i8]
+//   query <space> <index> <queries> <gtruth> <ef_search,ef_search,...> <k> <reorder> <quantized> [--per-query] [--dtype f32|f16|u8|i8]
 // <space> 0 = L2, 1 = inner product; <quantized> must be 0.  Recall as in query_npy.cpp:53-62 (|top-k found ∩ first k
 // ground-truth ids| / k).  Default: every ef value is ONE batched GPU launch over all queries ("Duration" = batch wall
 // time / queries, host buffers, PCIe included); --per-query times the reference's protocol instead (a loop of
-// single-query calls).  The element type of a .bin file is not stored with the metric: pass --dtype for non-float indexes.
+// single-query calls).  The element type of a .bin file is not stored with the metric: pass --dtype for non-float32 indexes
+// (f16: queries of any float dtype are rounded to float16, nearest even).
 #include <chrono>
 #include <iostream>
 #include <sstream>
@@ -79,7 +80,7 @@ static int dispatch(int space, const std::string& index_file, flatnav::util::Npy
 
 int main(int argc, char** argv) {
   if (argc < 9) {
-    std::clog << "Usage:\nquery <space> <index> <queries> <gtruth> <ef_search> <k> <Reorder ID> <Quantized> [--per-query] [--dtype f32|u8|i8]\n"
+    std::clog << "Usage:\nquery <space> <index> <queries> <gtruth> <ef_search> <k> <Reorder ID> <Quantized> [--per-query] [--dtype f32|f16|u8|i8]\n"
                  "\t <space>: 0 = L2, 1 = inner product\n\t <index>: .bin file written by construct / index.save()\n"
                  "\t <queries> <gtruth>: .npy files (rows of the index element type / integer ids)\n"
                  "\t <ef_search>: int,int,int,...\n\t <k>: number of neighbors\n"
@@ -117,6 +118,8 @@ int main(int argc, char** argv) {
     std::clog << "Loading " << q.shape[0] << " queries" << std::endl;
     const std::vector<int> gt = g.as<int>();
     if (dtype == "f32") return dispatch<float, DataType::float32>(space, index_file, q, gt, g.shape[1], efs, K, reorder, per_query);
+    if (dtype == "f16")
+      return dispatch<flatnav::util::float16_t, DataType::float16>(space, index_file, q, gt, g.shape[1], efs, K, reorder, per_query);
     if (dtype == "u8") return dispatch<uint8_t, DataType::uint8>(space, index_file, q, gt, g.shape[1], efs, K, reorder, per_query);
     if (dtype == "i8") return dispatch<int8_t, DataType::int8>(space, index_file, q, gt, g.shape[1], efs, K, reorder, per_query);
     std::cerr << "unknown --dtype " << dtype << std::endl;
