@@ -1,8 +1,8 @@
 """Builds the in-tree gfx950 shared library (C ABI of include/flatnav_hip.h) with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container as well as on the MI355X box.
-The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 80
-objects (kernel_inst.hip: 10 kernel families x 4 element types x 2 metrics) in parallel, plus beam_search.hip (host
+The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 88
+objects (kernel_inst.hip: 11 kernel families x 4 element types x 2 metrics) in parallel, plus beam_search.hip (host
 code, C ABI, re-layout kernels), and linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
 from __future__ import annotations
@@ -25,7 +25,8 @@ INST = os.path.join(CSRC, "kernel_inst.hip")
 TYPES = [("float", "f32"), ("uint8_t", "u8"), ("int8_t", "i8"), ("_Float16", "f16")]
 METRICS = [(0, "l2"), (1, "ip")]
 FAMILIES = [(0, "exact"), (3, "wire"), (4, "merged"), (5, "merged1"), (6, "merged0"), (7, "merged2"),
-            (8, "merged_d"), (9, "merged1_d"), (10, "merged0_d"), (11, "merged2_d")]  # 8-11: the DIRECT forms (small launches)
+            (8, "merged_d"), (9, "merged1_d"), (10, "merged0_d"), (11, "merged2_d"),  # 8-11: the DIRECT forms (small launches)
+            (12, "exact_f")]  # the filtered two-heap kernel
 
 
 def hipcc() -> str:

@@ -141,6 +141,7 @@ const KernelTable& kernel_table(int, int) {
     for (int c = 0; c < kNumCfgs; c++)
       for (int f = 0; f < 2; f++) {
         k.exact[c][f] = beam_search_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
+        k.exact_f[c][f] = beam_search_filtered_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
         k.scan[c][f] = entry_scan_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
         k.merged[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, MB_R>;
         k.merged1[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 1>;
@@ -166,6 +167,7 @@ const KernelTable& kernel_table(int dtype, int metric) {
     int i = 0;
 #define FNV_FILL(T, tag, M, mtag)              \
     fill_exact_##tag##_##mtag(tables[i]);       \
+    fill_exact_f_##tag##_##mtag(tables[i]);     \
     fill_merged_##tag##_##mtag(tables[i]);      \
     fill_merged1_##tag##_##mtag(tables[i]);     \
     fill_merged0_##tag##_##mtag(tables[i]);     \
@@ -192,6 +194,7 @@ const KernelTable& kernel_table(int dtype, int metric) {
 #endif
 
 kernel_fn pick_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).exact[cfg][full]; }
+kernel_fn pick_filtered_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).exact_f[cfg][full]; }
 kernel_fn pick_scan_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).scan[cfg][full]; }
 kernel_fn pick_sorted_kernel(int dtype, int metric, int cfg, bool full, bool lds, int B, bool direct = false) {
   const KernelTable& t = kernel_table(dtype, metric);
@@ -215,6 +218,14 @@ struct LaunchPlan {
   SearchParams heaps, sorted;                 // geometry + LDS layout for each (per-call fields unset)
   uint32_t lds = 0, slds = 0;
   int bpc = 0, sbpc = 0;
+  kernel_fn fkern = nullptr;  // filtered search: the two-heap kernel's filtered form on the `heaps` layout (set at first use)
+  int fbpc = 0;               // ... and the slots one CU keeps resident with it
+};
+
+// Filtered search (fnv_search_batch_filtered*): the caller's bitmap over label values, in device memory.
+struct SearchFilter {
+  const uint8_t* bits;  // byte L >> 3, bit L & 7 = label L allowed (null when n_bits == 0)
+  uint64_t n_bits;
 };
 
 // A host-buffer search that went through the pinned staging buffer: what search_host_finish copies where.
@@ -321,6 +332,10 @@ struct fnv_index_s : IndexOptions {
   size_t done_bytes = 0;
   unsigned long long* d_tielog = nullptr;  // merged-beam kernel: [nslots][log_entries] hand-over log (round 5)
   size_t tielog_bytes = 0;
+  uint32_t* d_nodebits = nullptr;  // filtered search: [capacity / 32] words, bit per node id (node_filter_kernel)
+  size_t nodebits_bytes = 0;
+  uint8_t* d_allowed = nullptr;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM
+  size_t allowed_bytes = 0;
   // staging for the host-buffer entry point
   void* h_pin = nullptr;  // 1 MB of pinned host memory: staging of small host-buffer searches
   void* h_res = nullptr;  // pinned host memory for the result slab of larger host-buffer searches (grown on demand)
@@ -690,7 +705,7 @@ int fnv_index_free(fnv_index_t ix) {
   if (ix->stream) (void)hipStreamSynchronize(ix->stream);
   if (ix->parent) ix->parent->n_views.fetch_sub(1);
   if (!ix->owns_buffers) ix->d_vectors = nullptr, ix->d_links = nullptr, ix->d_labels = nullptr;
-  void* bufs[] = {ix->d_vectors, ix->d_links, ix->d_labels, ix->d_dispenser, ix->d_bitmap, ix->d_ovf, ix->d_nodestage, ix->d_linkstage, ix->d_wirebuf, ix->d_spill, ix->d_q, ix->d_out, ix->d_phase, ix->d_entry, ix->d_done, ix->d_tielog};
+  void* bufs[] = {ix->d_vectors, ix->d_links, ix->d_labels, ix->d_dispenser, ix->d_bitmap, ix->d_ovf, ix->d_nodestage, ix->d_linkstage, ix->d_wirebuf, ix->d_spill, ix->d_q, ix->d_out, ix->d_phase, ix->d_entry, ix->d_done, ix->d_tielog, ix->d_nodebits, ix->d_allowed};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (ix->h_pin) (void)hipHostFree(ix->h_pin);
@@ -819,7 +834,8 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
 static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
                               int num_initializations, float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count,
                               uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream, bool node_ids,
-                              int force_variant = -1, bool ids_by_option = false, int32_t* host_status = nullptr);
+                              int force_variant = -1, bool ids_by_option = false, int32_t* host_status = nullptr,
+                              const SearchFilter* filter = nullptr);
 
 int fnv_search_batch_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
                             int num_initializations, float* d_out_dist, int32_t* d_out_labels,
@@ -1094,7 +1110,8 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
                               int force_variant,  // >= 0: fnv_tune's launches (an argument, not index state: a concurrent
                                                   // caller's launch on the same handle is never forced)
                               bool ids_by_option,  // node_ids = the "output_node_ids" option, read under the handle's mutex
-                              int32_t* host_status) {  // zero-copy small searches: the error flag's copy in the caller's pinned slab
+                              int32_t* host_status,  // zero-copy small searches: the error flag's copy in the caller's pinned slab
+                              const SearchFilter* filter) {  // filtered search: every query runs the filtered two-heap kernel
   if (!ix) return fail(FNV_ERR_INVALID, "index is null");
   // Index.h:847-849
   if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
@@ -1210,7 +1227,16 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   // equal keys force the merged-beam kernel to search a query twice (rarely on float data, often on integer-valued
   // data with wide beams) -- so it is measured: launches of at least 2048 queries are timed by the events that bracket
   // them anyway, harvested when a later call finds them complete, first one kernel, then the other, then the faster.
-  bool sorted = plan.mode != MODE_HEAPS;
+  // A filtered launch always runs the two-heap kernel's filtered form: no merged beam, no samples for the adaptive choice
+  // (the tuner's measurements are left alone), no hand-over, tie log or shadows.
+  if (filter && !plan.fkern) {
+    plan.fkern = pick_filtered_kernel(ix->dtype, ix->metric, plan.cfg, plan.full);
+    HIP_TRY(raise_lds_limit((const void*)plan.fkern, ix->device, plan.lds));
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern, WAVE, plan.lds) != hipSuccess) n = 0;
+    plan.fbpc = std::max(1, std::min(plan.bpc, n));
+  }
+  bool sorted = plan.mode != MODE_HEAPS && !filter;
   bool sample = false;
   int variant = sorted ? 1 : 0;
   // The merged-beam kernel's stragglers: a query that is searched twice finishes a whole exact-search latency late, and
@@ -1275,7 +1301,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
       if (variant >= 2) tail_pct = kTailPct[variant];
     }
   }
-  const int bpc = sorted ? plan.sbpc : plan.bpc;
+  const int bpc = sorted ? plan.sbpc : filter ? plan.fbpc : plan.bpc;
   uint32_t lds_bytes = sorted ? plan.slds : plan.lds;
   // Shadow mode (search_params.h): a launch that fills at most a quarter of the resident slots starts, next to the
   // merged-beam search of every query, an exact search of the same query on another slot.  A query in which equal keys
@@ -1296,6 +1322,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     if (!rc) rc = grow((void**)&ix->d_spill, &ix->spill_bytes, (size_t)max_slots * plan.heaps.spill_entries * 8);
     if (!rc && (shadow || tail_shadows)) rc = grow((void**)&ix->d_done, &ix->done_bytes, (size_t)nq * 4);
     if (!rc && sorted) rc = grow((void**)&ix->d_tielog, &ix->tielog_bytes, (size_t)max_slots * plan.sorted.log_entries * 8);
+    if (!rc && filter) rc = grow((void**)&ix->d_nodebits, &ix->nodebits_bytes, (size_t)(ix->capacity + 31) / 32 * 4);
     ix->ws_bytes = ix->bitmap_bytes + ix->ovf_bytes + ix->spill_bytes + ix->tielog_bytes;
     // out of memory on the handle itself: the hidden lanes' idle workspaces go first, then once more (from inside fnv_tune /
     // fnv_index_insert_batch, which hold the lanes, with the locks already held: t_holds_lanes_of)
@@ -1365,6 +1392,13 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   p.tail_exact = multi_round && sorted ? (uint32_t)std::min<uint64_t>((uint64_t)tail_pct * nslots / 100, nq) : 0u;
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));
+  if (filter) {  // the label bitmap -> this handle's node bitmap (labels as they are now: after reorder(), device builds ...)
+    const uint64_t words = (ix->capacity + 31) / 32;
+    hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
+                       live, words, filter->bits, filter->n_bits, ix->d_nodebits);
+    HIP_TRY(hipGetLastError());
+    p.node_bits = ix->d_nodebits;
+  }
   HIP_TRY(hipEventRecord(ix->ev0, stream));
   if (ix->entry_kernel && !ix->tail_bytes) {  // (split rows: K0's LDS tiles hold one table's rows; the in-kernel scan serves them)
     // K0: one pass over the shared entry-scan nodes for the whole batch (LDS-staged), same stream
@@ -1397,7 +1431,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     p.nq = (uint32_t)(2 * nq);
     p.tail_exact = 0u;
   }
-  kernel_fn kern = !sorted ? plan.kern : direct ? plan.skern_direct : plan.skern;
+  kernel_fn kern = filter ? plan.fkern : !sorted ? plan.kern : direct ? plan.skern_direct : plan.skern;
   HIP_TRY(raise_lds_limit((const void*)kern, ix->device, lds_bytes));
   hipLaunchKernelGGL(kern, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
   HIP_TRY(hipGetLastError());
@@ -1442,10 +1476,27 @@ static uint64_t now_ns() {
 // Host-buffer search in two halves, so that several devices can be kept busy by one caller: enqueue (H2D of the
 // queries, the search launch, D2H of the results -- all asynchronous on the index's own stream; the caller holds
 // ix->host_mu) and finish (wait, report a capacity error).
+// `host_filter` (filtered search): the label bitmap in host memory; it is staged into this handle's HBM first.
 static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search,
                                int num_initializations, float* out_dist, int32_t* out_labels, int32_t* out_count,
-                               uint64_t* out_ndist, uint64_t* out_nhops) {
+                               uint64_t* out_ndist, uint64_t* out_nhops, const SearchFilter* host_filter = nullptr) {
   ON_DEVICE(ix->device);
+  SearchFilter dev_filter{nullptr, 0};
+  const SearchFilter* filter = nullptr;
+  if (host_filter) {
+    const size_t fbytes = (size_t)((host_filter->n_bits + 7) / 8);
+    if (fbytes) {
+      {
+        std::lock_guard<std::mutex> lock(ix->mu);
+        int rc = grow((void**)&ix->d_allowed, &ix->allowed_bytes, fbytes);
+        if (rc) return rc;
+      }
+      HIP_TRY(hipMemcpyAsync(ix->d_allowed, host_filter->bits, fbytes, hipMemcpyHostToDevice, ix->stream));
+      dev_filter.bits = ix->d_allowed;
+    }
+    dev_filter.n_bits = host_filter->n_bits;
+    filter = &dev_filter;
+  }
   const size_t qbytes = (size_t)nq * ix->dim * dtype_size(ix->dtype);
   // one output slab: dist | labels | count | ndist | nhops
   const size_t o_dist = 0;
@@ -1510,7 +1561,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
     void* dh = out_nhops ? device_view(out_nhops) : nullptr;
     if (dq && dd && dl && (!out_count || dc) && (!out_ndist || dn) && (!out_nhops || dh)) {
       int rc0 = search_device_impl(ix, dq, nq, K, ef_search, num_initializations, (float*)dd, (int32_t*)dl, (int32_t*)dc, (uint64_t*)dn,
-                                   (uint64_t*)dh, ix->stream, false, -1, /*ids_by_option=*/true);
+                                   (uint64_t*)dh, ix->stream, false, -1, /*ids_by_option=*/true, nullptr, filter);
       if (rc0) return rc0;
       ix->t_enqueue_ns = now_ns();
       return FNV_OK;  // (search_host_finish: wait + the launch's status word)
@@ -1529,7 +1580,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
     uint8_t* ho = h + ooff;
     int rc0 = search_device_impl(ix, h + qoff, nq, K, ef_search, num_initializations, (float*)(ho + o_dist), (int32_t*)(ho + o_lab),
                                  (int32_t*)(ho + o_cnt), (uint64_t*)(ho + o_nd), (uint64_t*)(ho + o_nh), ix->stream, false, -1,
-                                 /*ids_by_option=*/true, (int32_t*)(h + soff));
+                                 /*ids_by_option=*/true, (int32_t*)(h + soff), filter);
     if (rc0) return rc0;
     ix->t_enqueue_ns = now_ns();
     PinnedCall& c = ix->pin;
@@ -1549,9 +1600,9 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   } else {
     HIP_TRY(hipMemcpyAsync(ix->d_q, queries, qbytes, hipMemcpyHostToDevice, ix->stream));
   }
-  int rc = fnv_search_batch_device(ix, ix->d_q, nq, K, ef_search, num_initializations, (float*)(o + o_dist),
-                                   (int32_t*)(o + o_lab), (int32_t*)(o + o_cnt), (uint64_t*)(o + o_nd),
-                                   (uint64_t*)(o + o_nh), ix->stream);
+  int rc = search_device_impl(ix, ix->d_q, nq, K, ef_search, num_initializations, (float*)(o + o_dist), (int32_t*)(o + o_lab),
+                              (int32_t*)(o + o_cnt), (uint64_t*)(o + o_nd), (uint64_t*)(o + o_nh), ix->stream, false, -1,
+                              /*ids_by_option=*/true, nullptr, filter);
   if (rc) return rc;
   ix->t_enqueue_ns = now_ns();
   if (pinned) {
@@ -1648,9 +1699,9 @@ static void sync_lane(fnv_index_t ix, fnv_index_s* lane) {
 // and its own stragglers: 2.4-3.3 ms against 1.28 ms), and ONE launch that starts before its queries are there -- reading
 // them from pinned host memory behind a gate word, results written straight back (every touch of host memory from a
 // running wave costs microseconds: 1.7-2.6 ms).  Neither is in the tree.
-int fnv_search_batch(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
-                     float* out_dist, int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist,
-                     uint64_t* out_nhops) {
+static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                             float* out_dist, int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist,
+                             uint64_t* out_nhops, const SearchFilter* host_filter) {
   int rc = check_search_args(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels);
   if (rc || nq == 0) return rc;
   // one caller at a time per lane (a lane's staging areas, stream and workspace are its caller's for the whole call); a
@@ -1701,7 +1752,7 @@ int fnv_search_batch(fnv_index_t ix, const void* queries, uint64_t nq, int K, in
   if (!host_lock.owns_lock()) host_lock = std::unique_lock<std::mutex>(ix->host_mu);
   if (lane != ix) sync_lane(ix, lane);
   rc = search_host_enqueue(lane, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count,
-                           out_ndist, out_nhops);
+                           out_ndist, out_nhops, host_filter);
   if (rc == FNV_ERR_NO_DEVICE && lane != ix) {
     // a lane could not get its workspace (another copy of the per-slot bitmaps and spill areas: 19 GB at 50M nodes): the
     // call waits for the handle's own lane instead, like any caller did before there were lanes
@@ -1710,7 +1761,7 @@ int fnv_search_batch(fnv_index_t ix, const void* queries, uint64_t nq, int K, in
     host_lock = std::unique_lock<std::mutex>(ix->host_mu);
     lane = ix;
     rc = search_host_enqueue(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count, out_ndist,
-                             out_nhops);
+                             out_nhops, host_filter);
   }
   if (rc) return rc;
   rc = search_host_finish(lane);
@@ -1726,6 +1777,42 @@ int fnv_search_batch(fnv_index_t ix, const void* queries, uint64_t nq, int K, in
     ix->last_served = lane;  // (lanes live as long as the handle)
   }
   return rc;
+}
+
+int fnv_search_batch(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                     float* out_dist, int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist,
+                     uint64_t* out_nhops) {
+  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count, out_ndist,
+                           out_nhops, nullptr);
+}
+
+// ---- filtered search: results restricted to the nodes whose label is set in a bitmap over label values -------------
+static int check_filter_args(const void* allowed_bits, uint64_t n_bits) {
+  if (n_bits > (1ull << 31)) return fail(FNV_ERR_INVALID, "n_bits must be at most 2^31 (labels are int32)");
+  if (n_bits > 0 && !allowed_bits) return fail(FNV_ERR_INVALID, "allowed_bits is null but n_bits > 0");
+  return FNV_OK;
+}
+
+int fnv_search_batch_filtered(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                              const void* allowed_bits, uint64_t n_bits, float* out_dist, int32_t* out_labels,
+                              int32_t* out_count, uint64_t* out_ndist, uint64_t* out_nhops) {
+  int rc = check_filter_args(allowed_bits, n_bits);
+  if (rc) return rc;
+  const SearchFilter f{(const uint8_t*)allowed_bits, n_bits};
+  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count, out_ndist,
+                           out_nhops, &f);
+}
+
+int fnv_search_batch_filtered_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
+                                     int num_initializations, const void* d_allowed_bits, uint64_t n_bits, float* d_out_dist,
+                                     int32_t* d_out_labels, int32_t* d_out_count, uint64_t* d_out_ndist, uint64_t* d_out_nhops,
+                                     void* hip_stream) {
+  if (!ix) return fail(FNV_ERR_INVALID, "index is null");
+  int rc = check_filter_args(d_allowed_bits, n_bits);
+  if (rc) return rc;
+  const SearchFilter f{n_bits ? (const uint8_t*)d_allowed_bits : nullptr, n_bits};
+  return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations, d_out_dist, d_out_labels, d_out_count,
+                            d_out_ndist, d_out_nhops, hip_stream, false, -1, /*ids_by_option=*/true, nullptr, &f);
 }
 
 // ---- several GPUs behind one call -----------------------------------------------------------------

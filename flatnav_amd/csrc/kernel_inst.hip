@@ -2,8 +2,8 @@
 //   hipcc -c -DFNV_INST_T=float -DFNV_INST_TAG=f32 -DFNV_INST_METRIC=0 -DFNV_INST_MTAG=l2 -DFNV_INST_FAMILY=4 ...
 // families: 0 exact two-heap kernel + entry scan, 3 wiring kernels, 4 merged beam (<= 256 entries in registers),
 // 5 merged beam (<= 64 entries in registers), 6 merged beam (LDS, any width), 7 merged beam (<= 128 in registers), 8-11 the
-// DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS).  flatnav_amd/build.py compiles the
-// 80 combinations in parallel and links them with beam_search.hip.
+// DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS), 12 the filtered two-heap kernel.
+// flatnav_amd/build.py compiles the 88 combinations in parallel and links them with beam_search.hip.
 #include <hip/hip_runtime.h>
 
 #include "kernel_table.h"
@@ -36,6 +36,8 @@ static void fill_rows(KernelTable& t) {
 #if FNV_INST_FAMILY == 0
   FNV_ROW(t.exact, beam_search_kernel)
   FNV_ROW(t.scan, entry_scan_kernel)
+#elif FNV_INST_FAMILY == 12
+  FNV_ROW(t.exact_f, beam_search_filtered_kernel)
 #elif FNV_INST_FAMILY == 4
 #define FNV_COMMA_MB_R , MB_R
   FNV_ROW(t.merged, beam_search_merged_kernel, FNV_COMMA_MB_R)
@@ -68,6 +70,8 @@ static void fill_rows(KernelTable& t) {
 
 #if FNV_INST_FAMILY == 0
 void FNV_CAT(fill_exact_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
+#elif FNV_INST_FAMILY == 12
+void FNV_CAT(fill_exact_f_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
 #elif FNV_INST_FAMILY == 4
 void FNV_CAT(fill_merged_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
 #elif FNV_INST_FAMILY == 5

@@ -38,6 +38,7 @@ inline int pick_row_cfg(uint32_t nchunks, uint32_t tail_chunks = 0) {
 // All kernels for one (element type, metric): [row configuration][FULL rows].
 struct KernelTable {
   kernel_fn exact[kNumCfgs][2];        // beam_search_kernel (two heaps, libstdc++-exact)
+  kernel_fn exact_f[kNumCfgs][2];      // beam_search_filtered_kernel (the same, results restricted to a node bitmap)
   kernel_fn scan[kNumCfgs][2];         // entry_scan_kernel (K0)
   kernel_fn merged[kNumCfgs][2];       // beam_search_merged_kernel (beam <= 256 in registers, one merge per link row)
   kernel_fn merged1[kNumCfgs][2];      // ... its one-chunk form (beam <= 64)
@@ -56,6 +57,7 @@ struct KernelTable {
 // one filler per kernel family and (type, metric), each defined by one compilation of kernel_inst.hip
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag)             \
   void fill_exact_##tag##_##mtag(KernelTable& t);        \
+  void fill_exact_f_##tag##_##mtag(KernelTable& t);      \
   void fill_merged_##tag##_##mtag(KernelTable& t);       \
   void fill_merged1_##tag##_##mtag(KernelTable& t);      \
   void fill_merged0_##tag##_##mtag(KernelTable& t);      \

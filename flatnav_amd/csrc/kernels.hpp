@@ -277,10 +277,29 @@ struct ExactState {
 };
 
 // One admission (Index.h:693-704) of (di, idi) into both heaps; the caller has checked nothing.
+// FILTER (filtered search): a node that is not `allowed` still enters the candidates heap (navigation) but not the
+// neighbours heap, so neither the beam's size nor max_dist changes; an allowed node is admitted exactly as without a filter.
+template <bool FILTER = false>
 __device__ __forceinline__ void exact_admit(const ExactCtx& x, LdsHeap& nbr, LdsHeap& cand, unsigned long long* spill,
-                                            ExactState& s, float di, uint32_t idi, int lane, PhaseTimer& ph) {
+                                            ExactState& s, float di, uint32_t idi, int lane, PhaseTimer& ph, bool allowed = true) {
   const int B = x.B, cand_slots = x.cand_slots;
   if (!(s.nbr_n < B || di < s.max_dist)) return;  // Index.h:693
+  if (FILTER && !allowed) {  // (allowed is wave-uniform)
+    if (s.cand_n < cand_slots) {
+      coop_push(cand, s.cand_n, fnv_stl::Entry{-di, idi}, lane, ph, 11);
+    } else {
+      if (s.cand_n >= cand_slots + (int)cold_args()->spill_entries) {
+        s.err = ST_CAND_OVERFLOW;
+        return;
+      }
+      CandHeap cand_big{cand.p, spill, cand_slots};
+      __threadfence_block();
+      coop_push(cand_big, s.cand_n, fnv_stl::Entry{-di, idi}, lane, ph, 11);
+      __threadfence_block();
+    }
+    s.cand_n++;
+    return;
+  }
   // max_dist == neighbors.top().first throughout (Index.h:702), so the new top is known without reading
   // the heap back: a push changes it only if the new element climbs to the root, a pop reports it
   bool at_root;
@@ -333,7 +352,9 @@ struct ExactResume {
 // `resumed` (false: a search from scratch): heaps, visited set and counters come from a replayed log (`rs`); the search starts
 // at the loop head.  (A run-time flag, not a template parameter: the merged-beam kernel inlines this function ONCE for both;
 // `rs` by value: a pointer to it would keep the struct in scratch memory.)
-template <typename T, int METRIC, int G, int CU, bool FULL, bool DIRECT = false>
+// FILTER (filtered search, beam_search_filtered_kernel): only nodes whose bit is set in the launch's node bitmap
+// (SearchParams::node_bits, one bit per node id) enter the neighbours heap; every node navigates.  Never resumed, never a shadow.
+template <typename T, int METRIC, int G, int CU, bool FULL, bool DIRECT = false, bool FILTER = false>
 __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU>& q, int qi, uint32_t entry, float best_d, int lane,
                                             PhaseTimer& ph, const uint32_t* stop = nullptr, bool resumed = false,
                                             ExactResume rs = ExactResume{ExactState{1, 1, 0.f, ST_OK}, 0u, 0u, false}) {
@@ -361,6 +382,12 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
   uint32_t vis_count = 1;
   bool ovf = false;       // 32-bit table: switched to the bitmap; tagged: some id went to the bitmap
   uint32_t n_dist = 0, n_hops = 0;
+  const uint32_t* const node_bits = FILTER ? cold_args()->node_bits : nullptr;
+  bool entry_allowed = true;
+  if (FILTER) {  // the entry navigates either way; it is a result only if allowed (max_dist starts at its distance regardless)
+    entry_allowed = (rfl((int)node_bits[entry >> 5]) >> (entry & 31)) & 1;
+    if (!entry_allowed) s.nbr_n = 0;
+  }
   if (resumed) {
     s = rs.s;
     n_dist = rs.n_dist;
@@ -370,7 +397,7 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
     if (lane == 0) {
       CandHeap c0{cand.p, spill, cand_slots};
       c0.set(0, fnv_stl::Entry{-best_d, entry});
-      nbr.set(0, fnv_stl::Entry{best_d, entry});
+      if (entry_allowed) nbr.set(0, fnv_stl::Entry{best_d, entry});
     }
     if (!tagged) {
       if (lane == 0) visited_insert_lds(vis, cold_args()->vis_slots - 1, cold_args()->vis_shift, entry);
@@ -447,6 +474,13 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
           cid[pu] = stage_ids[min(slot, n - 1)];  // lanes past the end re-read the last real id
         }
         const int npass = min(PU, (n - base + VPW - 1) / VPW);
+        // filtered search: each lane requests its slot's bitmap word before the row gather, so that the test waits on
+        // the same memory round trip as the distance instead of adding one
+        uint32_t fw[PU];
+        if (FILTER) {
+#pragma unroll
+          for (int pu = 0; pu < PU; pu++) fw[pu] = node_bits[cid[pu] >> 5];
+        }
         batch_dists<T, METRIC, G, CU, FULL>(vectors, row_bytes, nchunks, q, cid, npass, cd, lane);
         PH_MARK(5);
 
@@ -456,12 +490,14 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
         for (int pu = 0; pu < PU; pu++) {
           if (pu >= npass) break;
           unsigned long long pm = __ballot(group_leader && cval[pu] && (s.nbr_n < B || cd[pu] < s.max_dist));
+          unsigned long long am = ~0ull;  // lanes whose node may enter the neighbours heap
+          if (FILTER) am = __ballot((fw[pu] >> (cid[pu] & 31)) & 1u);
           while (pm) {
             const int i = __ffsll((long long)pm) - 1;
             pm &= pm - 1;
             const float di = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cd[pu]), i));
             const uint32_t idi = (uint32_t)__builtin_amdgcn_readlane((int)cid[pu], i);
-            exact_admit(x, nbr, cand, spill, s, di, idi, lane, ph);
+            exact_admit<FILTER>(x, nbr, cand, spill, s, di, idi, lane, ph, ((am >> i) & 1ull) != 0ull);
             if (s.err) pm = 0;
           }
           if (s.err) break;
@@ -699,6 +735,48 @@ __global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) vo
     const uint32_t entry = entry_point<T, METRIC, G, CU, FULL>(x.vectors, x.row_bytes, x.nchunks, q, qi, lane, best_d);
     PH_MARK(1);
     exact_query<T, METRIC, G, CU, FULL>(x, q, qi, entry, best_d, lane, ph);
+    PH_FLUSH;
+  }
+}
+
+// Filtered search (exact_f): beam_search_kernel with exact_query<..., FILTER = true> -- only nodes set in SearchParams::node_bits
+// become results.  (A copy of the kernel above rather than a shared body: routing beam_search_kernel through a helper changes
+// its register allocation, and the unfiltered kernels are kept instruction for instruction as they were.)
+template <typename T, int METRIC, int G, int CU, bool FULL>
+__global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) void beam_search_filtered_kernel(const SearchParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  // hot parameters (scalar registers for the whole launch); everything else is re-read where it is used
+  ExactCtx x;
+  x.vectors = p.vectors;
+  x.links = p.links;
+  x.row_bytes = p.row_bytes;
+  x.nchunks = (int)p.nchunks;
+  x.B = p.B;
+  x.M = (int)p.M;
+  x.cand_slots = (int)p.cand_slots;
+  x.tagged = p.vis_tag16 != 0u;
+  x.vg = VisGeom{p.vis_nmask, p.vis_rshift, p.vis_rmask, p.vis_mult, p.vis_w};
+  uint4* const qlds = reinterpret_cast<uint4*>(smem + p.off_q);
+  x.nbr = reinterpret_cast<unsigned long long*>(smem + p.off_nbr);
+  x.cand = reinterpret_cast<unsigned long long*>(smem + p.off_cand);
+  x.vis = reinterpret_cast<uint32_t*>(smem + p.off_vis);
+  x.stage_ids = reinterpret_cast<uint32_t*>(smem + p.off_stage_ids);
+  x.ovf_list = reinterpret_cast<uint32_t*>(smem + p.off_ovf);
+
+  while (true) {
+    const int qi = next_query(lane);
+    if (qi < 0) break;
+    PH_DECL
+    Query<G, CU> q;
+    stage_query<T>(q, qlds, x.vis, x.ovf_list, qi, x.tagged, lane);
+    __syncthreads();
+    PH_MARK(0);
+    // ---- entry-point selection (Index.h:845-870): argmin over nodes 0, s, 2s, ... -----------
+    float best_d;
+    const uint32_t entry = entry_point<T, METRIC, G, CU, FULL>(x.vectors, x.row_bytes, x.nchunks, q, qi, lane, best_d);
+    PH_MARK(1);
+    exact_query<T, METRIC, G, CU, FULL, false, true>(x, q, qi, entry, best_d, lane, ph);
     PH_FLUSH;
   }
 }

@@ -146,6 +146,52 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     return py::make_tuple(dist, labels);
   }
 
+  // search_filtered(queries, K, ef_search, allowed, num_initializations=100) -> (float32[Q,K], int32[Q,K]): the k-NN among the
+  // nodes whose label is allowed; `allowed` = 1-D bool mask indexed by label, or 1-D integer array of labels (order and
+  // duplicates ignored, a negative label raises ValueError).  Short rows are padded with (+inf, -1), never raised on.
+  py::tuple searchFiltered(const py::array& queries_any, int K, int ef_search, const py::array& allowed_any, int num_initializations) {
+    py::array queries = elements(queries_any);
+    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
+    if (K <= 0) throw std::invalid_argument("K must be positive.");
+    if (allowed_any.ndim() != 1) throw std::invalid_argument("allowed must be a 1-D bool mask or a 1-D array of labels.");
+    constexpr uint64_t kMaxBits = uint64_t(1) << 31;
+    std::vector<uint8_t> bits;
+    uint64_t n_bits = 0;
+    if (allowed_any.dtype().kind() == 'b') {
+      auto mask = allowed_any.cast<dense_array<bool>>();
+      n_bits = static_cast<uint64_t>(mask.size());
+      if (n_bits > kMaxBits) throw std::invalid_argument("allowed mask longer than 2^31 labels.");
+      bits.assign((n_bits + 7) / 8, 0);
+      for (uint64_t i = 0; i < n_bits; ++i)
+        if (mask.data()[i]) bits[i >> 3] |= static_cast<uint8_t>(1u << (i & 7));
+    } else if (allowed_any.size() == 0 || allowed_any.dtype().kind() == 'i' || allowed_any.dtype().kind() == 'u') {
+      auto ids = allowed_any.cast<dense_array<int64_t>>();
+      int64_t top = -1;
+      for (py::ssize_t i = 0; i < ids.size(); ++i) {
+        if (ids.data()[i] < 0) throw std::invalid_argument("allowed labels must be non-negative.");
+        top = std::max(top, ids.data()[i]);
+      }
+      n_bits = static_cast<uint64_t>(top + 1);
+      if (n_bits > kMaxBits) throw std::invalid_argument("allowed label does not fit an int32 label.");
+      bits.assign((n_bits + 7) / 8, 0);
+      for (py::ssize_t i = 0; i < ids.size(); ++i) bits[static_cast<size_t>(ids.data()[i]) >> 3] |= static_cast<uint8_t>(1u << (ids.data()[i] & 7));
+    } else {
+      throw std::invalid_argument("allowed must be a bool mask or an integer array of labels.");
+    }
+    const py::ssize_t nq = queries.shape(0);
+    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
+    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
+    {
+      const void* qptr = queries.data();
+      float* dptr = dist.mutable_data();
+      int* lptr = labels.mutable_data();
+      py::gil_scoped_release release;
+      _index->searchBatchFiltered(qptr, static_cast<uint64_t>(nq), K, ef_search, num_initializations, bits.empty() ? nullptr : bits.data(),
+                                  n_bits, dptr, lptr, nullptr);
+    }
+    return py::make_tuple(dist, labels);
+  }
+
   // search_single(query, K, ef_search, num_initializations=100) -> (float32[K], int32[K])
   py::tuple searchSingle(const py::array& query_any, int K, int ef_search, int num_initializations) {
     py::array query = elements(query_any);
@@ -223,6 +269,10 @@ void bindIndex(py::module_& m, const char* name) {
       .def("search", &T::search, py::arg("queries"), py::arg("K"), py::arg("ef_search"),
            py::arg("num_initializations") = 100,
            "Batched k-NN on the GPU (one kernel launch) -> (distances[Q,K] float32, labels[Q,K] int32).")
+      .def("search_filtered", &T::searchFiltered, py::arg("queries"), py::arg("K"), py::arg("ef_search"), py::arg("allowed"),
+           py::arg("num_initializations") = 100,
+           "Batched k-NN among the nodes whose label is allowed (`allowed`: bool mask indexed by label, or integer labels) "
+           "-> (distances[Q,K] float32, labels[Q,K] int32), rows padded with (+inf, -1) when fewer than K are allowed.")
       .def("get_query_distance_computations", &T::getQueryDistanceComputations,
            "Distance evaluations since the last call (needs collect_stats=True); resets the counter.")
       .def("save", &T::save, py::arg("filename"), "Write the index in flatnav's binary format.")

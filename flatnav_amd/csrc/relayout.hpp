@@ -182,4 +182,21 @@ __global__ void scatter_links_kernel(const uint32_t* __restrict__ node_ids, cons
   }
 }
 
+// Filtered search: node_bits[w] bit b = label_allowed(labels[32 w + b]) for the live nodes, 0 past them.  allowed_bits is a
+// bitmap over label VALUES (byte L >> 3, bit L & 7); a label that is negative or >= n_bits is not allowed.  One thread per
+// node; a wave's 64 verdicts are two words.
+__global__ __launch_bounds__(256) void node_filter_kernel(const int32_t* labels, uint64_t n_live, uint64_t n_words,
+                                                          const uint8_t* allowed_bits, uint64_t n_bits, uint32_t* node_bits) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool ok = false;
+  if (i < n_live) {
+    const int32_t L = labels[i];
+    ok = L >= 0 && (uint64_t)L < n_bits && ((allowed_bits[(uint32_t)L >> 3] >> (L & 7)) & 1u);
+  }
+  const unsigned long long m = __ballot(ok);
+  const int lane = (int)(threadIdx.x & (WAVE - 1));
+  const uint64_t w = i >> 5;
+  if ((lane & 31) == 0 && w < n_words) node_bits[w] = (uint32_t)(lane ? m >> 32 : m);
+}
+
 }  // namespace fnv_dev

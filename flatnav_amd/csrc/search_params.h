@@ -127,6 +127,9 @@ struct SearchParams {
   // a query in which equal keys meet at a decision is then searched again from scratch, as in rounds 2-4)
   unsigned long long* tie_log;  // [nslots][log_entries]
   uint32_t log_entries;
+  // Filtered search (beam_search_filtered_kernel only): bit (i & 31) of word i >> 5 set = node i may be a result; null elsewhere.
+  // (The last field: the other kernels' parameter offsets stay as they were.)
+  const uint32_t* node_bits;
 };
 
 // Broadcast of lane 0's value into a scalar register ("this value is wave-uniform").

@@ -27,6 +27,7 @@ C_ABI_SYMBOLS = [
     "fnv_index_read_links", "fnv_last_replayed_queries", "fnv_replicate", "fnv_replica_refresh",
     "fnv_search_batch_multi", "fnv_index_view", "fnv_tune", "fnv_last_launch_info", "fnv_gather_ceiling",
     "fnv_index_adopt", "fnv_lane_info", "fnv_last_handover_stats", "fnv_row_layout",
+    "fnv_search_batch_filtered", "fnv_search_batch_filtered_device",
 ]
 
 _lib = None
@@ -70,6 +71,11 @@ def lib() -> C.CDLL:
     L.fnv_search_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
     L.fnv_search_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int] + [
         C.c_void_p] * 6
+    if hasattr(L, "fnv_search_batch_filtered"):  # (older builds under the A/B tools lack the filtered entry points)
+        L.fnv_search_batch_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_uint64] + [C.c_void_p] * 5
+        L.fnv_search_batch_filtered_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
     L.fnv_search_status.argtypes = [C.c_void_p]
     L.fnv_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.fnv_last_replayed_queries.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
@@ -120,6 +126,36 @@ def device_count() -> int:
 
 def _np_dtype(name: str):
     return {"float32": np.float32, "uint8": np.uint8, "int8": np.int8, "float16": np.float16}[name]
+
+
+MAX_FILTER_BITS = 1 << 31  # labels are int32: a bitmap never needs more bits
+
+
+def pack_allowed(allowed):
+    """The C ABI's filter bitmap for `allowed` -> (uint8 array, n_bits).  `allowed`: a 1-D bool mask indexed by label (n_bits =
+    its length), or a 1-D integer array of labels (order and duplicates do not matter; n_bits = largest label + 1).  Byte L >> 3,
+    bit L & 7 (little-endian bit order) = label L allowed.  A negative label raises ValueError."""
+    a = np.asarray(allowed)
+    if a.ndim != 1:
+        raise ValueError("allowed must be a 1-D bool mask or a 1-D array of labels")
+    if a.dtype == np.bool_:
+        n_bits = int(a.size)
+        if n_bits > MAX_FILTER_BITS:
+            raise ValueError("allowed mask longer than 2^31 labels")
+        return np.ascontiguousarray(np.packbits(a, bitorder="little")), n_bits
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("allowed must be a bool mask or an integer array of labels, not %s" % a.dtype)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint8), 0
+    a = a.astype(np.int64, copy=False)
+    if int(a.min()) < 0:
+        raise ValueError("allowed labels must be non-negative")
+    n_bits = int(a.max()) + 1
+    if n_bits > MAX_FILTER_BITS:
+        raise ValueError("allowed label %d does not fit an int32 label" % (n_bits - 1))
+    mask = np.zeros(n_bits, dtype=np.bool_)
+    mask[a] = True
+    return np.ascontiguousarray(np.packbits(mask, bitorder="little")), n_bits
 
 
 def search_multi(indexes, queries, K: int, ef_search: int, num_initializations: int = 100, stats: bool = False):
@@ -284,6 +320,29 @@ class DeviceIndex:
             return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
         return d, l
 
+    def search_filtered(self, queries, K: int, ef_search: int, allowed, num_initializations: int = 100, stats: bool = False):
+        """Host-buffer batched search restricted to the nodes whose label is allowed (fnv_search_batch_filtered) ->
+        (dist float32[Q,K], labels int32[Q,K][, stats]).  `allowed`: see pack_allowed.  Rows with fewer than K allowed
+        results are padded with (+inf, -1) (stats["count"] says how many are real); that is not an error."""
+        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("Queries have incorrect dimensions.")
+        nq = q.shape[0]
+        if K <= 0:
+            raise ValueError("K must be positive")
+        bits, n_bits = pack_allowed(allowed)
+        d = np.empty((nq, K), dtype=np.float32)
+        l = np.empty((nq, K), dtype=np.int32)
+        cnt = np.empty(nq, dtype=np.int32)
+        nd = np.zeros(nq, dtype=np.uint64)
+        nh = np.zeros(nq, dtype=np.uint64)
+        check(lib().fnv_search_batch_filtered(self._h, q.ctypes.data, nq, K, ef_search, num_initializations,
+                                              bits.ctypes.data if n_bits else None, n_bits, d.ctypes.data, l.ctypes.data,
+                                              cnt.ctypes.data, nd.ctypes.data, nh.ctypes.data))
+        if stats:
+            return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
+        return d, l
+
     def search_into(self, queries: np.ndarray, K: int, ef_search: int, dist: np.ndarray, labels: np.ndarray,
                     num_initializations: int = 100) -> None:
         """Host-buffer batched search into arrays the CALLER owns (no allocation, no conversion): queries [Q, dim] of the index's
@@ -305,6 +364,16 @@ class DeviceIndex:
         check(lib().fnv_search_batch_device(self._h, q_ptr, nq, K, ef_search, num_initializations, dist_ptr,
                                             label_ptr, count_ptr or None, ndist_ptr or None, nhops_ptr or None,
                                             stream or None))
+
+    def search_device_filtered(self, q_ptr: int, nq: int, K: int, ef_search: int, num_initializations: int, bits_ptr: int,
+                               n_bits: int, dist_ptr: int, label_ptr: int, count_ptr: int = 0, ndist_ptr: int = 0,
+                               nhops_ptr: int = 0, stream=None) -> None:
+        """Device-buffer filtered search (fnv_search_batch_filtered_device): every pointer, the label bitmap `bits_ptr` of
+        `n_bits` bits included, is device memory; enqueued on `stream` (raw hipStream_t handle, None / 0 = null stream).
+        A candidate-heap overflow is reported by status()."""
+        check(lib().fnv_search_batch_filtered_device(self._h, q_ptr, nq, K, ef_search, num_initializations, bits_ptr or None,
+                                                     int(n_bits), dist_ptr, label_ptr, count_ptr or None, ndist_ptr or None,
+                                                     nhops_ptr or None, stream or None))
 
     def tune(self, queries, K: int, ef_search: int, num_initializations: int = 100, nq: int = 0) -> None:
         """Settle the adaptive kernel choice for (K, ef_search, this batch size) in one call (fnv_tune): afterwards no

@@ -851,6 +851,41 @@ class Index {
     return results;
   }
 
+  // Filtered search (flatnav_hip.h, fnv_search_batch_filtered): the K nearest neighbours among the nodes whose label L is set
+  // in allowed_bits (byte L >> 3, bit L & 7; labels >= n_bits and negative labels are not allowed).  Rows with fewer than K
+  // allowed results are padded with (+inf, -1) and out_count says how many are real: not an error.  Always on this index's
+  // primary GPU.
+  void searchBatchFiltered(const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                           const uint8_t* allowed_bits, uint64_t n_bits, float* out_dist, label_t* out_labels,
+                           int32_t* out_count = nullptr) {
+    if (num_initializations <= 0) throw std::invalid_argument("num_initializations must be greater than 0.");
+    std::lock_guard<std::mutex> g(_device_guard);
+    ensureDevice();
+    std::vector<uint64_t> ndist;
+    if (_collect_stats) ndist.resize(nq);
+    detail::throwOnDeviceError(fnv_search_batch_filtered(_device_index, queries, nq, K, ef_search, num_initializations, allowed_bits,
+                                                         n_bits, out_dist, reinterpret_cast<int32_t*>(out_labels), out_count,
+                                                         _collect_stats ? ndist.data() : nullptr, nullptr));
+    if (_collect_stats) {  // same accounting as searchBatch
+      uint64_t total = static_cast<uint64_t>(num_initializations) * nq;
+      for (uint64_t v : ndist) total += v;
+      _distance_computations.fetch_add(total);
+    }
+  }
+
+  // One query: up to K (distance, label) pairs among the allowed labels, ascending (fewer when fewer are reachable).
+  std::vector<dist_label_t> searchFiltered(const void* query, const int K, int ef_search, const uint8_t* allowed_bits,
+                                           uint64_t n_bits, int num_initializations = 100) {
+    std::vector<float> dist(static_cast<size_t>(std::max(K, 0)));
+    std::vector<label_t> labels(static_cast<size_t>(std::max(K, 0)));
+    int32_t count = 0;
+    searchBatchFiltered(query, 1, K, ef_search, num_initializations, allowed_bits, n_bits, dist.data(), labels.data(), &count);
+    std::vector<dist_label_t> results;
+    results.reserve(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) results.emplace_back(dist[static_cast<size_t>(i)], labels[static_cast<size_t>(i)]);
+    return results;
+  }
+
   // ---- reordering (reference Index.h:412-440, 872-926) ---------------------------------------
   void doGraphReordering(const std::vector<std::string>& reordering_methods) {
     for (const auto& method : reordering_methods) {

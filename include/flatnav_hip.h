@@ -276,6 +276,32 @@ int fnv_search_batch_device(fnv_index_t index, const void* d_queries, uint64_t n
                             int32_t* d_out_count, uint64_t* d_out_ndist, uint64_t* d_out_nhops,
                             void* hip_stream);
 
+/* Filtered search: the K nearest neighbours of each query AMONG THE NODES WHOSE LABEL IS ALLOWED.  One filter for the whole
+ * call: allowed_bits is a bitmap over label VALUES -- byte L >> 3, bit L & 7 set (little-endian bit order, as
+ * numpy.packbits(mask, bitorder="little") writes it) = label L allowed; a label that is negative or >= n_bits is not allowed.
+ * n_bits <= 2^31; allowed_bits may be NULL only when n_bits == 0 (the empty filter: every row comes back as (+inf, -1)).
+ * The search is the reference's beamSearch (Index.h:606-707) with one change: every node it reaches enters the candidates
+ * heap and navigates, only allowed nodes enter the result heap (and only they move max_dist).  The entry point is chosen as
+ * without a filter.  With every label allowed the answers are exactly fnv_search_batch's: ids, distance bits, out_count,
+ * out_ndist and out_nhops.  Fewer than K results is a normal outcome: the row is padded with (+inf, -1) and out_count[q]
+ * says how many are real -- not an error.  A search that needs more candidate room than "spill_entries" (selective filters
+ * keep the candidates heap busier) reports FNV_ERR_CAPACITY, as fnv_search_batch does.  Filtered launches always run the
+ * two-heap kernel (never the merged-beam kernel), take no samples for the adaptive kernel choice and leave what it has
+ * measured as it was.  The label bitmap is translated into a node bitmap in the workspace of whichever handle or lane runs
+ * the call (labels as they are at launch time: after a reorder, for device-built indexes), so concurrent filtered calls
+ * never share one.
+ * fnv_search_batch_filtered: host buffers (allowed_bits included); thread safety as fnv_search_batch.
+ * fnv_search_batch_filtered_device: every buffer, allowed_bits included, in the index's device memory, enqueued on
+ *   `hip_stream` without synchronising; contract as fnv_search_batch_device (one launch in flight per handle; the status
+ *   of a capacity overflow comes from fnv_search_status). */
+int fnv_search_batch_filtered(fnv_index_t index, const void* queries, uint64_t nq, int K, int ef_search,
+                              int num_initializations, const void* allowed_bits, uint64_t n_bits, float* out_dist,
+                              int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist, uint64_t* out_nhops);
+int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, uint64_t nq, int K, int ef_search,
+                                     int num_initializations, const void* d_allowed_bits, uint64_t n_bits,
+                                     float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count,
+                                     uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream);
+
 /* ---- several GPUs of one node: index replicated, query rows sharded, no per-query collective -------
  * The reference parallelises a batch over host threads that share one index in memory (executeInParallel over rows,
  * python-bindings/src/flatnav/bindings.cpp:198-211, include/flatnav/util/Multithreading.h:19-48); here every GPU
