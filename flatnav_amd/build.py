@@ -24,6 +24,7 @@ MAIN = os.path.join(CSRC, "beam_search.hip")
 INST = os.path.join(CSRC, "kernel_inst.hip")
 TYPES = [("float", "f32"), ("uint8_t", "u8"), ("int8_t", "i8"), ("_Float16", "f16")]
 METRICS = [(0, "l2"), (1, "ip")]
+# (ordinal, name) as in kernel_table.h's FNV_FOR_EACH_FAMILY; a family missing here fails at link time
 FAMILIES = [(0, "exact"), (3, "wire"), (4, "merged"), (5, "merged1"), (6, "merged0"), (7, "merged2"),
             (8, "merged_d"), (9, "merged1_d"), (10, "merged0_d"), (11, "merged2_d"),  # 8-11: the DIRECT forms (small launches)
             (12, "exact_f")]  # the filtered two-heap kernel
@@ -44,7 +45,7 @@ def _units(defines):
             for fam, fname in FAMILIES:
                 units.append((os.path.join(OBJ, "inst_%s_%s_%s.o" % (fname, tag, mtag)), INST,
                               ["-DFNV_INST_T=" + ctype, "-DFNV_INST_TAG=" + tag, "-DFNV_INST_METRIC=%d" % metric,
-                               "-DFNV_INST_MTAG=" + mtag, "-DFNV_INST_FAMILY=%d" % fam]))
+                               "-DFNV_INST_MTAG=" + mtag, "-DFNV_INST_FAMILY=%d" % fam, "-DFNV_INST_FNAME=" + fname]))
     return [(o, s, f + ["-D" + d for d in defines]) for o, s, f in units]
 
 

@@ -135,29 +135,30 @@ hipError_t raise_lds_limit(const void* kern, int device, uint32_t bytes) {
 #ifndef FNV_DEV_METRIC
 #define FNV_DEV_METRIC FNV_METRIC_L2
 #endif
+#define FNV_DEV_KERNEL(K, ...) K<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true __VA_ARGS__>
 const KernelTable& kernel_table(int, int) {
   static KernelTable t = [] {
     KernelTable k;
+    const kernel_fn merged[kNumBeamForms][2] = {
+        {FNV_DEV_KERNEL(beam_search_merged_kernel, , 0), FNV_DEV_KERNEL(beam_search_merged_kernel, , 0, true)},
+        {FNV_DEV_KERNEL(beam_search_merged_kernel, , 1), FNV_DEV_KERNEL(beam_search_merged_kernel, , 1, true)},
+        {FNV_DEV_KERNEL(beam_search_merged_kernel, , 2), FNV_DEV_KERNEL(beam_search_merged_kernel, , 2, true)},
+        {FNV_DEV_KERNEL(beam_search_merged_kernel, , MB_R), FNV_DEV_KERNEL(beam_search_merged_kernel, , MB_R, true)}};
     for (int c = 0; c < kNumCfgs; c++)
       for (int f = 0; f < 2; f++) {
-        k.exact[c][f] = beam_search_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
-        k.exact_f[c][f] = beam_search_filtered_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
-        k.scan[c][f] = entry_scan_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
-        k.merged[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, MB_R>;
-        k.merged1[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 1>;
-        k.merged0[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 0>;
-        k.merged2[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 2>;
-        k.merged_d[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, MB_R, true>;
-        k.merged1_d[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 1, true>;
-        k.merged0_d[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 0, true>;
-        k.merged2_d[c][f] = beam_search_merged_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true, 2, true>;
-        k.select[c][f] = wire_select_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
-        k.connect[c][f] = wire_connect_kernel<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true>;
+        k.exact[c][f] = FNV_DEV_KERNEL(beam_search_kernel);
+        k.exact_f[c][f] = FNV_DEV_KERNEL(beam_search_filtered_kernel);
+        k.scan[c][f] = FNV_DEV_KERNEL(entry_scan_kernel);
+        for (int form = 0; form < kNumBeamForms; form++)
+          for (int d = 0; d < 2; d++) k.merged[form][d][c][f] = merged[form][d];
+        k.select[c][f] = FNV_DEV_KERNEL(wire_select_kernel);
+        k.connect[c][f] = FNV_DEV_KERNEL(wire_connect_kernel);
       }
     return k;
   }();
   return t;
 }
+#undef FNV_DEV_KERNEL
 #else
 // Product builds: the instantiations live in kernel_inst.hip objects (one per family x element type x metric).
 const KernelTable& kernel_table(int dtype, int metric) {
@@ -165,21 +166,13 @@ const KernelTable& kernel_table(int dtype, int metric) {
   static std::once_flag once;
   std::call_once(once, [] {
     int i = 0;
-#define FNV_FILL(T, tag, M, mtag)              \
-    fill_exact_##tag##_##mtag(tables[i]);       \
-    fill_exact_f_##tag##_##mtag(tables[i]);     \
-    fill_merged_##tag##_##mtag(tables[i]);      \
-    fill_merged1_##tag##_##mtag(tables[i]);     \
-    fill_merged0_##tag##_##mtag(tables[i]);     \
-    fill_merged2_##tag##_##mtag(tables[i]);     \
-    fill_merged_d_##tag##_##mtag(tables[i]);    \
-    fill_merged1_d_##tag##_##mtag(tables[i]);   \
-    fill_merged0_d_##tag##_##mtag(tables[i]);   \
-    fill_merged2_d_##tag##_##mtag(tables[i]);   \
-    fill_wire_##tag##_##mtag(tables[i]);        \
+#define FNV_FILL_FAMILY(ordinal, family, tag, mtag) fill_##family##_##tag##_##mtag(tables[i]);
+#define FNV_FILL(T, tag, M, mtag)                       \
+    FNV_FOR_EACH_FAMILY(FNV_FILL_FAMILY, tag, mtag) \
     i++;
     FNV_FOR_EACH_TYPE_METRIC(FNV_FILL)
 #undef FNV_FILL
+#undef FNV_FILL_FAMILY
   });
   int t;  // order of FNV_FOR_EACH_TYPE_METRIC; every caller has passed validate_geometry (dtype_size != 0)
   switch (dtype) {
@@ -197,9 +190,7 @@ kernel_fn pick_kernel(int dtype, int metric, int cfg, bool full) { return kernel
 kernel_fn pick_filtered_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).exact_f[cfg][full]; }
 kernel_fn pick_scan_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).scan[cfg][full]; }
 kernel_fn pick_sorted_kernel(int dtype, int metric, int cfg, bool full, bool lds, int B, bool direct = false) {
-  const KernelTable& t = kernel_table(dtype, metric);
-  if (direct) return lds ? t.merged0_d[cfg][full] : B <= WAVE ? t.merged1_d[cfg][full] : B <= 2 * WAVE ? t.merged2_d[cfg][full] : t.merged_d[cfg][full];
-  return lds ? t.merged0[cfg][full] : B <= WAVE ? t.merged1[cfg][full] : B <= 2 * WAVE ? t.merged2[cfg][full] : t.merged[cfg][full];
+  return kernel_table(dtype, metric).merged[beam_form(lds, B)][direct][cfg][full];
 }
 wire_fn pick_wire_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).select[cfg][full]; }
 wire_fn pick_connect_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).connect[cfg][full]; }
@@ -228,18 +219,81 @@ struct SearchFilter {
   uint64_t n_bits;
 };
 
-// A host-buffer search that went through the pinned staging buffer: what search_host_finish copies where.
+// Where a search writes: [nq][K] distances and labels, and per query (each optional) the result count and the counters.
+struct SearchOutputs {
+  float* dist = nullptr;
+  int32_t* labels = nullptr;
+  int32_t* count = nullptr;
+  uint64_t *ndist = nullptr, *nhops = nullptr;
+};
+
+// One slab of `nq` x `K` results at `base`: dist | labels | count | ndist | nhops (the counters 8-byte aligned).
+// Returns the arrays; `bytes`: the slab's size (a null `base` asks for that alone).
+static SearchOutputs lay_out_slab(void* base, uint64_t nq, int K, size_t* bytes = nullptr) {
+  const uintptr_t b = (uintptr_t)base;
+  const size_t o_lab = (size_t)nq * K * 4;
+  const size_t o_cnt = o_lab + (size_t)nq * K * 4;
+  const size_t o_nd = (o_cnt + (size_t)nq * 4 + 7) & ~(size_t)7;
+  const size_t o_nh = o_nd + (size_t)nq * 8;
+  if (bytes) *bytes = o_nh + (size_t)nq * 8;
+  return SearchOutputs{(float*)b, (int32_t*)(b + o_lab), (int32_t*)(b + o_cnt), (uint64_t*)(b + o_nd), (uint64_t*)(b + o_nh)};
+}
+
+// What one search launch does differently from a plain one: a call names only what it changes.
+struct SearchOptions {
+  bool node_ids = false;            // write node ids whatever "output_node_ids" says (the device builder's beams)
+  int force_variant = -1;           // >= 0: fnv_tune's launches (an argument, not index state: a concurrent caller's launch on
+                                    // the same handle is never forced)
+  int32_t* host_status = nullptr;   // zero-copy small searches: the error flag's copy in the caller's pinned slab
+  const SearchFilter* filter = nullptr;  // filtered search: every query runs the filtered two-heap kernel
+};
+
+// A host-buffer search that went through a pinned slab: what search_host_finish copies where.
 struct PinnedCall {
   bool active = false;
-  const uint8_t* slab = nullptr;
+  SearchOutputs slab, user;  // the results in pinned memory; the caller's arrays
   const int32_t* status = nullptr;
   uint64_t nq = 0;
   int K = 0;
-  size_t o_lab = 0, o_cnt = 0, o_nd = 0, o_nh = 0;
-  float* out_dist = nullptr;
-  int32_t* out_labels = nullptr;
-  int32_t* out_count = nullptr;
-  uint64_t *out_ndist = nullptr, *out_nhops = nullptr;
+  void arm(const SearchOutputs& slab_, const int32_t* status_, const SearchOutputs& user_, uint64_t nq_, int K_) {
+    active = true;
+    slab = slab_;
+    status = status_;
+    user = user_;
+    nq = nq_;
+    K = K_;
+  }
+};
+
+// A buffer that grows on demand (never shrinks) and frees itself with its owner: device memory, or pinned host memory.
+struct DeviceBuf {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  const bool host;
+  explicit DeviceBuf(bool pinned_host = false) : host(pinned_host) {}
+  DeviceBuf(const DeviceBuf&) = delete;
+  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  ~DeviceBuf() { release(); }
+  template <typename T>
+  T* as() const { return (T*)ptr; }
+  // At least `need` bytes (`headroom` more when it has to be allocated anew); the contents are not kept.
+  int grow(size_t need, bool zero = false, size_t headroom = 0) {
+    if (need <= bytes) return FNV_OK;
+    if (ptr) HIP_TRY(host ? hipHostFree(ptr) : hipFree(ptr));
+    ptr = nullptr;
+    bytes = 0;
+    HIP_TRY(host ? hipHostMalloc(&ptr, need + headroom, hipHostMallocDefault) : hipMalloc(&ptr, need + headroom));
+    if (zero) HIP_TRY(hipMemset(ptr, 0, need + headroom));
+    bytes = need + headroom;
+    return FNV_OK;
+  }
+  size_t release() {  // returns the bytes given back
+    if (ptr) (void)(host ? hipHostFree(ptr) : hipFree(ptr));
+    const size_t freed = bytes;
+    ptr = nullptr;
+    bytes = 0;
+    return freed;
+  }
 };
 
 // Everything fnv_set_option can change: one block, so that views and replicas start as exact copies of their source.
@@ -310,41 +364,31 @@ struct fnv_index_s : IndexOptions {
   bool last_shadow = false;       // ... and whether every query had an exact shadow (small launches)
   // host-buffer searches: steady-clock time of launch / of completion (atomic: every lane's caller reports into the handle)
   std::atomic<uint64_t> t_enqueue_ns{0}, t_complete_ns{0};
-  // workspace (grown on demand)
   uint32_t* d_dispenser = nullptr;  // [0] dispenser, [1] status, [3] queries a merged-beam launch handed to the exact search, [4..7] by
                                     // reason, [8] of them resumed from their log, [9] hops taken from logs, [10] hops of those queries
   unsigned long long* d_phase = nullptr;  // profiling builds only
-  void* d_entry = nullptr;  // [nq] uint32 entry nodes | [nq] float entry distances (K0 output)
-  size_t entry_bytes = 0;
-  uint32_t* d_bitmap = nullptr;
-  size_t bitmap_bytes = 0;
-  void* d_wirebuf = nullptr;  // fnv_index_insert_batch: [count*keep] x {req_target, req_index, sorted_target, sorted_req} | sort scratch
-  size_t wirebuf_bytes = 0;
-  uint32_t* d_ovf = nullptr;  // [nslots][ovf_cap] ids whose bitmap words need clearing (big indexes)
-  size_t ovf_bytes = 0;
-  void* d_nodestage = nullptr;  // write_nodes: AoS staging chunk + bad flag
-  size_t nodestage_bytes = 0;
-  void* d_linkstage = nullptr;  // fnv_index_write_links: [count] ids | [count][M] rows | bad flag
-  size_t linkstage_bytes = 0;
-  unsigned long long* d_spill = nullptr;
-  size_t spill_bytes = 0;
-  uint32_t* d_done = nullptr;  // shadow mode: [nq] "answered" flags
-  size_t done_bytes = 0;
-  unsigned long long* d_tielog = nullptr;  // merged-beam kernel: [nslots][log_entries] hand-over log (round 5)
-  size_t tielog_bytes = 0;
-  uint32_t* d_nodebits = nullptr;  // filtered search: [capacity / 32] words, bit per node id (node_filter_kernel)
-  size_t nodebits_bytes = 0;
-  uint8_t* d_allowed = nullptr;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM
-  size_t allowed_bytes = 0;
+  // The launch workspace, per query slot: what search_device_impl grows, free_lane_workspace gives back and ws_bytes counts.
+  struct Workspace {
+    DeviceBuf bitmap;  // uint32 [nslots][bitmap_words]: the visited set's HBM part
+    DeviceBuf ovf;     // uint32 [nslots][ovf_cap] ids whose bitmap words need clearing (big indexes)
+    DeviceBuf spill;   // uint64 [nslots][spill_entries]: what the candidates heap does not keep in LDS
+    DeviceBuf tielog;  // uint64, merged-beam kernel: [nslots][log_entries] hand-over log (round 5)
+    size_t bytes() const { return bitmap.bytes + ovf.bytes + spill.bytes + tielog.bytes; }
+    size_t release() { return bitmap.release() + ovf.release() + spill.release() + tielog.release(); }
+  } ws;
+  // further buffers, each grown on demand
+  DeviceBuf d_entry;      // [nq] uint32 entry nodes | [nq] float entry distances (K0 output)
+  DeviceBuf d_done;       // uint32, shadow mode: [nq] "answered" flags
+  DeviceBuf d_nodebits;   // uint32, filtered search: [capacity / 32] words, bit per node id (node_filter_kernel)
+  DeviceBuf d_allowed;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM
+  DeviceBuf d_wirebuf;    // fnv_index_insert_batch: [count*keep] x {req_target, req_index, sorted_target, sorted_req} | sort scratch
+  DeviceBuf d_nodestage;  // write_nodes: AoS staging chunk + bad flag
+  DeviceBuf d_linkstage;  // fnv_index_write_links: [count] ids | [count][M] rows | bad flag
   // staging for the host-buffer entry point
+  DeviceBuf d_q, d_out;
   void* h_pin = nullptr;  // 1 MB of pinned host memory: staging of small host-buffer searches
-  void* h_res = nullptr;  // pinned host memory for the result slab of larger host-buffer searches (grown on demand)
-  size_t h_res_bytes = 0;
+  DeviceBuf h_res{true};  // pinned host memory for the result slab of larger host-buffer searches
   PinnedCall pin;
-  void* d_q = nullptr;
-  size_t d_q_bytes = 0;
-  void* d_out = nullptr;
-  size_t d_out_bytes = 0;
   hipStream_t stream = nullptr;  // owned, used by fnv_search_batch
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t last_stream = nullptr;
@@ -472,14 +516,9 @@ int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes,
   const uint64_t chunk_nodes = std::max<uint64_t>(1, (256ull << 20) / node_size);
   // staging area: [chunk of AoS records][bad flag]; kept on the index (a device build writes dozens of batches)
   const size_t need = std::min(chunk_nodes, count_nodes) * node_size + 16;
-  if (need > ix->nodestage_bytes) {
-    if (ix->d_nodestage) HIP_TRY(hipFree(ix->d_nodestage));
-    ix->d_nodestage = nullptr;
-    ix->nodestage_bytes = 0;
-    HIP_TRY(hipMalloc(&ix->d_nodestage, need));
-    ix->nodestage_bytes = need;
-  }
-  uint8_t* d_stage = (uint8_t*)ix->d_nodestage;
+  int rcg = ix->d_nodestage.grow(need);
+  if (rcg) return rcg;
+  uint8_t* d_stage = ix->d_nodestage.as<uint8_t>();
   int* d_bad = (int*)(d_stage + (need - 16));
   auto cleanup = [&]() {};
 #define UP_TRY(expr)                                                                                   \
@@ -582,11 +621,7 @@ int fnv_index_upload(const void* aos_blob, uint64_t node_size, uint64_t data_siz
 
   int bad = 0;
   rc = write_nodes_impl(ix, 0, n_nodes, aos_blob, node_size, data_size, n_nodes, &bad);
-  if (ix->d_nodestage) {  // a one-off upload does not keep its (up to 256 MB) staging chunk
-    (void)hipFree(ix->d_nodestage);
-    ix->d_nodestage = nullptr;
-    ix->nodestage_bytes = 0;
-  }
+  ix->d_nodestage.release();  // a one-off upload does not keep its (up to 256 MB) staging chunk
   if (rc) {
     fnv_index_free(ix);
     return rc;
@@ -689,7 +724,7 @@ int fnv_index_info(fnv_index_t ix, uint64_t info[8]) {
   info[4] = ix->dim;
   info[5] = (uint64_t)ix->metric;
   info[6] = (uint64_t)ix->device;
-  info[7] = ix->capacity * ((uint64_t)ix->row_bytes + ix->tail_bytes + 4ull * ix->M + 4) + ix->bitmap_bytes + ix->spill_bytes;
+  info[7] = ix->capacity * ((uint64_t)ix->row_bytes + ix->tail_bytes + 4ull * ix->M + 4) + ix->ws.bitmap.bytes + ix->ws.spill.bytes;
   return FNV_OK;
 }
 
@@ -705,15 +740,13 @@ int fnv_index_free(fnv_index_t ix) {
   if (ix->stream) (void)hipStreamSynchronize(ix->stream);
   if (ix->parent) ix->parent->n_views.fetch_sub(1);
   if (!ix->owns_buffers) ix->d_vectors = nullptr, ix->d_links = nullptr, ix->d_labels = nullptr;
-  void* bufs[] = {ix->d_vectors, ix->d_links, ix->d_labels, ix->d_dispenser, ix->d_bitmap, ix->d_ovf, ix->d_nodestage, ix->d_linkstage, ix->d_wirebuf, ix->d_spill, ix->d_q, ix->d_out, ix->d_phase, ix->d_entry, ix->d_done, ix->d_tielog, ix->d_nodebits, ix->d_allowed};
-  for (void* b : bufs)
+  for (void* b : {(void*)ix->d_vectors, (void*)ix->d_links, (void*)ix->d_labels, (void*)ix->d_dispenser, (void*)ix->d_phase})
     if (b) (void)hipFree(b);
   if (ix->h_pin) (void)hipHostFree(ix->h_pin);
-  if (ix->h_res) (void)hipHostFree(ix->h_res);
   if (ix->ev0) (void)hipEventDestroy(ix->ev0);
   if (ix->ev1) (void)hipEventDestroy(ix->ev1);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
-  delete ix;
+  delete ix;  // (every DeviceBuf frees itself)
   return FNV_OK;
 }
 
@@ -748,14 +781,9 @@ int fnv_index_write_links(fnv_index_t ix, const uint32_t* node_ids, const uint32
   std::lock_guard<std::mutex> lock(ix->mu);
   ON_DEVICE(ix->device);
   const size_t need = (size_t)count * (4 + 4ull * ix->M) + sizeof(int);
-  if (need > ix->linkstage_bytes) {
-    if (ix->d_linkstage) HIP_TRY(hipFree(ix->d_linkstage));
-    ix->d_linkstage = nullptr;
-    ix->linkstage_bytes = 0;
-    HIP_TRY(hipMalloc(&ix->d_linkstage, need + need / 2));
-    ix->linkstage_bytes = need + need / 2;
-  }
-  uint32_t* d_ids = (uint32_t*)ix->d_linkstage;
+  int rc = ix->d_linkstage.grow(need, false, need / 2);
+  if (rc) return rc;
+  uint32_t* d_ids = ix->d_linkstage.as<uint32_t>();
   uint32_t* d_rows = d_ids + count;
   int* d_bad = (int*)(d_rows + count * ix->M);
   HIP_TRY(hipMemcpy(d_ids, node_ids, count * 4, hipMemcpyHostToDevice));
@@ -830,19 +858,16 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   return FNV_OK;
 }
 
-// One batched search launch; node_ids: write node ids instead of labels (the device builder's beams).
-static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
-                              int num_initializations, float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count,
-                              uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream, bool node_ids,
-                              int force_variant = -1, bool ids_by_option = false, int32_t* host_status = nullptr,
-                              const SearchFilter* filter = nullptr);
+// One batched search launch.
+static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                              const SearchOutputs& out, void* hip_stream, const SearchOptions& opt = SearchOptions());
 
 int fnv_search_batch_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
                             int num_initializations, float* d_out_dist, int32_t* d_out_labels,
                             int32_t* d_out_count, uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream) {
   if (!ix) return fail(FNV_ERR_INVALID, "index is null");
-  return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations, d_out_dist, d_out_labels, d_out_count,
-                            d_out_ndist, d_out_nhops, hip_stream, false, -1, /*ids_by_option=*/true);
+  return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations,
+                            SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, d_out_nhops}, hip_stream);
 }
 
 // ---- launch configuration ---------------------------------------------------------------------------------
@@ -1019,39 +1044,27 @@ static int configure_launch(fnv_index_s* ix, SearchParams& p, kernel_fn kern, in
   return FNV_OK;
 }
 
-static int grow(void** buf, size_t* have, size_t need, bool zero = false) {
-  if (need <= *have) return FNV_OK;
-  if (*buf) HIP_TRY(hipFree(*buf));
-  *buf = nullptr;
-  *have = 0;
-  HIP_TRY(hipMalloc(buf, need));
-  if (zero) HIP_TRY(hipMemset(*buf, 0, need));
-  *have = need;
-  return FNV_OK;
-}
-
-// Set while fnv_tune / fnv_index_insert_batch run: this thread holds ix->lane_mu AND every lane's host_mu of that handle
-// (taken up front, so that no host-buffer search runs on a lane meanwhile).  release_idle_lanes then frees with the locks
-// it already has -- try_lock on a std::mutex the calling thread owns is undefined behaviour.
+// While fnv_tune / fnv_index_insert_batch run, their thread holds the handle's host_mu and lane_mu AND every lane's host_mu
+// (taken up front, so that no host-buffer search runs on a lane meanwhile: the existing lanes are locked, and none is created --
+// a caller that wants one waits on lane_mu, holding nothing).  release_idle_lanes then frees with the locks it already
+// has -- try_lock on a std::mutex the calling thread owns is undefined behaviour.
 static thread_local const fnv_index_s* t_holds_lanes_of = nullptr;
-struct HoldsLanes {
+struct HoldAllLanes {
+  std::lock_guard<std::mutex> host_lock, no_new_lanes;
+  std::vector<std::unique_lock<std::mutex>> lane_locks;
   const fnv_index_s* before;
-  explicit HoldsLanes(const fnv_index_s* ix) : before(t_holds_lanes_of) { t_holds_lanes_of = ix; }
-  ~HoldsLanes() { t_holds_lanes_of = before; }
+  explicit HoldAllLanes(fnv_index_s* ix) : host_lock(ix->host_mu), no_new_lanes(ix->lane_mu), before(t_holds_lanes_of) {
+    for (std::atomic<fnv_index_s*>& slot : ix->lanes)
+      if (fnv_index_s* l = slot.load()) lane_locks.emplace_back(l->host_mu);
+    t_holds_lanes_of = ix;
+  }
+  ~HoldAllLanes() { t_holds_lanes_of = before; }
 };
 
 static size_t free_lane_workspace(fnv_index_s* l) {  // the caller owns l->host_mu
   std::lock_guard<std::mutex> lk(l->mu);
   DeviceScope scope(l->device);
-  size_t freed = 0;
-  void** bufs[] = {(void**)&l->d_bitmap, (void**)&l->d_ovf, (void**)&l->d_spill, (void**)&l->d_tielog};
-  size_t* sizes[] = {&l->bitmap_bytes, &l->ovf_bytes, &l->spill_bytes, &l->tielog_bytes};
-  for (int i = 0; i < 4; i++) {
-    if (*bufs[i]) (void)hipFree(*bufs[i]);
-    *bufs[i] = nullptr;
-    freed += *sizes[i];
-    *sizes[i] = 0;
-  }
+  const size_t freed = l->ws.release();
   l->ws_bytes = 0;
   return freed;
 }
@@ -1092,184 +1105,202 @@ static uint32_t log_entries_for(const fnv_index_s* ix, int B) {
   return std::min<uint32_t>(16384u, std::max<uint32_t>(1024u, pow2_ceil(24ull * (uint64_t)B + 512)));
 }
 
-// HBM a launch of `nq` queries needs as per-slot workspace on a handle of this index (what search_device_impl grows).
+// Per query slot of a launch on this index: words of the visited set's HBM bitmap (whole 16-byte groups: wide clears) and
+// entries of the list of ids whose bitmap words need clearing.
+static uint32_t bitmap_words_of(const fnv_index_s* ix) { return (uint32_t)(((ix->capacity + 31) / 32 + 3) / 4 * 4); }
+static uint32_t ovf_cap_of(const fnv_index_s* ix) {
+  return ix->overflow_list >= 0 ? (uint32_t)ix->overflow_list : ((uint64_t)bitmap_words_of(ix) * 4 > (512u << 10) ? 16384u : 0u);
+}
+
+// HBM a launch of `nq` queries needs as per-slot workspace on a handle of this index (what grow_workspace grows).
 static size_t launch_workspace_bytes(fnv_index_s* ix, uint64_t nq) {
   std::lock_guard<std::mutex> lock(ix->mu);
-  const uint64_t bitmap_words = ((ix->capacity + 31) / 32 + 3) / 4 * 4;
-  const uint64_t ovf_cap = ix->overflow_list >= 0 ? (uint64_t)ix->overflow_list : (bitmap_words * 4 > (512u << 10) ? 16384u : 0u);
   const int per_cu = ix->plan.valid ? std::max(ix->plan.bpc, ix->plan.sbpc) : 32;  // (no plan yet: the hardware's 32 waves per CU)
   const uint64_t slots = std::min<uint64_t>(2 * nq, (uint64_t)per_cu * (uint64_t)ix->num_cus);  // (small launches: a shadow per query)
   // (the plan's own formula -- plan.sorted is unset while the plan runs the two-heap kernel only; no plan yet: the largest automatic log)
   const uint64_t log_entries = ix->plan.valid ? log_entries_for(ix, ix->plan.B) : (ix->tie_replay ? std::max<uint64_t>(16384u, (uint64_t)ix->tie_log_entries) : 0u);
-  return (size_t)(slots * (bitmap_words * 4 + ovf_cap * 4 + (uint64_t)ix->spill_entries * 8 + log_entries * 8));
+  return (size_t)(slots * ((uint64_t)bitmap_words_of(ix) * 4 + (uint64_t)ovf_cap_of(ix) * 4 + (uint64_t)ix->spill_entries * 8 + log_entries * 8));
 }
 
-static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
-                              int num_initializations, float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count,
-                              uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream, bool node_ids,
-                              int force_variant,  // >= 0: fnv_tune's launches (an argument, not index state: a concurrent
-                                                  // caller's launch on the same handle is never forced)
-                              bool ids_by_option,  // node_ids = the "output_node_ids" option, read under the handle's mutex
-                              int32_t* host_status,  // zero-copy small searches: the error flag's copy in the caller's pinned slab
-                              const SearchFilter* filter) {  // filtered search: every query runs the filtered two-heap kernel
-  if (!ix) return fail(FNV_ERR_INVALID, "index is null");
-  // Index.h:847-849
-  if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
-  if (K <= 0 || ef_search <= 0) return fail(FNV_ERR_INVALID, "K and ef_search must be positive");
-  if (nq == 0) return FNV_OK;
-  if (!d_queries || !d_out_dist || !d_out_labels) return fail(FNV_ERR_INVALID, "null buffer");
-  if (nq > 0x7FFFFFFFull) return fail(FNV_ERR_INVALID, "too many queries in one batch");
-  std::lock_guard<std::mutex> lock(ix->mu);
-  if (ids_by_option) node_ids = ix->output_node_ids != 0;
-  ON_DEVICE(ix->device);
-  hipStream_t stream = (hipStream_t)hip_stream;
+// How the kernels walk a row of this index: the row configuration, the chunks of a staged query, whether rows are whole spans.
+struct RowGeometry {
+  int cfg;
+  uint32_t nchunks, tail_chunks, q_chunks;
+  bool full;
+};
+static RowGeometry row_geometry(const fnv_index_s* ix) {
+  RowGeometry g;
+  g.nchunks = ix->row_bytes / 16;
+  g.tail_chunks = ix->tail_bytes / 16;
+  g.cfg = pick_row_cfg(g.nchunks, g.tail_chunks);
+  const uint32_t per_iter = (uint32_t)(kCfgs[g.cfg].G * kCfgs[g.cfg].CU);
+  g.q_chunks = (g.nchunks + per_iter - 1) / per_iter * per_iter;
+  if (g.tail_chunks) g.q_chunks = g.nchunks + (uint32_t)kCfgs[g.cfg].G;  // split rows: lane g also reads query chunk 24 + g (zero past the row)
+  g.full = g.tail_chunks == 0 && (g.nchunks % per_iter) == 0;  // rows are whole spans: the lean FULL kernels apply
+                                                                // (the three-line configuration's non-FULL form IS the split-row kernel)
+  return g;
+}
 
-  // ---- launch plan: depends on (beam width, K, live geometry, options) only -> cached between calls ------------
-  const int B = std::max(ef_search, K);  // Index.h:392
+// The adaptive choice keeps its measurements per (beam width, batch class: more than one round of queries or not).
+static int tuner_key(int B, bool multi_round) { return 2 * B + (multi_round ? 1 : 0); }
+
+// The status word of a launch -> the call's result (`advice`: how each caller has always ended the message).
+static int check_status(int32_t st, const char* advice = "raise the spill_entries option") {
+  if (st == ST_CAND_OVERFLOW) return fail(FNV_ERR_CAPACITY, std::string("candidate heap overflowed its HBM spill area; ") + advice);
+  return FNV_OK;
+}
+static int check_device_status(fnv_index_s* ix, const char* advice = "raise the spill_entries option") {  // (the stream has been waited for)
+  int32_t st = 0;
+  HIP_TRY(hipMemcpy(&st, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return check_status(st, advice);
+}
+
+// ---- one search launch, step by step (search_device_impl runs them in this order under the handle's mutex) -----------
+// (a) The launch plan: depends on (beam width, K, live geometry, options) only -> cached between calls.
+static int ensure_plan(fnv_index_s* ix, int B, int K) {
   LaunchPlan& plan = ix->plan;
-  if (!(plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity &&
-        plan.options_version == ix->options_version)) {
-    plan = LaunchPlan();
-    SearchParams p;
-    memset(&p, 0, sizeof(p));
-    p.vectors = ix->d_vectors;
-    p.tails = ix->tails();
-    p.tail_chunks = ix->tail_bytes / 16;
-    p.links = ix->d_links;
-    p.M = ix->M;
-    p.dim = ix->dim;
-    p.row_bytes = ix->row_bytes;
-    p.nchunks = ix->row_bytes / 16;
-    p.K = K;
-    p.B = B;
-    const int cfg = pick_row_cfg(p.nchunks, p.tail_chunks);
-    const uint32_t per_iter = (uint32_t)(kCfgs[cfg].G * kCfgs[cfg].CU);
-    p.q_chunks = (p.nchunks + per_iter - 1) / per_iter * per_iter;
-    if (p.tail_chunks) p.q_chunks = p.nchunks + (uint32_t)kCfgs[cfg].G;  // split rows: lane g also reads query chunk 24 + g (zero past the row)
-    p.q_lds_bytes = cfg_query_in_regs(cfg) ? 0u : p.q_chunks * 16u;
-    p.cand_slots = ix->cand_slots ? (uint32_t)ix->cand_slots : (uint32_t)(ix->cand_factor * p.B + 192);
-    p.cand_slots = std::max<uint32_t>(p.cand_slots, (uint32_t)p.B + 1);  // also hosts the final result list
-    p.spill_entries = (uint32_t)ix->spill_entries;
-    p.bitmap_words = (uint32_t)(((ix->capacity + 31) / 32 + 3) / 4 * 4);  // whole 16-byte groups: wide clears
-    p.ovf_cap = ix->overflow_list >= 0 ? (uint32_t)ix->overflow_list
-                                       : ((uint64_t)p.bitmap_words * 4 > (512u << 10) ? 16384u : 0u);
-    p.log_entries = log_entries_for(ix, p.B);
-    const bool full = p.tail_chunks == 0 && (p.nchunks % per_iter) == 0;  // rows are whole spans: the lean FULL kernels apply
-                                                                            // (the three-line configuration's non-FULL form IS the split-row kernel)
-    plan.cfg = cfg;
-    plan.full = full;
+  if (plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity && plan.options_version == ix->options_version)
+    return FNV_OK;
+  plan = LaunchPlan();
+  const RowGeometry g = row_geometry(ix);
+  SearchParams p;
+  memset(&p, 0, sizeof(p));
+  p.vectors = ix->d_vectors;
+  p.tails = ix->tails();
+  p.tail_chunks = g.tail_chunks;
+  p.links = ix->d_links;
+  p.M = ix->M;
+  p.dim = ix->dim;
+  p.row_bytes = ix->row_bytes;
+  p.nchunks = g.nchunks;
+  p.K = K;
+  p.B = B;
+  p.q_chunks = g.q_chunks;
+  p.q_lds_bytes = cfg_query_in_regs(g.cfg) ? 0u : p.q_chunks * 16u;
+  p.cand_slots = ix->cand_slots ? (uint32_t)ix->cand_slots : (uint32_t)(ix->cand_factor * p.B + 192);
+  p.cand_slots = std::max<uint32_t>(p.cand_slots, (uint32_t)p.B + 1);  // also hosts the final result list
+  p.spill_entries = (uint32_t)ix->spill_entries;
+  p.bitmap_words = bitmap_words_of(ix);
+  p.ovf_cap = ovf_cap_of(ix);
+  p.log_entries = log_entries_for(ix, p.B);
+  plan.cfg = g.cfg;
+  plan.full = g.full;
 
-    // the exact two-heap kernel: always configured (it also replays what a merged-beam kernel hands over)
-    plan.heaps = p;
-    plan.kern = pick_kernel(ix->dtype, ix->metric, cfg, full);
-    int rc = configure_launch(ix, plan.heaps, plan.kern, MODE_HEAPS, &plan.lds, &plan.bpc);
+  // the exact two-heap kernel: always configured (it also replays what a merged-beam kernel hands over)
+  plan.heaps = p;
+  plan.kern = pick_kernel(ix->dtype, ix->metric, g.cfg, g.full);
+  int rc = configure_launch(ix, plan.heaps, plan.kern, MODE_HEAPS, &plan.lds, &plan.bpc);
+  if (rc) return rc;
+
+  // Merged-beam kernel (merged_beam.hpp): the beam as one sorted array, one merge per link row -- in registers for
+  // beams of at most 256 entries ("beam_registers" = 0: never), else in LDS; queries in which equal keys meet at a
+  // decision are searched again by the same wave with the exact two-heap code.  Same results.  "sorted_beam":
+  // 0 = never, 1 = always, 2 (default) = adaptive: measured against the two-heap kernel per beam width (below).
+  const bool tagged = plan.heaps.vis_tag16 != 0;
+  const bool want = ix->sorted_beam != 0 && B >= ix->sorted_beam_min && ix->capacity < (1ull << 31);
+  plan.mode = (!tagged || !want) ? MODE_HEAPS : (B <= MB_MAX_BEAM && ix->beam_registers != 0) ? MODE_MERGED_REGS : MODE_MERGED_LDS;
+  if (plan.mode != MODE_HEAPS) {
+    plan.skern = pick_sorted_kernel(ix->dtype, ix->metric, g.cfg, g.full, plan.mode == MODE_MERGED_LDS, B);
+    plan.skern_direct = pick_sorted_kernel(ix->dtype, ix->metric, g.cfg, g.full, plan.mode == MODE_MERGED_LDS, B, true);
+    // a layout that fnv_tune measured for this beam width overrides the rules below (heap home, table size)
+    fnv_index_s::LayoutChoice lc;
+    if (auto it = ix->layouts.find(B); it != ix->layouts.end()) lc = it->second;
+    const int64_t cand_lds_mode = lc.cand_lds >= 0 ? lc.cand_lds : ix->sorted_cand_lds;
+    const uint32_t forced = lc.vis_slots;
+    // the exact re-run's candidates heap: in LDS if that costs neither resident queries nor visited-table
+    // slots, else entirely in the slot's HBM spill area (slower for the few queries that need it)
+    SearchParams with = p, without = p;
+    without.cand_slots = 0;
+    uint32_t lds_w = 0, lds_wo = 0;
+    int bpc_w = 0, bpc_wo = 0;
+    rc = configure_launch(ix, without, plan.skern, plan.mode, &lds_wo, &bpc_wo, false, forced);
     if (rc) return rc;
-
-    // Merged-beam kernel (merged_beam.hpp): the beam as one sorted array, one merge per link row -- in registers for
-    // beams of at most 256 entries ("beam_registers" = 0: never), else in LDS; queries in which equal keys meet at a
-    // decision are searched again by the same wave with the exact two-heap code.  Same results.  "sorted_beam":
-    // 0 = never, 1 = always, 2 (default) = adaptive: measured against the two-heap kernel per beam width (below).
-    const bool tagged = plan.heaps.vis_tag16 != 0;
-    const bool want = ix->sorted_beam != 0 && B >= ix->sorted_beam_min && ix->capacity < (1ull << 31);
-    plan.mode = (!tagged || !want) ? MODE_HEAPS : (B <= MB_MAX_BEAM && ix->beam_registers != 0) ? MODE_MERGED_REGS : MODE_MERGED_LDS;
-    if (plan.mode != MODE_HEAPS) {
-      plan.skern = pick_sorted_kernel(ix->dtype, ix->metric, cfg, full, plan.mode == MODE_MERGED_LDS, B);
-      plan.skern_direct = pick_sorted_kernel(ix->dtype, ix->metric, cfg, full, plan.mode == MODE_MERGED_LDS, B, true);
-      // a layout that fnv_tune measured for this beam width overrides the rules below (heap home, table size)
-      fnv_index_s::LayoutChoice lc;
-      if (auto it = ix->layouts.find(B); it != ix->layouts.end()) lc = it->second;
-      const int64_t cand_lds_mode = lc.cand_lds >= 0 ? lc.cand_lds : ix->sorted_cand_lds;
-      const uint32_t forced = lc.vis_slots;
-      // the exact re-run's candidates heap: in LDS if that costs neither resident queries nor visited-table
-      // slots, else entirely in the slot's HBM spill area (slower for the few queries that need it)
-      SearchParams with = p, without = p;
-      without.cand_slots = 0;
-      uint32_t lds_w = 0, lds_wo = 0;
-      int bpc_w = 0, bpc_wo = 0;
-      rc = configure_launch(ix, without, plan.skern, plan.mode, &lds_wo, &bpc_wo, false, forced);
+    const int rc_w = configure_launch(ix, with, plan.skern, plan.mode, &lds_w, &bpc_w, false, forced);
+    // (an exact re-run whose candidates heap lives in HBM pays a global round trip per heap operation: a handful of
+    // such queries per launch are stragglers that cost 10 % of it -- measured at ef=100 on float data with 5 re-runs
+    // in 10 000 queries -- so up to beams of 128 the LDS home is worth going down to 9 resident queries; wider beams'
+    // heaps cost more LDS than the stragglers cost time)
+    bool keep_lds = rc_w == FNV_OK && (cand_lds_mode == 1 ||
+                                       (cand_lds_mode == 2 && ((bpc_w >= bpc_wo && with.vis_slots >= without.vis_slots) ||
+                                                               (B <= 2 * WAVE && bpc_w >= (int)ix->occupancy_roomy))));
+    // both candidates once more with the free table growth; an LDS home that costs residency AND table slots is not taken
+    SearchParams fin_w = p, fin_wo = p;
+    // (p's own heap size, not `with`'s: configure_launch may already have trimmed that one by up to an eighth to fit an LDS
+    //  granule, and the trim must be applied once, to the final layout)
+    fin_w.cand_slots = p.cand_slots;
+    fin_wo.cand_slots = 0u;
+    uint32_t flds_w = 0, flds_wo = 0;
+    int fbpc_w = 0, fbpc_wo = 0;
+    rc = configure_launch(ix, fin_wo, plan.skern, plan.mode, &flds_wo, &fbpc_wo, true, forced);
+    if (rc) return rc;
+    if (keep_lds) {
+      rc = configure_launch(ix, fin_w, plan.skern, plan.mode, &flds_w, &fbpc_w, true, forced);
       if (rc) return rc;
-      const int rc_w = configure_launch(ix, with, plan.skern, plan.mode, &lds_w, &bpc_w, false, forced);
-      // (an exact re-run whose candidates heap lives in HBM pays a global round trip per heap operation: a handful of
-      // such queries per launch are stragglers that cost 10 % of it -- measured at ef=100 on float data with 5 re-runs
-      // in 10 000 queries -- so up to beams of 128 the LDS home is worth going down to 9 resident queries; wider beams'
-      // heaps cost more LDS than the stragglers cost time)
-      bool keep_lds = rc_w == FNV_OK && (cand_lds_mode == 1 ||
-                                         (cand_lds_mode == 2 && ((bpc_w >= bpc_wo && with.vis_slots >= without.vis_slots) ||
-                                                                 (B <= 2 * WAVE && bpc_w >= (int)ix->occupancy_roomy))));
-      // both candidates once more with the free table growth; an LDS home that costs residency AND table slots is not taken
-      SearchParams fin_w = p, fin_wo = p;
-      // (p's own heap size, not `with`'s: configure_launch may already have trimmed that one by up to an eighth to fit an LDS
-      //  granule, and the trim must be applied once, to the final layout)
-      fin_w.cand_slots = p.cand_slots;
-      fin_wo.cand_slots = 0u;
-      uint32_t flds_w = 0, flds_wo = 0;
-      int fbpc_w = 0, fbpc_wo = 0;
-      rc = configure_launch(ix, fin_wo, plan.skern, plan.mode, &flds_wo, &fbpc_wo, true, forced);
-      if (rc) return rc;
-      if (keep_lds) {
-        rc = configure_launch(ix, fin_w, plan.skern, plan.mode, &flds_w, &fbpc_w, true, forced);
-        if (rc) return rc;
-        if (cand_lds_mode == 2 && fin_w.vis_slots < fin_wo.vis_slots && fbpc_w < fbpc_wo) keep_lds = false;
-      }
-      plan.sorted = keep_lds ? fin_w : fin_wo;
-      plan.slds = keep_lds ? flds_w : flds_wo;
-      plan.sbpc = keep_lds ? fbpc_w : fbpc_wo;
-      if (!plan.sorted.vis_tag16) plan.mode = MODE_HEAPS;
-      if ((uint64_t)plan.sorted.cand_slots + plan.sorted.spill_entries < 3ull * (uint64_t)B + 256) plan.mode = MODE_HEAPS;
+      if (cand_lds_mode == 2 && fin_w.vis_slots < fin_wo.vis_slots && fbpc_w < fbpc_wo) keep_lds = false;
     }
-    plan.B = B;
-    plan.K = K;
-    plan.capacity = ix->capacity;
-    plan.options_version = ix->options_version;
-    plan.valid = true;
+    plan.sorted = keep_lds ? fin_w : fin_wo;
+    plan.slds = keep_lds ? flds_w : flds_wo;
+    plan.sbpc = keep_lds ? fbpc_w : fbpc_wo;
+    if (!plan.sorted.vis_tag16) plan.mode = MODE_HEAPS;
+    if ((uint64_t)plan.sorted.cand_slots + plan.sorted.spill_entries < 3ull * (uint64_t)B + 256) plan.mode = MODE_HEAPS;
   }
+  plan.B = B;
+  plan.K = K;
+  plan.capacity = ix->capacity;
+  plan.options_version = ix->options_version;
+  plan.valid = true;
+  return FNV_OK;
+}
+
+// (b) Which kernel variant the launch runs, and whether it is a sample for the adaptive choice.
+struct KernelChoice {
+  bool sorted;  // the merged-beam kernel (else the two-heap kernel, or its filtered form)
+  int variant;
+  bool multi_round, sample = false, exploratory = false;
+  int64_t tail_pct;
+};
+static KernelChoice choose_kernel(fnv_index_s* ix, int B, uint64_t nq, int force_variant, bool filtered) {
+  const LaunchPlan& plan = ix->plan;
   // Adaptive choice ("sorted_beam" = 2): both kernels give the same answers; which one is faster depends on how often
   // equal keys force the merged-beam kernel to search a query twice (rarely on float data, often on integer-valued
   // data with wide beams) -- so it is measured: launches of at least 2048 queries are timed by the events that bracket
   // them anyway, harvested when a later call finds them complete, first one kernel, then the other, then the faster.
   // A filtered launch always runs the two-heap kernel's filtered form: no merged beam, no samples for the adaptive choice
   // (the tuner's measurements are left alone), no hand-over, tie log or shadows.
-  if (filter && !plan.fkern) {
-    plan.fkern = pick_filtered_kernel(ix->dtype, ix->metric, plan.cfg, plan.full);
-    HIP_TRY(raise_lds_limit((const void*)plan.fkern, ix->device, plan.lds));
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern, WAVE, plan.lds) != hipSuccess) n = 0;
-    plan.fbpc = std::max(1, std::min(plan.bpc, n));
-  }
-  bool sorted = plan.mode != MODE_HEAPS && !filter;
-  bool sample = false;
-  int variant = sorted ? 1 : 0;
+  KernelChoice c;
+  c.sorted = plan.mode != MODE_HEAPS && !filtered;
+  c.variant = c.sorted ? 1 : 0;
   // The merged-beam kernel's stragglers: a query that is searched twice finishes a whole exact-search latency late, and
   // in the last round of a launch that lengthens the launch itself (one such query costs as much as hundreds).  With
   // "sorted_tail_exact_pct" = p the last p % of one round of queries skip the sorted pass (the exact search is slower but
   // never needs a second one): -15 % on the integer-valued SIFT stand-in at ef=52, +0-4 % on float data without ties --
   // so by default (-1) it is one more variant that the adaptive choice measures.
   const uint64_t round_slots = (uint64_t)plan.sbpc * (uint64_t)ix->num_cus;
-  const bool multi_round = sorted && nq > round_slots;
-  int64_t tail_pct = ix->sorted_tail_exact_pct < 0 ? 0 : ix->sorted_tail_exact_pct;
-  bool exploratory = false;
+  c.multi_round = c.sorted && nq > round_slots;
+  c.tail_pct = ix->sorted_tail_exact_pct < 0 ? 0 : ix->sorted_tail_exact_pct;
+  const bool multi_round = c.multi_round;
   const int pinned = force_variant >= 0 ? force_variant : (int)ix->sorted_variant;  // fnv_tune / "sorted_variant"
   const bool shadows_on = ix->shadow_exact != 0;
   const bool try_tail = ix->sorted_tail_exact_pct < 0;
-  if (sorted && pinned >= 0) {
-    variant = variant_allowed(pinned, multi_round, true, shadows_on, true) ? pinned : 1;
-    sorted = variant != 0;
-    if (variant >= 2) tail_pct = kTailPct[variant];
-  } else if (sorted && ix->sorted_beam == 2 && ix->is_lane) {
+  if (c.sorted && pinned >= 0) {
+    c.variant = variant_allowed(pinned, multi_round, true, shadows_on, true) ? pinned : 1;
+    c.sorted = c.variant != 0;
+    if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
+  } else if (c.sorted && ix->sorted_beam == 2 && ix->is_lane) {
     // a hidden lane runs what its owner has measured (copied by sync_lane) and never explores or samples: a production
     // caller that happens to land on a lane must not pay for 3 x variants exploratory launches per lane
     if (nq >= 2048) {
-      if (auto it = ix->tuner.find(2 * B + (multi_round ? 1 : 0)); it != ix->tuner.end()) {
+      if (auto it = ix->tuner.find(tuner_key(B, multi_round)); it != ix->tuner.end()) {
         const fnv_index_s::Tuner& t = it->second;
         int best = -1;
         for (int v = 0; v < kNumVariants; v++)
           if (variant_allowed(v, multi_round, try_tail, shadows_on) && t.samples[v] > 0 && (best < 0 || t.best[v] < t.best[best])) best = v;
-        if (best >= 0) variant = best;
+        if (best >= 0) c.variant = best;
       }
-      sorted = variant != 0;
-      if (variant >= 2) tail_pct = kTailPct[variant];
+      c.sorted = c.variant != 0;
+      if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
     }
-  } else if (sorted && ix->sorted_beam == 2) {
+  } else if (c.sorted && ix->sorted_beam == 2) {
     if (ix->sample_kernel >= 0 && ix->launched && hipEventQuery(ix->ev1) == hipSuccess) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) == hipSuccess && ms > 0.f) {
@@ -1282,95 +1313,136 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
       ix->sample_kernel = -1;
     }
     if (nq >= 2048) {
-      fnv_index_s::Tuner& t = ix->tuner[2 * B + (multi_round ? 1 : 0)];
+      fnv_index_s::Tuner& t = ix->tuner[tuner_key(B, multi_round)];
       // three samples each (the first launch of a kernel is a cold one; the best of the rest decides), then the fastest
       // (fnv_tune takes all the samples in one call, so that no caller's launch is an exploratory one)
-      variant = -1;
+      c.variant = -1;
       for (int v : {1, 0, 6, 4, 3, 2, 5})
-        if (variant_allowed(v, multi_round, try_tail, shadows_on) && variant < 0 && t.samples[v] < 3) variant = v;
-      exploratory = variant >= 0;
-      if (variant < 0) {
-        variant = 0;
+        if (variant_allowed(v, multi_round, try_tail, shadows_on) && c.variant < 0 && t.samples[v] < 3) c.variant = v;
+      c.exploratory = c.variant >= 0;
+      if (c.variant < 0) {
+        c.variant = 0;
         for (int v = 1; v < kNumVariants; v++)
           if (variant_allowed(v, multi_round, try_tail, shadows_on) && t.samples[v] > 0 &&
-              (t.best[v] < t.best[variant] || (v == 1 && t.best[1] <= t.best[0])))
-            variant = v;
+              (t.best[v] < t.best[c.variant] || (v == 1 && t.best[1] <= t.best[0])))
+            c.variant = v;
       }
-      sample = t.samples[variant] < 4;
-      sorted = variant != 0;
-      if (variant >= 2) tail_pct = kTailPct[variant];
+      c.sample = t.samples[c.variant] < 4;
+      c.sorted = c.variant != 0;
+      if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
     }
   }
-  const int bpc = sorted ? plan.sbpc : filter ? plan.fbpc : plan.bpc;
-  uint32_t lds_bytes = sorted ? plan.slds : plan.lds;
-  // Shadow mode (search_params.h): a launch that fills at most a quarter of the resident slots starts, next to the
-  // merged-beam search of every query, an exact search of the same query on another slot.  A query in which equal keys
-  // meet at a decision is then answered after ONE exact-search latency from the start of the launch instead of a
-  // merged-beam pass plus a re-run (batch of 64 at ef=100 on the integer-valued data: p50 0.80 -> 0.47 ms); the shadow of
-  // a query that needs none stops at its next hop.  Same bytes either way.
-  const bool shadow = sorted && ix->shadow_exact != 0 && 4 * nq <= (uint64_t)bpc * (uint64_t)ix->num_cus;
-  const uint32_t nslots = shadow ? (uint32_t)(2 * nq) : (uint32_t)std::min<uint64_t>(nq, (uint64_t)bpc * (uint64_t)ix->num_cus);
-  // Tail shadows (variant 6, search_params.h): one exact shadow per slot at most -- of the queries dispensed last
-  const uint32_t tail_shadows = (sorted && !shadow && variant == kVariantTailShadows) ? (uint32_t)std::min<uint64_t>(nq, nslots) : 0u;
-  const uint32_t max_slots = std::max<uint32_t>(nslots, (uint32_t)std::min<uint64_t>(nq, (uint64_t)std::max(plan.bpc, plan.sbpc) * (uint64_t)ix->num_cus));
+  return c;
+}
 
-  // ---- workspace (grown on demand; sized for whichever kernel keeps more slots resident) -------------------------
+// (c) The workspace, grown on demand and sized for whichever kernel keeps more slots resident.
+static int grow_workspace(fnv_index_s* ix, uint32_t max_slots, uint64_t nq, bool sorted, bool done_flags, bool filtered) {
+  const LaunchPlan& plan = ix->plan;
   int rc = FNV_OK;
   for (int attempt = 0; attempt < 2; attempt++) {
-    rc = grow((void**)&ix->d_bitmap, &ix->bitmap_bytes, (size_t)max_slots * plan.heaps.bitmap_words * 4, true);
-    if (!rc) rc = grow((void**)&ix->d_ovf, &ix->ovf_bytes, (size_t)max_slots * plan.heaps.ovf_cap * 4);
-    if (!rc) rc = grow((void**)&ix->d_spill, &ix->spill_bytes, (size_t)max_slots * plan.heaps.spill_entries * 8);
-    if (!rc && (shadow || tail_shadows)) rc = grow((void**)&ix->d_done, &ix->done_bytes, (size_t)nq * 4);
-    if (!rc && sorted) rc = grow((void**)&ix->d_tielog, &ix->tielog_bytes, (size_t)max_slots * plan.sorted.log_entries * 8);
-    if (!rc && filter) rc = grow((void**)&ix->d_nodebits, &ix->nodebits_bytes, (size_t)(ix->capacity + 31) / 32 * 4);
-    ix->ws_bytes = ix->bitmap_bytes + ix->ovf_bytes + ix->spill_bytes + ix->tielog_bytes;
+    rc = ix->ws.bitmap.grow((size_t)max_slots * plan.heaps.bitmap_words * 4, true);
+    if (!rc) rc = ix->ws.ovf.grow((size_t)max_slots * plan.heaps.ovf_cap * 4);
+    if (!rc) rc = ix->ws.spill.grow((size_t)max_slots * plan.heaps.spill_entries * 8);
+    if (!rc && done_flags) rc = ix->d_done.grow((size_t)nq * 4);
+    if (!rc && sorted) rc = ix->ws.tielog.grow((size_t)max_slots * plan.sorted.log_entries * 8);
+    if (!rc && filtered) rc = ix->d_nodebits.grow((size_t)(ix->capacity + 31) / 32 * 4);
+    ix->ws_bytes = ix->ws.bytes();
     // out of memory on the handle itself: the hidden lanes' idle workspaces go first, then once more (from inside fnv_tune /
     // fnv_index_insert_batch, which hold the lanes, with the locks already held: t_holds_lanes_of)
     if (rc != FNV_ERR_NO_DEVICE || attempt || ix->is_lane || ix->parent) break;
     (void)hipGetLastError();
     if (release_idle_lanes(ix, nullptr) == 0) break;
   }
+  return rc;
+}
+
+// (d) Small launches on small indexes (round 5): when a bitmap of ALL node ids fits the LDS of the slots the launch needs, the
+// visited set is that bitmap (csrc/visited.hpp visited_insert_direct: one LDS round trip per link row, nothing overflows)
+// instead of the tag table, and the launch runs the kernel's DIRECT instantiation -- a launch that leaves the GPU mostly idle
+// is a chain of dependent latencies, and the tag table is 1.8 k of a lone hop's 7.9 k cycles.  The table is the last but
+// two of the slot's LDS areas: only what follows it moves.
+// Only in launches that fill at most a quarter of the slots, and not when the caller has pinned the table's shape
+// ("visited_slots", "visited_tag_bits", "visited_wide"); "visited_direct" = 0 turns it off.
+static bool lay_out_direct(const fnv_index_s* ix, SearchParams& p, uint32_t* lds_bytes, int bpc, uint32_t nslots) {
+  if (ix->visited_direct == 0 || ix->visited_slots != 0 || ix->visited_tag_bits != 0 || ix->visited_wide != 0 || !p.vis_tag16) return false;
+  const uint64_t ids = std::max<uint64_t>(ix->capacity, ix->parent ? ix->parent->capacity : 0);
+  const uint64_t bytes = ((ids + 7) / 8 + 15) / 16 * 16;
+  auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+  if (bytes + p.off_vis + 1024 <= kLdsPerCu) {
+    SearchParams d = p;
+    d.vis_w = 1;
+    d.vis_bytes = (uint32_t)bytes;
+    d.vis_slots = (uint32_t)(bytes * 8);  // (what fnv_last_launch_geometry reports: one slot per node id)
+    uint32_t off = align16(d.off_vis + d.vis_bytes);
+    d.off_stage_ids = off;
+    off = align16(off + (WAVE + 1) * 4);
+    d.off_ovf = off;
+    off = align16(off + (OVF_LIST + 2 + STASH) * 4);
+    const uint64_t per_cu = std::min<uint64_t>((uint64_t)bpc, kLdsPerCu / lds_allocated(off));
+    if (off <= kLdsPerCu && (uint64_t)nslots <= per_cu * (uint64_t)ix->num_cus) {
+      p = d;
+      *lds_bytes = off;
+      return true;
+    }
+  }
+  return false;
+}
+
+static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                              const SearchOutputs& out, void* hip_stream, const SearchOptions& opt) {
+  if (!ix) return fail(FNV_ERR_INVALID, "index is null");
+  // Index.h:847-849
+  if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
+  if (K <= 0 || ef_search <= 0) return fail(FNV_ERR_INVALID, "K and ef_search must be positive");
+  if (nq == 0) return FNV_OK;
+  if (!d_queries || !out.dist || !out.labels) return fail(FNV_ERR_INVALID, "null buffer");
+  if (nq > 0x7FFFFFFFull) return fail(FNV_ERR_INVALID, "too many queries in one batch");
+  std::lock_guard<std::mutex> lock(ix->mu);
+  ON_DEVICE(ix->device);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const SearchFilter* filter = opt.filter;
+
+  const int B = std::max(ef_search, K);  // Index.h:392
+  int rc = ensure_plan(ix, B, K);
+  if (rc) return rc;
+  LaunchPlan& plan = ix->plan;
+  if (filter && !plan.fkern) {
+    plan.fkern = pick_filtered_kernel(ix->dtype, ix->metric, plan.cfg, plan.full);
+    HIP_TRY(raise_lds_limit((const void*)plan.fkern, ix->device, plan.lds));
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern, WAVE, plan.lds) != hipSuccess) n = 0;
+    plan.fbpc = std::max(1, std::min(plan.bpc, n));
+  }
+  const KernelChoice c = choose_kernel(ix, B, nq, opt.force_variant, filter != nullptr);
+  const bool sorted = c.sorted;
+  const int bpc = sorted ? plan.sbpc : opt.filter ? plan.fbpc : plan.bpc;
+  uint32_t lds_bytes = sorted ? plan.slds : plan.lds;
+  // Shadow mode (search_params.h): a launch that fills at most a quarter of the resident slots starts, next to the
+  // merged-beam search of every query, an exact search of the same query on another slot.  A query in which equal keys
+  // meet at a decision is then answered after ONE exact-search latency from the start of the launch instead of a
+  // merged-beam pass plus a re-run (batch of 64 at ef=100 on the integer-valued data: p50 0.80 -> 0.47 ms); the shadow of
+  // a query that needs none stops at its next hop.  Same bytes either way.
+  const bool small_launch = 4 * nq <= (uint64_t)bpc * (uint64_t)ix->num_cus;
+  const bool shadow = sorted && ix->shadow_exact != 0 && small_launch;
+  const uint32_t nslots = shadow ? (uint32_t)(2 * nq) : (uint32_t)std::min<uint64_t>(nq, (uint64_t)bpc * (uint64_t)ix->num_cus);
+  // Tail shadows (variant 6, search_params.h): one exact shadow per slot at most -- of the queries dispensed last
+  const uint32_t tail_shadows = (sorted && !shadow && c.variant == kVariantTailShadows) ? (uint32_t)std::min<uint64_t>(nq, nslots) : 0u;
+  const uint32_t max_slots = std::max<uint32_t>(nslots, (uint32_t)std::min<uint64_t>(nq, (uint64_t)std::max(plan.bpc, plan.sbpc) * (uint64_t)ix->num_cus));
+
+  rc = grow_workspace(ix, max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr);
   if (rc) return rc;
 
   SearchParams p = sorted ? plan.sorted : plan.heaps;
-  // Small launches on small indexes (round 5): when a bitmap of ALL node ids fits the LDS of the slots the launch needs, the
-  // visited set is that bitmap (csrc/visited.hpp visited_insert_direct: one LDS round trip per link row, nothing overflows)
-  // instead of the tag table, and the launch runs the kernel's DIRECT instantiation -- a launch that leaves the GPU mostly idle
-  // is a chain of dependent latencies, and the tag table is 1.8 k of a lone hop's 7.9 k cycles.  The table is the last but
-  // two of the slot's LDS areas: only what follows it moves.
-  // Only in launches that fill at most a quarter of the slots, and not when the caller has pinned the table's shape
-  // ("visited_slots", "visited_tag_bits", "visited_wide"); "visited_direct" = 0 turns it off.
-  const bool small_launch = 4 * nq <= (uint64_t)bpc * (uint64_t)ix->num_cus;  // (the condition of shadow mode)
-  bool direct = false;
-  if (sorted && small_launch && ix->visited_direct != 0 && ix->visited_slots == 0 && ix->visited_tag_bits == 0 && ix->visited_wide == 0 && p.vis_tag16) {
-    const uint64_t ids = std::max<uint64_t>(ix->capacity, ix->parent ? ix->parent->capacity : 0);
-    const uint64_t bytes = ((ids + 7) / 8 + 15) / 16 * 16;
-    auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
-    if (bytes + p.off_vis + 1024 <= kLdsPerCu) {
-      SearchParams d = p;
-      d.vis_w = 1;
-      d.vis_bytes = (uint32_t)bytes;
-      d.vis_slots = (uint32_t)(bytes * 8);  // (what fnv_last_launch_geometry reports: one slot per node id)
-      uint32_t off = align16(d.off_vis + d.vis_bytes);
-      d.off_stage_ids = off;
-      off = align16(off + (WAVE + 1) * 4);
-      d.off_ovf = off;
-      off = align16(off + (OVF_LIST + 2 + STASH) * 4);
-      const uint64_t per_cu = std::min<uint64_t>((uint64_t)bpc, kLdsPerCu / lds_allocated(off));
-      if (off <= kLdsPerCu && (uint64_t)nslots <= per_cu * (uint64_t)ix->num_cus) {
-        p = d;
-        lds_bytes = off;
-        direct = true;
-      }
-    }
-  }
-  p.labels = node_ids ? nullptr : ix->d_labels;
+  const bool direct = sorted && small_launch && lay_out_direct(ix, p, &lds_bytes, bpc, nslots);
+
+  // (e) the per-call fields, and the launch
+  p.labels = (opt.node_ids || ix->output_node_ids != 0) ? nullptr : ix->d_labels;  // ("output_node_ids": read under the handle's mutex)
   p.queries = (const uint8_t*)d_queries;
-  p.out_dist = d_out_dist;
-  p.out_labels = d_out_labels;
-  p.out_count = d_out_count;
-  p.out_ndist = d_out_ndist;
-  p.out_nhops = d_out_nhops;
+  p.out_dist = out.dist;
+  p.out_labels = out.labels;
+  p.out_count = out.count;
+  p.out_ndist = out.ndist;
+  p.out_nhops = out.nhops;
   const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
   p.n_nodes = live;
   p.nq = (uint32_t)nq;
@@ -1379,33 +1451,33 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   if (step == 0) step = 1;
   p.scan_step = (uint32_t)step;
   p.n_scan = (uint32_t)((live + step - 1) / step);
-  p.ovf_bitmap = ix->d_bitmap;
-  p.ovf_glist = ix->d_ovf;
-  p.cand_spill = ix->d_spill;
-  p.tie_log = ix->d_tielog;
+  p.ovf_bitmap = ix->ws.bitmap.as<uint32_t>();
+  p.ovf_glist = ix->ws.ovf.as<uint32_t>();
+  p.cand_spill = ix->ws.spill.as<unsigned long long>();
+  p.tie_log = ix->ws.tielog.as<unsigned long long>();
   if (!sorted) p.log_entries = 0u;
   p.dispenser = ix->d_dispenser;
   p.status = (int32_t*)(ix->d_dispenser + 1);
-  p.host_status = host_status;
+  p.host_status = opt.host_status;
   p.redo_count = ix->d_dispenser + 3;  // [3] queries searched exactly after a tie, [4..7] by reason
   p.phase_cycles = ix->d_phase;
-  p.tail_exact = multi_round && sorted ? (uint32_t)std::min<uint64_t>((uint64_t)tail_pct * nslots / 100, nq) : 0u;
+  p.tail_exact = c.multi_round && sorted ? (uint32_t)std::min<uint64_t>((uint64_t)c.tail_pct * nslots / 100, nq) : 0u;
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));
   if (filter) {  // the label bitmap -> this handle's node bitmap (labels as they are now: after reorder(), device builds ...)
     const uint64_t words = (ix->capacity + 31) / 32;
     hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
-                       live, words, filter->bits, filter->n_bits, ix->d_nodebits);
+                       live, words, filter->bits, filter->n_bits, ix->d_nodebits.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    p.node_bits = ix->d_nodebits;
+    p.node_bits = ix->d_nodebits.as<uint32_t>();
   }
   HIP_TRY(hipEventRecord(ix->ev0, stream));
   if (ix->entry_kernel && !ix->tail_bytes) {  // (split rows: K0's LDS tiles hold one table's rows; the in-kernel scan serves them)
     // K0: one pass over the shared entry-scan nodes for the whole batch (LDS-staged), same stream
-    rc = grow((void**)&ix->d_entry, &ix->entry_bytes, (size_t)nq * 8);
+    rc = ix->d_entry.grow((size_t)nq * 8);
     if (rc) return rc;
-    p.entry_node_out = (uint32_t*)ix->d_entry;
-    p.entry_dist_out = (float*)((uint8_t*)ix->d_entry + (size_t)nq * 4);
+    p.entry_node_out = ix->d_entry.as<uint32_t>();
+    p.entry_dist_out = (float*)(ix->d_entry.as<uint8_t>() + (size_t)nq * 4);
     p.scan_tile_stride = p.row_bytes + 16;
     const uint32_t fixed = SCAN_WAVES * p.q_chunks * 16 + SCAN_QPB * 8;
     p.scan_tile_rows = std::max<uint32_t>(1, std::min<uint32_t>(p.n_scan, (64u * 1024u) / p.scan_tile_stride));
@@ -1418,16 +1490,16 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     p.entry_dist = p.entry_dist_out;
   }
   if (tail_shadows) {  // the queries, then exact shadows of the last `tail_shadows` of them (pulled by slots that would go idle)
-    HIP_TRY(hipMemsetAsync(ix->d_done, 0, (size_t)nq * 4, stream));
+    HIP_TRY(hipMemsetAsync(ix->d_done.ptr, 0, (size_t)nq * 4, stream));
     p.shadow_base = (uint32_t)nq;
-    p.done_flags = ix->d_done;
+    p.done_flags = ix->d_done.as<uint32_t>();
     p.nq = (uint32_t)(nq + tail_shadows);
     p.tail_exact = 0u;
   }
   if (shadow) {  // from here on the launch has 2 nq work items: the queries, then their exact shadows
-    HIP_TRY(hipMemsetAsync(ix->d_done, 0, (size_t)nq * 4, stream));
+    HIP_TRY(hipMemsetAsync(ix->d_done.ptr, 0, (size_t)nq * 4, stream));
     p.shadow_base = (uint32_t)nq;
-    p.done_flags = ix->d_done;
+    p.done_flags = ix->d_done.as<uint32_t>();
     p.nq = (uint32_t)(2 * nq);
     p.tail_exact = 0u;
   }
@@ -1436,12 +1508,13 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   hipLaunchKernelGGL(kern, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ix->ev1, stream));
-  ix->sample_kernel = sample ? variant : -1;
-  ix->sample_B = 2 * B + (multi_round ? 1 : 0);
+  // (f) what the launch was: for the adaptive choice's next harvest, and for the fnv_last_* calls
+  ix->sample_kernel = c.sample ? c.variant : -1;
+  ix->sample_B = tuner_key(B, c.multi_round);
   ix->sample_nq = nq;
-  ix->last_variant = sorted ? std::max(variant, 1) : 0;
-  ix->last_exploratory = exploratory;
-  if (exploratory) ix->explored_launches++;
+  ix->last_variant = sorted ? std::max(c.variant, 1) : 0;
+  ix->last_exploratory = c.exploratory;
+  if (c.exploratory) ix->explored_launches++;
   ix->last_shadow = shadow;
   ix->last_stream = stream;
   ix->launched = true;
@@ -1462,11 +1535,7 @@ int fnv_search_status(fnv_index_t ix) {
   if (!ix->launched) return FNV_OK;
   ON_DEVICE(ix->device);
   HIP_TRY(hipStreamSynchronize(ix->last_stream));
-  int32_t st = 0;
-  HIP_TRY(hipMemcpy(&st, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (st == ST_CAND_OVERFLOW)
-    return fail(FNV_ERR_CAPACITY, "candidate heap overflowed its HBM spill area; raise the spill_entries option");
-  return FNV_OK;
+  return check_device_status(ix);
 }
 
 static uint64_t now_ns() {
@@ -1478,33 +1547,27 @@ static uint64_t now_ns() {
 // ix->host_mu) and finish (wait, report a capacity error).
 // `host_filter` (filtered search): the label bitmap in host memory; it is staged into this handle's HBM first.
 static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search,
-                               int num_initializations, float* out_dist, int32_t* out_labels, int32_t* out_count,
-                               uint64_t* out_ndist, uint64_t* out_nhops, const SearchFilter* host_filter = nullptr) {
+                               int num_initializations, const SearchOutputs& user, const SearchFilter* host_filter = nullptr) {
   ON_DEVICE(ix->device);
   SearchFilter dev_filter{nullptr, 0};
-  const SearchFilter* filter = nullptr;
+  SearchOptions opt;
   if (host_filter) {
     const size_t fbytes = (size_t)((host_filter->n_bits + 7) / 8);
     if (fbytes) {
       {
         std::lock_guard<std::mutex> lock(ix->mu);
-        int rc = grow((void**)&ix->d_allowed, &ix->allowed_bytes, fbytes);
+        int rc = ix->d_allowed.grow(fbytes);
         if (rc) return rc;
       }
-      HIP_TRY(hipMemcpyAsync(ix->d_allowed, host_filter->bits, fbytes, hipMemcpyHostToDevice, ix->stream));
-      dev_filter.bits = ix->d_allowed;
+      HIP_TRY(hipMemcpyAsync(ix->d_allowed.ptr, host_filter->bits, fbytes, hipMemcpyHostToDevice, ix->stream));
+      dev_filter.bits = ix->d_allowed.as<uint8_t>();
     }
     dev_filter.n_bits = host_filter->n_bits;
-    filter = &dev_filter;
+    opt.filter = &dev_filter;
   }
   const size_t qbytes = (size_t)nq * ix->dim * dtype_size(ix->dtype);
-  // one output slab: dist | labels | count | ndist | nhops
-  const size_t o_dist = 0;
-  const size_t o_lab = o_dist + (size_t)nq * K * 4;
-  const size_t o_cnt = o_lab + (size_t)nq * K * 4;
-  const size_t o_nd = (o_cnt + (size_t)nq * 4 + 7) & ~(size_t)7;
-  const size_t o_nh = o_nd + (size_t)nq * 8;
-  const size_t obytes = o_nh + (size_t)nq * 8;
+  size_t obytes = 0;
+  (void)lay_out_slab(nullptr, nq, K, &obytes);  // one output slab, on the device and in pinned memory
   // Small batches (a single query above all) go through one pinned host buffer: one H2D copy, one D2H copy of the
   // whole slab plus the status word, no pageable-memory copies (each of those synchronises) -- the host side of a
   // one-query search drops from ~10 driver round trips to 4 asynchronous calls and one wait.
@@ -1512,32 +1575,23 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   const bool pinned = soff + 64 <= (1u << 20);
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    int rc = grow(&ix->d_q, &ix->d_q_bytes, qbytes);
-    if (!rc) rc = grow(&ix->d_out, &ix->d_out_bytes, obytes);
+    int rc = ix->d_q.grow(qbytes);
+    if (!rc) rc = ix->d_out.grow(obytes);
     if (rc) return rc;
     if (pinned && !ix->h_pin) HIP_TRY(hipHostMalloc(&ix->h_pin, 1u << 20, hipHostMallocDefault));
     // larger batches (round 4): the queries still go in as one pageable copy, but the five result arrays come back as ONE
     // slab into pinned memory (grown on demand, up to 256 MB of results) and are scattered by the CPU -- five pageable
     // device-to-host copies each synchronise with the runtime's staging
     const size_t res_need = ((obytes + 63) & ~(size_t)63) + 64;
-    if (!pinned && res_need <= (256u << 20) && res_need > ix->h_res_bytes) {
-      // best effort: pinned memory is commonly capped (ulimit -l, containers) -- without the slab the five pageable
-      // copies below still work
-      void* old = ix->h_res;
-      ix->h_res = nullptr;
-      ix->h_res_bytes = 0;
-      if (old) (void)hipHostFree(old);
-      void* slab = nullptr;
-      if (hipHostMalloc(&slab, res_need + res_need / 4, hipHostMallocDefault) == hipSuccess && slab) {
-        ix->h_res = slab;
-        ix->h_res_bytes = res_need + res_need / 4;
-      } else {
-        (void)hipGetLastError();
-      }
+    // best effort: pinned memory is commonly capped (ulimit -l, containers) -- without the slab the five pageable
+    // copies below still work
+    if (!pinned && res_need <= (256u << 20) && ix->h_res.grow(res_need, false, res_need / 4) != FNV_OK) {
+      ix->h_res.release();
+      (void)hipGetLastError();
     }
   }
-  const bool pinned_results = !pinned && ix->h_res && ((obytes + 63) & ~(size_t)63) + 64 <= ix->h_res_bytes;
-  uint8_t* o = (uint8_t*)ix->d_out;
+  const bool pinned_results = !pinned && ix->h_res.ptr && ((obytes + 63) & ~(size_t)63) + 64 <= ix->h_res.bytes;
+  const SearchOutputs dev_slab = lay_out_slab(ix->d_out.ptr, nq, K);
   ix->pin = PinnedCall();
   // A caller whose arrays are ALREADY pinned (hipHostMalloc / hipHostRegister / torch pin_memory) needs no staging at any batch
   // size (round 6): the kernel reads the queries from and writes the results into the caller's own memory -- each query
@@ -1554,14 +1608,14 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
       return a.devicePointer;
     };
     void* dq = device_view(queries);
-    void* dd = dq ? device_view(out_dist) : nullptr;
-    void* dl = dd ? device_view(out_labels) : nullptr;
-    void* dc = out_count ? device_view(out_count) : nullptr;
-    void* dn = out_ndist ? device_view(out_ndist) : nullptr;
-    void* dh = out_nhops ? device_view(out_nhops) : nullptr;
-    if (dq && dd && dl && (!out_count || dc) && (!out_ndist || dn) && (!out_nhops || dh)) {
-      int rc0 = search_device_impl(ix, dq, nq, K, ef_search, num_initializations, (float*)dd, (int32_t*)dl, (int32_t*)dc, (uint64_t*)dn,
-                                   (uint64_t*)dh, ix->stream, false, -1, /*ids_by_option=*/true, nullptr, filter);
+    void* dd = dq ? device_view(user.dist) : nullptr;
+    void* dl = dd ? device_view(user.labels) : nullptr;
+    void* dc = user.count ? device_view(user.count) : nullptr;
+    void* dn = user.ndist ? device_view(user.ndist) : nullptr;
+    void* dh = user.nhops ? device_view(user.nhops) : nullptr;
+    if (dq && dd && dl && (!user.count || dc) && (!user.ndist || dn) && (!user.nhops || dh)) {
+      int rc0 = search_device_impl(ix, dq, nq, K, ef_search, num_initializations,
+                                   SearchOutputs{(float*)dd, (int32_t*)dl, (int32_t*)dc, (uint64_t*)dn, (uint64_t*)dh}, ix->stream, opt);
       if (rc0) return rc0;
       ix->t_enqueue_ns = now_ns();
       return FNV_OK;  // (search_host_finish: wait + the launch's status word)
@@ -1573,72 +1627,40 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   // once (when it is staged), its K results are posted writes.  Measured on 1M x 128 (profiles/r6_host_zero_copy.txt): kernel
   // time +0-3 %, wall time of a call -13 ... -40 us at every batch size from 1 to 1024 queries (one query: 0.157 -> 0.143 ms
   // at ef=50; 64: 0.24-0.26 -> 0.215 ms; 1024: 0.446 -> 0.405 ms).
+  uint8_t* h = (uint8_t*)ix->h_pin;  // (small batches)
   if (pinned && nq <= (uint64_t)ix->host_zero_copy) {
-    uint8_t* h = (uint8_t*)ix->h_pin;
     memcpy(h + qoff, queries, qbytes);
     *(int32_t*)(h + soff) = ST_OK;
-    uint8_t* ho = h + ooff;
-    int rc0 = search_device_impl(ix, h + qoff, nq, K, ef_search, num_initializations, (float*)(ho + o_dist), (int32_t*)(ho + o_lab),
-                                 (int32_t*)(ho + o_cnt), (uint64_t*)(ho + o_nd), (uint64_t*)(ho + o_nh), ix->stream, false, -1,
-                                 /*ids_by_option=*/true, (int32_t*)(h + soff), filter);
+    const SearchOutputs pin_slab = lay_out_slab(h + ooff, nq, K);
+    opt.host_status = (int32_t*)(h + soff);
+    int rc0 = search_device_impl(ix, h + qoff, nq, K, ef_search, num_initializations, pin_slab, ix->stream, opt);
     if (rc0) return rc0;
     ix->t_enqueue_ns = now_ns();
-    PinnedCall& c = ix->pin;
-    c.active = true;
-    c.slab = ho;
-    c.status = (const int32_t*)(h + soff);
-    c.nq = nq;
-    c.K = K;
-    c.o_lab = o_lab; c.o_cnt = o_cnt; c.o_nd = o_nd; c.o_nh = o_nh;
-    c.out_dist = out_dist; c.out_labels = out_labels; c.out_count = out_count; c.out_ndist = out_ndist; c.out_nhops = out_nhops;
+    ix->pin.arm(pin_slab, opt.host_status, user, nq, K);
     return FNV_OK;
   }
   if (pinned) {
-    uint8_t* h = (uint8_t*)ix->h_pin;
     memcpy(h + qoff, queries, qbytes);
-    HIP_TRY(hipMemcpyAsync(ix->d_q, h + qoff, qbytes, hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ix->d_q.ptr, h + qoff, qbytes, hipMemcpyHostToDevice, ix->stream));
   } else {
-    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, qbytes, hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipMemcpyAsync(ix->d_q.ptr, queries, qbytes, hipMemcpyHostToDevice, ix->stream));
   }
-  int rc = search_device_impl(ix, ix->d_q, nq, K, ef_search, num_initializations, (float*)(o + o_dist), (int32_t*)(o + o_lab),
-                              (int32_t*)(o + o_cnt), (uint64_t*)(o + o_nd), (uint64_t*)(o + o_nh), ix->stream, false, -1,
-                              /*ids_by_option=*/true, nullptr, filter);
+  int rc = search_device_impl(ix, ix->d_q.ptr, nq, K, ef_search, num_initializations, dev_slab, ix->stream, opt);
   if (rc) return rc;
   ix->t_enqueue_ns = now_ns();
-  if (pinned) {
-    uint8_t* h = (uint8_t*)ix->h_pin;
-    HIP_TRY(hipMemcpyAsync(h + ooff, o, obytes, hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipMemcpyAsync(h + soff, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
-    PinnedCall& c = ix->pin;
-    c.active = true;
-    c.slab = h + ooff;
-    c.status = (const int32_t*)(h + soff);
-    c.nq = nq;
-    c.K = K;
-    c.o_lab = o_lab; c.o_cnt = o_cnt; c.o_nd = o_nd; c.o_nh = o_nh;
-    c.out_dist = out_dist; c.out_labels = out_labels; c.out_count = out_count; c.out_ndist = out_ndist; c.out_nhops = out_nhops;
+  if (pinned || pinned_results) {  // the whole slab and the status word into pinned memory; search_host_finish scatters them
+    uint8_t* slab = pinned ? h + ooff : ix->h_res.as<uint8_t>();
+    int32_t* status = (int32_t*)(pinned ? h + soff : slab + ((obytes + 63) & ~(size_t)63));
+    HIP_TRY(hipMemcpyAsync(slab, ix->d_out.ptr, obytes, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(status, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+    ix->pin.arm(lay_out_slab(slab, nq, K), status, user, nq, K);
     return FNV_OK;
   }
-  if (pinned_results) {
-    uint8_t* h = (uint8_t*)ix->h_res;
-    const size_t soff2 = (obytes + 63) & ~(size_t)63;
-    HIP_TRY(hipMemcpyAsync(h, o, obytes, hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipMemcpyAsync(h + soff2, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
-    PinnedCall& c = ix->pin;
-    c.active = true;
-    c.slab = h;
-    c.status = (const int32_t*)(h + soff2);
-    c.nq = nq;
-    c.K = K;
-    c.o_lab = o_lab; c.o_cnt = o_cnt; c.o_nd = o_nd; c.o_nh = o_nh;
-    c.out_dist = out_dist; c.out_labels = out_labels; c.out_count = out_count; c.out_ndist = out_ndist; c.out_nhops = out_nhops;
-    return FNV_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(out_dist, o + o_dist, (size_t)nq * K * 4, hipMemcpyDeviceToHost, ix->stream));
-  HIP_TRY(hipMemcpyAsync(out_labels, o + o_lab, (size_t)nq * K * 4, hipMemcpyDeviceToHost, ix->stream));
-  if (out_count) HIP_TRY(hipMemcpyAsync(out_count, o + o_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->stream));
-  if (out_ndist) HIP_TRY(hipMemcpyAsync(out_ndist, o + o_nd, (size_t)nq * 8, hipMemcpyDeviceToHost, ix->stream));
-  if (out_nhops) HIP_TRY(hipMemcpyAsync(out_nhops, o + o_nh, (size_t)nq * 8, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(user.dist, dev_slab.dist, (size_t)nq * K * 4, hipMemcpyDeviceToHost, ix->stream));
+  HIP_TRY(hipMemcpyAsync(user.labels, dev_slab.labels, (size_t)nq * K * 4, hipMemcpyDeviceToHost, ix->stream));
+  if (user.count) HIP_TRY(hipMemcpyAsync(user.count, dev_slab.count, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->stream));
+  if (user.ndist) HIP_TRY(hipMemcpyAsync(user.ndist, dev_slab.ndist, (size_t)nq * 8, hipMemcpyDeviceToHost, ix->stream));
+  if (user.nhops) HIP_TRY(hipMemcpyAsync(user.nhops, dev_slab.nhops, (size_t)nq * 8, hipMemcpyDeviceToHost, ix->stream));
   return FNV_OK;
 }
 
@@ -1650,14 +1672,12 @@ static int search_host_finish(fnv_index_t ix) {
   if (!c.active) return fnv_search_status(ix);
   c.active = false;
   const size_t nk = (size_t)c.nq * c.K * 4;
-  memcpy(c.out_dist, c.slab, nk);
-  memcpy(c.out_labels, c.slab + c.o_lab, nk);
-  if (c.out_count) memcpy(c.out_count, c.slab + c.o_cnt, (size_t)c.nq * 4);
-  if (c.out_ndist) memcpy(c.out_ndist, c.slab + c.o_nd, (size_t)c.nq * 8);
-  if (c.out_nhops) memcpy(c.out_nhops, c.slab + c.o_nh, (size_t)c.nq * 8);
-  if (*c.status == ST_CAND_OVERFLOW)
-    return fail(FNV_ERR_CAPACITY, "candidate heap overflowed its HBM spill area; raise the spill_entries option");
-  return FNV_OK;
+  memcpy(c.user.dist, c.slab.dist, nk);
+  memcpy(c.user.labels, c.slab.labels, nk);
+  if (c.user.count) memcpy(c.user.count, c.slab.count, (size_t)c.nq * 4);
+  if (c.user.ndist) memcpy(c.user.ndist, c.slab.ndist, (size_t)c.nq * 8);
+  if (c.user.nhops) memcpy(c.user.nhops, c.slab.nhops, (size_t)c.nq * 8);
+  return check_status(*c.status);
 }
 
 static int check_search_args(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search,
@@ -1700,9 +1720,8 @@ static void sync_lane(fnv_index_t ix, fnv_index_s* lane) {
 // them from pinned host memory behind a gate word, results written straight back (every touch of host memory from a
 // running wave costs microseconds: 1.7-2.6 ms).  Neither is in the tree.
 static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
-                             float* out_dist, int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist,
-                             uint64_t* out_nhops, const SearchFilter* host_filter) {
-  int rc = check_search_args(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels);
+                             const SearchOutputs& out, const SearchFilter* host_filter) {
+  int rc = check_search_args(ix, queries, nq, K, ef_search, num_initializations, out.dist, out.labels);
   if (rc || nq == 0) return rc;
   // one caller at a time per lane (a lane's staging areas, stream and workspace are its caller's for the whole call); a
   // caller that finds the handle busy takes the second lane, a further ones take more lanes when their batches are small, else wait for the first
@@ -1751,8 +1770,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
   }
   if (!host_lock.owns_lock()) host_lock = std::unique_lock<std::mutex>(ix->host_mu);
   if (lane != ix) sync_lane(ix, lane);
-  rc = search_host_enqueue(lane, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count,
-                           out_ndist, out_nhops, host_filter);
+  rc = search_host_enqueue(lane, queries, nq, K, ef_search, num_initializations, out, host_filter);
   if (rc == FNV_ERR_NO_DEVICE && lane != ix) {
     // a lane could not get its workspace (another copy of the per-slot bitmaps and spill areas: 19 GB at 50M nodes): the
     // call waits for the handle's own lane instead, like any caller did before there were lanes
@@ -1760,8 +1778,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
     host_lock.unlock();  // (never hold a lane while waiting for the handle: fnv_tune takes them in the other order)
     host_lock = std::unique_lock<std::mutex>(ix->host_mu);
     lane = ix;
-    rc = search_host_enqueue(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count, out_ndist,
-                             out_nhops, host_filter);
+    rc = search_host_enqueue(ix, queries, nq, K, ef_search, num_initializations, out, host_filter);
   }
   if (rc) return rc;
   rc = search_host_finish(lane);
@@ -1782,8 +1799,8 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
 int fnv_search_batch(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
                      float* out_dist, int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist,
                      uint64_t* out_nhops) {
-  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count, out_ndist,
-                           out_nhops, nullptr);
+  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations,
+                           SearchOutputs{out_dist, out_labels, out_count, out_ndist, out_nhops}, nullptr);
 }
 
 // ---- filtered search: results restricted to the nodes whose label is set in a bitmap over label values -------------
@@ -1799,8 +1816,8 @@ int fnv_search_batch_filtered(fnv_index_t ix, const void* queries, uint64_t nq, 
   int rc = check_filter_args(allowed_bits, n_bits);
   if (rc) return rc;
   const SearchFilter f{(const uint8_t*)allowed_bits, n_bits};
-  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels, out_count, out_ndist,
-                           out_nhops, &f);
+  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations,
+                           SearchOutputs{out_dist, out_labels, out_count, out_ndist, out_nhops}, &f);
 }
 
 int fnv_search_batch_filtered_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
@@ -1811,8 +1828,10 @@ int fnv_search_batch_filtered_device(fnv_index_t ix, const void* d_queries, uint
   int rc = check_filter_args(d_allowed_bits, n_bits);
   if (rc) return rc;
   const SearchFilter f{n_bits ? (const uint8_t*)d_allowed_bits : nullptr, n_bits};
-  return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations, d_out_dist, d_out_labels, d_out_count,
-                            d_out_ndist, d_out_nhops, hip_stream, false, -1, /*ids_by_option=*/true, nullptr, &f);
+  SearchOptions opt;
+  opt.filter = &f;
+  return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations,
+                            SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, d_out_nhops}, hip_stream, opt);
 }
 
 // ---- several GPUs behind one call -----------------------------------------------------------------
@@ -1993,42 +2012,38 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
   if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
   if (K <= 0 || ef_search <= 0) return fail(FNV_ERR_INVALID, "K and ef_search must be positive");
   if (!queries || nq == 0) return fail(FNV_ERR_INVALID, "fnv_tune needs a batch of queries");
-  std::lock_guard<std::mutex> host_lock(ix->host_mu);
-  // (no host-buffer search on the hidden lanes meanwhile either: the existing ones are locked, and none is created -- a caller
-  //  that wants one waits on lane_mu, holding nothing)
-  std::lock_guard<std::mutex> no_new_lanes(ix->lane_mu);
-  std::vector<std::unique_lock<std::mutex>> lane_locks;
-  for (std::atomic<fnv_index_s*>& slot : ix->lanes)
-    if (fnv_index_s* l = slot.load()) lane_locks.emplace_back(l->host_mu);
-  HoldsLanes holds_lanes(ix);
+  HoldAllLanes hold(ix);
   ON_DEVICE(ix->device);
   const size_t qbytes = (size_t)nq * ix->dim * dtype_size(ix->dtype);
   const size_t o_lab = (size_t)nq * K * 4, obytes = 2 * o_lab;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    int rc = grow(&ix->d_q, &ix->d_q_bytes, 2 * qbytes);
-    if (!rc) rc = grow(&ix->d_out, &ix->d_out_bytes, obytes);
+    int rc = ix->d_q.grow(2 * qbytes);
+    if (!rc) rc = ix->d_out.grow(obytes);
     if (rc) return rc;
   }
   // The batch twice in a row: a launch on rows [off, off + nq) searches the same queries in a rotated order.  Which
   // queries tie -- and so which ones are stragglers of the last round -- is a property of the queries: timing several
   // rotations and averaging measures a variant's EXPECTED time, not its luck with one order.
-  uint8_t* dq2 = (uint8_t*)ix->d_q;
+  uint8_t* dq2 = ix->d_q.as<uint8_t>();
   HIP_TRY(hipMemcpy(dq2, queries, qbytes, queries_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dq2 + qbytes, dq2, qbytes, hipMemcpyDeviceToDevice));
   const size_t qrow_bytes = (size_t)ix->dim * dtype_size(ix->dtype);
-  uint8_t* o = (uint8_t*)ix->d_out;
+  SearchOutputs scratch;  // distances | labels, nothing else
+  scratch.dist = ix->d_out.as<float>();
+  scratch.labels = (int32_t*)(ix->d_out.as<uint8_t>() + o_lab);
   auto launch = [&](int variant, uint64_t rotate = 0) -> int {
-    return search_device_impl(ix, dq2 + (rotate % nq) * qrow_bytes, nq, K, ef_search, num_initializations, (float*)o,
-                              (int32_t*)(o + o_lab), nullptr, nullptr, nullptr, ix->stream, false, variant, /*ids_by_option=*/true);
+    SearchOptions opt;
+    opt.force_variant = variant;
+    return search_device_impl(ix, dq2 + (rotate % nq) * qrow_bytes, nq, K, ef_search, num_initializations, scratch, ix->stream, opt);
   };
   // what kind of launch is this?  (one probing launch of the merged-beam kernel tells: plan, round size)
   const int B = std::max(ef_search, K);
   {
     std::lock_guard<std::mutex> lock(ix->mu);
     ix->layouts.erase(B);
-    ix->tuner.erase(2 * B);
-    ix->tuner.erase(2 * B + 1);
+    ix->tuner.erase(tuner_key(B, false));
+    ix->tuner.erase(tuner_key(B, true));
     ix->plan.valid = false;
     ix->tune_epoch++;  // (whatever follows -- including the early return below -- lanes drop their copy of the old choice)
   }
@@ -2208,15 +2223,11 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
   }
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    ix->tuner[2 * B + (multi_round ? 1 : 0)] = t;
+    ix->tuner[tuner_key(B, multi_round)] = t;
     ix->sample_kernel = -1;
     ix->tune_epoch++;
   }
-  int32_t st = 0;
-  HIP_TRY(hipMemcpy(&st, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (st == ST_CAND_OVERFLOW)
-    return fail(FNV_ERR_CAPACITY, "candidate heap overflowed its HBM spill area; raise the spill_entries option");
-  return FNV_OK;
+  return check_device_status(ix);
 }
 
 // Measurement aid: the rate (GB/s of row bytes) a pure gather of random rows of this index's vector table reaches with
@@ -2275,29 +2286,19 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
     return fail(FNV_ERR_RUNTIME, "Maximum number of nodes reached. (device index capacity)");
   if (evals_out) *evals_out = 0;
   if (count == 0) return FNV_OK;
-  std::lock_guard<std::mutex> host_lock(ix->host_mu);
-  // (no host-buffer search on the hidden lanes meanwhile either: the existing ones are locked, and none is created -- a caller
-  //  that wants one waits on lane_mu, holding nothing)
-  std::lock_guard<std::mutex> no_new_lanes(ix->lane_mu);
-  std::vector<std::unique_lock<std::mutex>> lane_locks;
-  for (std::atomic<fnv_index_s*>& slot : ix->lanes)
-    if (fnv_index_s* l = slot.load()) lane_locks.emplace_back(l->host_mu);
-  HoldsLanes holds_lanes(ix);
+  HoldAllLanes hold(ix);
   ON_DEVICE(ix->device);
   const int W = ef_construction;
   const uint32_t keep = std::max<uint32_t>(ix->M / 2, 1);  // Index.h:373
   const size_t esize = dtype_size(ix->dtype);
   const size_t qrow = (size_t)ix->dim * esize;
   const size_t qbytes = count * qrow;
-  const size_t o_dist = 0;
-  const size_t o_lab = o_dist + (size_t)count * W * 4;
-  const size_t o_cnt = o_lab + (size_t)count * W * 4;
-  const size_t o_nd = (o_cnt + (size_t)count * 4 + 7) & ~(size_t)7;
-  const size_t obytes = o_nd + (size_t)count * 8;
+  size_t obytes = 0;
+  (void)lay_out_slab(nullptr, count, W, &obytes);
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    int rcg = grow(&ix->d_q, &ix->d_q_bytes, qbytes);
-    if (!rcg) rcg = grow(&ix->d_out, &ix->d_out_bytes, obytes);
+    int rcg = ix->d_q.grow(qbytes);
+    if (!rcg) rcg = ix->d_out.grow(obytes);
     if (rcg) return rcg;
   }
   const size_t nreq = (size_t)count * keep;
@@ -2307,30 +2308,32 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
   const size_t req_bytes = (nreq * 4 + 255) & ~(size_t)255;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    int rcg = grow(&ix->d_wirebuf, &ix->wirebuf_bytes, 4 * req_bytes + sort_bytes + 256);
+    int rcg = ix->d_wirebuf.grow(4 * req_bytes + sort_bytes + 256);
     if (rcg) return rcg;
   }
-  uint8_t* o = (uint8_t*)ix->d_out;
+  SearchOutputs beams = lay_out_slab(ix->d_out.ptr, count, W);  // the beams: distances | node ids | counts | evaluations
+  beams.nhops = nullptr;
   // the new nodes' vectors are the queries (Index.h:371: beamSearch(data, entry, ef_construction)); dense rows
   if (!ix->tail_bytes) {
-    HIP_TRY(hipMemcpy2DAsync(ix->d_q, qrow, ix->d_vectors + first_node * (uint64_t)ix->row_bytes, ix->row_bytes, qrow,
+    HIP_TRY(hipMemcpy2DAsync(ix->d_q.ptr, qrow, ix->d_vectors + first_node * (uint64_t)ix->row_bytes, ix->row_bytes, qrow,
                              count, hipMemcpyDeviceToDevice, ix->stream));
   } else {  // split rows: the main table's part of every row, then what the side table holds of it
     const size_t main_part = std::min<size_t>(qrow, ix->row_bytes), tail_part = qrow - main_part;
-    HIP_TRY(hipMemcpy2DAsync(ix->d_q, qrow, ix->d_vectors + first_node * (uint64_t)ix->row_bytes, ix->row_bytes, main_part,
+    HIP_TRY(hipMemcpy2DAsync(ix->d_q.ptr, qrow, ix->d_vectors + first_node * (uint64_t)ix->row_bytes, ix->row_bytes, main_part,
                              count, hipMemcpyDeviceToDevice, ix->stream));
     if (tail_part)
-      HIP_TRY(hipMemcpy2DAsync((uint8_t*)ix->d_q + main_part, qrow, ix->tails() + first_node * (uint64_t)ix->tail_bytes,
+      HIP_TRY(hipMemcpy2DAsync(ix->d_q.as<uint8_t>() + main_part, qrow, ix->tails() + first_node * (uint64_t)ix->tail_bytes,
                                ix->tail_bytes, tail_part, count, hipMemcpyDeviceToDevice, ix->stream));
   }
-  int rc = search_device_impl(ix, ix->d_q, count, W, W, num_initializations, (float*)(o + o_dist), (int32_t*)(o + o_lab),
-                              (int32_t*)(o + o_cnt), (uint64_t*)(o + o_nd), nullptr, ix->stream, /*node_ids=*/true);
+  SearchOptions opt;
+  opt.node_ids = true;
+  int rc = search_device_impl(ix, ix->d_q.ptr, count, W, W, num_initializations, beams, ix->stream, opt);
   if (rc) return rc;
 
   std::lock_guard<std::mutex> lock(ix->mu);
   WireParams w;
   memset(&w, 0, sizeof(w));
-  uint8_t* wb = (uint8_t*)ix->d_wirebuf;
+  uint8_t* wb = ix->d_wirebuf.as<uint8_t>();
   uint32_t* req_target = (uint32_t*)wb;
   uint32_t* req_index = (uint32_t*)(wb + req_bytes);
   uint32_t* sorted_target = (uint32_t*)(wb + 2 * req_bytes);
@@ -2338,14 +2341,13 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
   void* sort_tmp = wb + 4 * req_bytes;
   w.vectors = ix->d_vectors;
   w.tails = ix->tails();
-  w.tail_chunks = ix->tail_bytes / 16;
   w.links = ix->d_links;
   w.req_target = req_target;
   w.sorted_target = sorted_target;
   w.sorted_req = sorted_req;
-  w.beam_dist = (const float*)(o + o_dist);
-  w.beam_ids = (const int32_t*)(o + o_lab);
-  w.beam_count = (const int32_t*)(o + o_cnt);
+  w.beam_dist = beams.dist;
+  w.beam_ids = beams.labels;
+  w.beam_count = beams.count;
   w.dispenser = ix->d_dispenser;
   w.first_node = (uint32_t)first_node;
   w.count = (uint32_t)count;
@@ -2353,12 +2355,10 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
   w.M = ix->M;
   w.keep = keep;
   w.row_bytes = ix->row_bytes;
-  w.nchunks = ix->row_bytes / 16;
-  const int cfg = pick_row_cfg(w.nchunks, w.tail_chunks);
-  const uint32_t per_iter = (uint32_t)(kCfgs[cfg].G * kCfgs[cfg].CU);
-  w.q_chunks = (w.nchunks + per_iter - 1) / per_iter * per_iter;
-  if (w.tail_chunks) w.q_chunks = w.nchunks + (uint32_t)kCfgs[cfg].G;
-  const bool full = w.tail_chunks == 0 && (w.nchunks % per_iter) == 0;
+  const RowGeometry g = row_geometry(ix);
+  w.nchunks = g.nchunks;
+  w.tail_chunks = g.tail_chunks;
+  w.q_chunks = g.q_chunks;
   w.cap = std::max<uint32_t>((uint32_t)W, 4 * ix->M);  // connect prunes row + up to cap - M requesters at a time
   auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
   uint32_t off = 0;
@@ -2375,8 +2375,8 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
   off = align16(off + (WAVE + 1) * 4);
   const uint32_t lds_bytes = off;
   if (lds_bytes > 160u * 1024u) return fail(FNV_ERR_INVALID, "ef_construction too large for the on-chip wiring state");
-  wire_fn kernels[2] = {pick_wire_kernel(ix->dtype, ix->metric, cfg, full),
-                        pick_connect_kernel(ix->dtype, ix->metric, cfg, full)};
+  wire_fn kernels[2] = {pick_wire_kernel(ix->dtype, ix->metric, g.cfg, g.full),
+                        pick_connect_kernel(ix->dtype, ix->metric, g.cfg, g.full)};
   for (int phase = 0; phase < 2; phase++) {
     wire_fn kern = kernels[phase];
     HIP_TRY(raise_lds_limit((const void*)kern, ix->device, lds_bytes));
@@ -2400,7 +2400,7 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
   std::vector<uint64_t> nd;
   if (evals_out) {
     nd.resize(count);
-    HIP_TRY(hipMemcpyAsync(nd.data(), o + o_nd, count * 8, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(nd.data(), beams.ndist, count * 8, hipMemcpyDeviceToHost, ix->stream));
   }
   HIP_TRY(hipStreamSynchronize(ix->stream));
   if (evals_out) {
@@ -2408,10 +2408,8 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
     for (uint64_t e : nd) total += e;
     *evals_out = total;
   }
-  int32_t st = 0;
-  HIP_TRY(hipMemcpy(&st, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (st == ST_CAND_OVERFLOW)
-    return fail(FNV_ERR_CAPACITY, "candidate heap overflowed its HBM spill area; raise spill_entries");
+  rc = check_device_status(ix, "raise spill_entries");
+  if (rc) return rc;
   ix->n_nodes = first_node + count;
   return FNV_OK;
 }

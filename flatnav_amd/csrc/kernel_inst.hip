@@ -1,8 +1,6 @@
 // kernel_inst.hip -- one compilation = the instantiations of ONE kernel family for ONE (element type, metric):
-//   hipcc -c -DFNV_INST_T=float -DFNV_INST_TAG=f32 -DFNV_INST_METRIC=0 -DFNV_INST_MTAG=l2 -DFNV_INST_FAMILY=4 ...
-// families: 0 exact two-heap kernel + entry scan, 3 wiring kernels, 4 merged beam (<= 256 entries in registers),
-// 5 merged beam (<= 64 entries in registers), 6 merged beam (LDS, any width), 7 merged beam (<= 128 in registers), 8-11 the
-// DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS), 12 the filtered two-heap kernel.
+//   hipcc -c -DFNV_INST_T=float -DFNV_INST_TAG=f32 -DFNV_INST_METRIC=0 -DFNV_INST_MTAG=l2 -DFNV_INST_FAMILY=4 -DFNV_INST_FNAME=merged ...
+// The families (ordinal, name) are listed in kernel_table.h (FNV_FOR_EACH_FAMILY).
 // flatnav_amd/build.py compiles the 88 combinations in parallel and links them with beam_search.hip.
 #include <hip/hip_runtime.h>
 
@@ -11,9 +9,8 @@
 #include "merged_beam.hpp"
 #include "wire.hpp"
 
-#define FNV_CAT_(a, b, c, d, e) a##b##c##d##e
-#define FNV_CAT(a, b, c, d, e) FNV_CAT_(a, b, c, d, e)
-#define FNV_FILLER(family) FNV_CAT(fill_, family, FNV_INST_TAG, _, FNV_INST_MTAG)
+#define FNV_CAT_(a, b, c, d, e, f) a##b##c##d##e##f
+#define FNV_CAT(a, b, c, d, e, f) FNV_CAT_(a, b, c, d, e, f)
 
 namespace fnv_dev {
 
@@ -38,59 +35,18 @@ static void fill_rows(KernelTable& t) {
   FNV_ROW(t.scan, entry_scan_kernel)
 #elif FNV_INST_FAMILY == 12
   FNV_ROW(t.exact_f, beam_search_filtered_kernel)
-#elif FNV_INST_FAMILY == 4
-#define FNV_COMMA_MB_R , MB_R
-  FNV_ROW(t.merged, beam_search_merged_kernel, FNV_COMMA_MB_R)
-#elif FNV_INST_FAMILY == 5
-#define FNV_COMMA_ONE , 1
-  FNV_ROW(t.merged1, beam_search_merged_kernel, FNV_COMMA_ONE)
-#elif FNV_INST_FAMILY == 6
-#define FNV_COMMA_ZERO , 0
-  FNV_ROW(t.merged0, beam_search_merged_kernel, FNV_COMMA_ZERO)
-#elif FNV_INST_FAMILY == 7
-#define FNV_COMMA_TWO , 2
-  FNV_ROW(t.merged2, beam_search_merged_kernel, FNV_COMMA_TWO)
-#elif FNV_INST_FAMILY == 8
-#define FNV_COMMA_MB_R_D , MB_R, true
-  FNV_ROW(t.merged_d, beam_search_merged_kernel, FNV_COMMA_MB_R_D)
-#elif FNV_INST_FAMILY == 9
-#define FNV_COMMA_ONE_D , 1, true
-  FNV_ROW(t.merged1_d, beam_search_merged_kernel, FNV_COMMA_ONE_D)
-#elif FNV_INST_FAMILY == 10
-#define FNV_COMMA_ZERO_D , 0, true
-  FNV_ROW(t.merged0_d, beam_search_merged_kernel, FNV_COMMA_ZERO_D)
-#elif FNV_INST_FAMILY == 11
-#define FNV_COMMA_TWO_D , 2, true
-  FNV_ROW(t.merged2_d, beam_search_merged_kernel, FNV_COMMA_TWO_D)
+#elif FNV_INST_FAMILY >= 4 && FNV_INST_FAMILY <= 11
+  constexpr int kFormOfFamily[4] = {3, 1, 0, 2};  // families 4-7 (and 8-11): MB_R / one / no (LDS) / two register chunks
+  constexpr int form = kFormOfFamily[(FNV_INST_FAMILY - 4) % 4];
+  constexpr bool direct = FNV_INST_FAMILY >= 8;
+  FNV_ROW(t.merged[form][direct], beam_search_merged_kernel, , kBeamFormR[form], direct)
 #else
   FNV_ROW(t.select, wire_select_kernel)
   FNV_ROW(t.connect, wire_connect_kernel)
 #endif
 }
 
-#if FNV_INST_FAMILY == 0
-void FNV_CAT(fill_exact_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 12
-void FNV_CAT(fill_exact_f_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 4
-void FNV_CAT(fill_merged_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 5
-void FNV_CAT(fill_merged1_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 6
-void FNV_CAT(fill_merged0_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 7
-void FNV_CAT(fill_merged2_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 8
-void FNV_CAT(fill_merged_d_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 9
-void FNV_CAT(fill_merged1_d_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 10
-void FNV_CAT(fill_merged0_d_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#elif FNV_INST_FAMILY == 11
-void FNV_CAT(fill_merged2_d_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#else
-void FNV_CAT(fill_wire_, FNV_INST_TAG, _, FNV_INST_MTAG, )(KernelTable& t) {
-#endif
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
   fill_rows<false>(t);
   fill_rows<true>(t);
 }

@@ -35,16 +35,18 @@ inline int pick_row_cfg(uint32_t nchunks, uint32_t tail_chunks = 0) {
   return 5;
 }
 
+// Forms of the merged-beam kernel (merged_beam.hpp): the beam in LDS (any width), or in one / two / MB_R 64-entry chunks of
+// registers (beams of at most 64 / 128 / 256 entries) -- the kernel's R argument.
+constexpr int kNumBeamForms = 4;
+constexpr int kBeamFormR[kNumBeamForms] = {0, 1, 2, MB_R};
+inline int beam_form(bool lds, int B) { return lds ? 0 : B <= WAVE ? 1 : B <= 2 * WAVE ? 2 : 3; }
+
 // All kernels for one (element type, metric): [row configuration][FULL rows].
 struct KernelTable {
   kernel_fn exact[kNumCfgs][2];        // beam_search_kernel (two heaps, libstdc++-exact)
   kernel_fn exact_f[kNumCfgs][2];      // beam_search_filtered_kernel (the same, results restricted to a node bitmap)
   kernel_fn scan[kNumCfgs][2];         // entry_scan_kernel (K0)
-  kernel_fn merged[kNumCfgs][2];       // beam_search_merged_kernel (beam <= 256 in registers, one merge per link row)
-  kernel_fn merged1[kNumCfgs][2];      // ... its one-chunk form (beam <= 64)
-  kernel_fn merged0[kNumCfgs][2];      // ... its LDS form (any beam width)
-  kernel_fn merged2[kNumCfgs][2];      // ... its two-chunk form (beam <= 128)
-  kernel_fn merged_d[kNumCfgs][2], merged1_d[kNumCfgs][2], merged0_d[kNumCfgs][2], merged2_d[kNumCfgs][2];  // their DIRECT forms
+  kernel_fn merged[kNumBeamForms][2][kNumCfgs][2];  // beam_search_merged_kernel, [beam form][DIRECT form] first
   wire_fn select[kNumCfgs][2];         // wire_select_kernel
   wire_fn connect[kNumCfgs][2];        // wire_connect_kernel
 };
@@ -54,20 +56,19 @@ struct KernelTable {
   X(float, f32, 0, l2) X(float, f32, 1, ip) X(uint8_t, u8, 0, l2) X(uint8_t, u8, 1, ip) X(int8_t, i8, 0, l2) X(int8_t, i8, 1, ip) \
   X(_Float16, f16, 0, l2) X(_Float16, f16, 1, ip)
 
-// one filler per kernel family and (type, metric), each defined by one compilation of kernel_inst.hip
-#define FNV_DECLARE_FILLERS(T, tag, M, mtag)             \
-  void fill_exact_##tag##_##mtag(KernelTable& t);        \
-  void fill_exact_f_##tag##_##mtag(KernelTable& t);      \
-  void fill_merged_##tag##_##mtag(KernelTable& t);       \
-  void fill_merged1_##tag##_##mtag(KernelTable& t);      \
-  void fill_merged0_##tag##_##mtag(KernelTable& t);      \
-  void fill_merged2_##tag##_##mtag(KernelTable& t);      \
-  void fill_merged_d_##tag##_##mtag(KernelTable& t);     \
-  void fill_merged1_d_##tag##_##mtag(KernelTable& t);    \
-  void fill_merged0_d_##tag##_##mtag(KernelTable& t);    \
-  void fill_merged2_d_##tag##_##mtag(KernelTable& t);    \
-  void fill_wire_##tag##_##mtag(KernelTable& t);
+// The kernel families, X(ordinal, name): one compilation of kernel_inst.hip (-DFNV_INST_FAMILY=ordinal -DFNV_INST_FNAME=name)
+// per family and (type, metric) defines the filler fill_<name>_<type tag>_<metric tag>.  0 the exact two-heap kernel + entry
+// scan, 12 its filtered form, 3 the wiring kernels, 4-7 the merged beam in MB_R / 1 / 0 (LDS) / 2 register chunks, 8-11 the
+// DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS).
+#define FNV_FOR_EACH_FAMILY(X, ...)                                                                              \
+  X(0, exact, __VA_ARGS__) X(12, exact_f, __VA_ARGS__) X(3, wire, __VA_ARGS__) X(4, merged, __VA_ARGS__)         \
+  X(5, merged1, __VA_ARGS__) X(6, merged0, __VA_ARGS__) X(7, merged2, __VA_ARGS__) X(8, merged_d, __VA_ARGS__)   \
+  X(9, merged1_d, __VA_ARGS__) X(10, merged0_d, __VA_ARGS__) X(11, merged2_d, __VA_ARGS__)
+
+#define FNV_DECLARE_FILLER(ordinal, family, tag, mtag) void fill_##family##_##tag##_##mtag(KernelTable& t);
+#define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_FOR_EACH_FAMILY(FNV_DECLARE_FILLER, tag, mtag)
 FNV_FOR_EACH_TYPE_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
+#undef FNV_DECLARE_FILLER
 
 }  // namespace fnv_dev

@@ -30,7 +30,7 @@ args = ap.parse_args()
 out = "/tmp/isa_regions.s"
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DFNV_ASM_MARKS", "-Wno-unused-function", "-Wno-inline-asm",
        "-I" + os.path.join(ROOT, "include"), "-DFNV_INST_T=" + args.type, "-DFNV_INST_TAG=" + args.tag, "-DFNV_INST_METRIC=%d" % args.metric,
-       "-DFNV_INST_MTAG=" + ("l2" if args.metric == 0 else "ip"), "-DFNV_INST_FAMILY=%d" % args.family] + ["-D" + d for d in args.defines] + [
+       "-DFNV_INST_MTAG=" + ("l2" if args.metric == 0 else "ip"), "-DFNV_INST_FAMILY=%d" % args.family, "-DFNV_INST_FNAME=f%d" % args.family] + ["-D" + d for d in args.defines] + [
            "-S", "--cuda-device-only", os.path.join(ROOT, "flatnav_amd/csrc/kernel_inst.hip"), "-o", out]
 subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 s = open(out).read()
