@@ -9,12 +9,22 @@
 //                        candidate unless an already kept node is strictly closer to it than u is, stop at M/2
 //                        kept; write u's row (kept nodes in the order the reference pops them -- farthest first,
 //                        equal distances as libstdc++'s heap leaves them -- then self-loops); record one
-//                        back-link request per kept v: req_target[u's slot t] = v.
+//                        back-link request per kept v: req_target[u's slot t] = v.  A beam with fewer than M/2 entries
+//                        is not pruned (Index.h:715-717): all of it is kept and the row is the beam's own heap popped
+//                        empty -- farthest first, equal distances in the order that heap gives them up, which the
+//                        search kernel recorded (it writes the beam closest first with equal distances in reverse pop
+//                        order; the row is the beam read backwards).  That order is the search's, not a function of
+//                        (distance, id) as everywhere else in this file.
 //   radix sort           the batch's requests by target id (stable: the requesters of one target stay in insertion
 //                        order, i.e. ascending new-node id -- the order in which a sequential build meets them).
 //   wire_connect_kernel  one wave per target v (= per run of equal keys): if the requesters fit v's free (self-loop)
 //                        slots they take them in order (Index.h:789-797), otherwise {row(v)} + {requesters} is
-//                        re-pruned with the same rule, keep <= M (Index.h:799-829).
+//                        re-pruned with the same rule, keep <= M (Index.h:799-829).  The candidate arrays hold
+//                        cap = max(ef_construction, 4 M) entries: a target with more requesters than fit is consumed in
+//                        rounds -- fill up to cap in insertion order, prune to <= M whenever more than M are held, the
+//                        kept nodes (in pop order) start the next round.  A row that was pruned is written as that
+//                        list + self-loops, also when a last round added requesters without needing another prune.
+//                        (tests/batched_wiring_ref.cpp restates this rule on the CPU; the tests compare byte for byte.)
 // A wave owns its target's row outright, so hot targets cost one pruning pass over all their requesters
 // instead of a lock hand-off per requester (a first version with per-node spin locks spent 3/4 of its time
 // in hand-offs on hub nodes).  The reference re-prunes once per arriving back-link; pruning the union once is a
