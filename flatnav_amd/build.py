@@ -17,8 +17,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libflatnav_hip.so")
-HEADERS = [os.path.join(CSRC, f) for f in ("search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp", "visited.hpp",
-                                           "kernels.hpp", "wire.hpp", "merged_beam.hpp", "relayout.hpp")] + [
+HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
+                                           "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "relayout.hpp",
+                                           "launch_plan.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
 MAIN = os.path.join(CSRC, "beam_search.hip")
 INST = os.path.join(CSRC, "kernel_inst.hip")
@@ -53,8 +54,8 @@ def _stale(obj, src):
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    # relayout.hpp (upload / measurement kernels) is included by beam_search.hip only
-    deps = HEADERS if src == MAIN else [h for h in HEADERS if not h.endswith("relayout.hpp")]
+    # relayout.hpp (upload / measurement kernels) and launch_plan.hpp (the launch planner) are included by beam_search.hip only
+    deps = HEADERS if src == MAIN else [h for h in HEADERS if not h.endswith(("relayout.hpp", "launch_plan.hpp"))]
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 
 

@@ -21,9 +21,14 @@
 // lane), reduces the distances across lanes with DPP, then replays the reference's
 // sequential admission rule on the results.
 //
+// The launch planner -- row layout, visited-table geometry, a slot's LDS layout, table-size ladder, kernel family and variant,
+// launch shape: every decision that is arithmetic -- lives in launch_plan.hpp, free of HIP (tests/test_launch_plan.py runs
+// it on the CPU); this file owns the HIP runtime around it: handles, buffers, streams and events, kernel lookup, the
+// occupancy queries and LDS limits the planner asks for, the launches and the C ABI.
+//
 // Also here: incremental construction (fnv_index_write_nodes / write_links / insert_batch: Index::add,
 // include/flatnav/index/Index.h:353-378 with selectNeighbors :714-763 and connectNeighbors :765-834 as the
-// wire_select / wire_connect kernels of wire.hpp) and the merged-beam search kernel (merged_beam.hpp).
+// wire_select / wire_connect kernels of wire.hpp); the merged-beam search kernel is merged_beam.hpp.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -43,6 +48,7 @@
 
 #include "../../include/flatnav_hip.h"
 #include "kernel_table.h"
+#include "launch_plan.hpp"
 #ifdef FNV_DEV_FAST_BUILD
 #include "kernels.hpp"
 #include "merged_beam.hpp"
@@ -69,16 +75,6 @@ int fail(int code, const std::string& msg) {
     if (_e != hipSuccess)                                                                               \
       return fail(FNV_ERR_NO_DEVICE, std::string(#expr) + " failed: " + hipGetErrorString(_e));        \
   } while (0)
-
-size_t dtype_size(int dt) {
-  switch (dt) {
-    case FNV_DTYPE_FLOAT32: return 4;
-    case FNV_DTYPE_FLOAT16: return 2;
-    case FNV_DTYPE_UINT8:
-    case FNV_DTYPE_INT8: return 1;
-    default: return 0;
-  }
-}
 
 // Every entry point works on its index's device and gives the calling thread its current device back on every exit
 // path: a library call must not move a torch (or any other HIP) caller's allocations to another GPU.
@@ -197,18 +193,10 @@ wire_fn pick_connect_kernel(int dtype, int metric, int cfg, bool full) { return 
 
 }  // namespace
 
-// What a search launch looks like for one (beam width, K) on one index: cached, because working it out costs
-// several occupancy queries and a single-query search should not pay for them every time.
-struct LaunchPlan {
-  bool valid = false;
-  int B = 0, K = 0, cfg = 0, mode = 0;
-  bool full = false;
-  uint64_t capacity = 0, options_version = 0;
+// The cached launch plan of a handle (launch_plan.hpp) and the kernels that run it.
+struct PlannedLaunch : LaunchPlan {
   kernel_fn kern = nullptr, skern = nullptr;  // exact two-heap kernel; merged-beam kernel (mode != 0)
   kernel_fn skern_direct = nullptr;           // ... its DIRECT form (small launches on small indexes)
-  SearchParams heaps, sorted;                 // geometry + LDS layout for each (per-call fields unset)
-  uint32_t lds = 0, slds = 0;
-  int bpc = 0, sbpc = 0;
   kernel_fn fkern = nullptr;  // filtered search: the two-heap kernel's filtered form on the `heaps` layout (set at first use)
   int fbpc = 0;               // ... and the slots one CU keeps resident with it
 };
@@ -296,65 +284,23 @@ struct DeviceBuf {
   }
 };
 
-// Everything fnv_set_option can change: one block, so that views and replicas start as exact copies of their source.
-struct IndexOptions {
-  int64_t visited_factor = 27, visited_slots = 0, visited_floor = 2048, occupancy_target = 13, occupancy_roomy = 9, cand_factor = 2,
-          cand_slots = 0, spill_entries = 16384, blocks_per_cu = 0, visited_wide = 0,
-          entry_kernel = 0, output_node_ids = 0, visited_tag_bits = 0, sorted_beam = 2,
-          sorted_beam_min = 1, sorted_cand_lds = 2, sorted_tail_exact_pct = -1, beam_registers = 1,
-          sorted_variant = -1, tune_layout = 1, shadow_exact = 1, tie_replay = 1, tie_log_entries = 0, visited_direct = 1,
-          host_zero_copy = 1 << 20;  // (every call that fits the pinned staging buffer)
-  int64_t overflow_list = -1;  // -1: automatic (a list in HBM only when the bitmap is larger than 512 KB)
-};
-
-// Kernel variants of one launch: 0 the exact two-heap kernel, 1 the merged-beam kernel, 2-5 the merged-beam kernel with
-// the last 50 / 75 / 100 / 25 % of a round of queries sent straight to the exact search, 6 (round 4) the merged-beam kernel
-// for every query plus exact shadows of the last ones on the slots the drain leaves idle (search_params.h).
-constexpr int kNumVariants = 7;
-constexpr int kVariantTailShadows = 6;
-static const int kTailPct[kNumVariants] = {0, 0, 50, 75, 100, 25, 0};
-static inline bool variant_allowed(int v, bool multi_round, bool try_tail, bool shadows_on, bool pinned_only = false) {
-  if (v < 2) return true;
-  // (tail shadows: measured in round 4 -- 0.5-3 % better than the merged-beam kernel alone, behind the best exact tail on every configuration:
-  //  a shadow can only start when a slot falls idle, which is too late for the ties that end a launch -- so the variant can
-  //  be pinned for A/B runs but is not part of the adaptive choice)
-  if (v == kVariantTailShadows) return shadows_on && pinned_only;
-  return multi_round && try_tail;  // an exact tail needs more than one round of queries
-}
-
-struct fnv_index_s : IndexOptions {
+struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cus: what the planner reads)
   bool owns_buffers = true;  // false: a view (fnv_index_view) of another handle's vectors / links / labels
   fnv_index_s* parent = nullptr;  // a view's source: its live node count is read at every launch
   std::atomic<int> n_views{0};    // live views of this handle's buffers (it cannot be freed before them)
   int device = 0;
-  int dtype = FNV_DTYPE_FLOAT32, metric = FNV_METRIC_L2;
-  uint32_t M = 0, dim = 0, row_bytes = 0;
-  uint32_t tail_bytes = 0;  // split rows (distance.hpp, row_layout below): bytes per row in the side table that follows the main
-                            // table in d_vectors' allocation ([capacity][row_bytes] main, then [capacity][tail_bytes]); 0: one table
+  int metric = FNV_METRIC_L2;
   const uint8_t* tails() const { return tail_bytes ? d_vectors + capacity * (uint64_t)row_bytes : nullptr; }
   uint64_t vector_bytes() const { return capacity * ((uint64_t)row_bytes + tail_bytes); }
   std::atomic<uint64_t> n_nodes{0};  // live nodes: what a search sees (entry scan, id range); a view reads its source's at
                                      // every launch while the source may be growing -> atomic
-  uint64_t capacity = 0;  // rows the device buffers hold (>= n_nodes; grows never)
   uint8_t* d_vectors = nullptr;
   uint32_t* d_links = nullptr;
   int32_t* d_labels = nullptr;
-  int num_cus = 0;
   std::string gcn_arch;  // hipDeviceProp_t::gcnArchName: replicas on the same GPU model inherit the source's measurements
   uint64_t options_version = 0;
-  LaunchPlan plan;
-  // adaptive kernel choice ("sorted_beam" = 2): per beam width, the best time per query seen for each variant
-  struct Tuner {
-    // ms per query: [0] two-heap kernel, [1] merged-beam kernel, [2..5] merged-beam kernel whose last 50 / 75 / 100 / 25 %
-    // of a round of queries go straight to the exact search ("sorted_tail_exact_pct"; launches of more than one round)
-    float best[kNumVariants] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
-    int samples[kNumVariants] = {0, 0, 0, 0, 0, 0, 0};
-  };
-  // Per beam width: the LDS layout fnv_tune measured to be the fastest (absent: the rules of configure_launch).
-  struct LayoutChoice {
-    int cand_lds = -1;       // where the exact search keeps its candidates heap: -1 = by rule, 0 = HBM, 1 = LDS
-    uint32_t vis_slots = 0;  // visited-table slots: 0 = by rule
-  };
+  PlannedLaunch plan;
+  // adaptive kernel choice ("sorted_beam" = 2) and the layouts fnv_tune measured, per beam width (launch_plan.hpp)
   std::map<int, LayoutChoice> layouts;
   std::map<int, Tuner> tuner;
   int sample_B = 0, sample_kernel = -1;  // the launch between ev0 / ev1 is a sample for this entry (-1: it is not)
@@ -467,47 +413,6 @@ int alloc_buffers(fnv_index_s* ix) {  // the caller is on ix->device
   return index_common_init(ix);
 }
 
-// Row stride of the vector table.  Rows are 16-byte chunks; when rounding the stride up to whole 128-byte lines costs
-// at most FLATNAV_ROW_PAD_PCT (default 30) per cent of padding it is done: a 100-d float32 row (400 bytes) at a
-// 16-byte stride straddles 4-5 lines (4.0 on average = the 512 bytes the padded row occupies anyway), takes the clamped
-// non-FULL distance path and costs the gather ~20 % of its rate (tools/gather_bench.hip: 5.9 vs 7.1 TB/s of row bytes);
-// at a 512-byte stride it is exactly four lines and whole 8-lane x 4-chunk spans.  The padding is zero in rows and in
-// the staged query, so every distance keeps its bits (zeros add nothing to either partial sum).
-uint32_t row_stride_bytes(uint32_t dim, int data_type) {
-  const uint64_t rb16 = ((uint64_t)dim * dtype_size(data_type) + 15) / 16 * 16;
-  const uint64_t rb128 = (rb16 + 127) / 128 * 128;
-  long pct = 30;
-  if (const char* env = getenv("FLATNAV_ROW_PAD_PCT")) pct = strtol(env, nullptr, 10);
-  if (pct > 0 && (rb128 - rb16) * 100 <= (uint64_t)pct * rb16) return (uint32_t)rb128;
-  return (uint32_t)rb16;
-}
-
-// SPLIT ROWS (round 6, distance.hpp): a row of exactly three 128-byte lines plus at most 32 bytes (d = 97 ... 104 float32, 385 ... 416
-// one-byte elements) keeps its whole lines in the main table (stride 384) and its last one or two chunks in a dense side
-// table -- as long as that table stays small enough to live in L2 / Infinity Cache (FLATNAV_SPLIT_TAIL_MAX_MB, default 64 MB:
-// 4 M rows of 16 bytes), where the fourth request of a gather no longer costs an HBM line that is 7/8 padding.
-// FLATNAV_SPLIT_ROWS=0 turns it off (rows are then padded to four lines, as in rounds 2-5).  Every handle on the same
-// buffers (views, fnv_index_adopt, replicas, the ranks of a broadcast) derives the same layout from (dim, type, capacity).
-struct RowLayout {
-  uint32_t row_bytes, tail_bytes;
-};
-RowLayout row_layout(uint32_t dim, int data_type, uint64_t capacity) {
-  const uint64_t rb16 = ((uint64_t)dim * dtype_size(data_type) + 15) / 16 * 16;
-  const uint64_t rem = rb16 % 128;
-  long on = 1, max_mb = 64;
-  if (const char* env = getenv("FLATNAV_SPLIT_ROWS")) on = strtol(env, nullptr, 10);
-  if (const char* env = getenv("FLATNAV_SPLIT_TAIL_MAX_MB")) max_mb = strtol(env, nullptr, 10);
-  if (on && rb16 - rem == 384 && rem > 0 && rem <= 32 && capacity * rem <= ((uint64_t)max_mb << 20))
-    return RowLayout{384u, (uint32_t)rem};
-  return RowLayout{row_stride_bytes(dim, data_type), 0u};
-}
-
-uint32_t pow2_ceil(uint64_t v) {
-  uint32_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 // Copy AoS node records [data][M links][label] (reference Index.h:61-63) for nodes first..first+count-1 into the
 // SoA device buffers, 256 MB at a time.  Link ids >= id_limit are flagged (and replaced by a self-loop).
 int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes, const void* aos_rows,
@@ -520,21 +425,12 @@ int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes,
   if (rcg) return rcg;
   uint8_t* d_stage = ix->d_nodestage.as<uint8_t>();
   int* d_bad = (int*)(d_stage + (need - 16));
-  auto cleanup = [&]() {};
-#define UP_TRY(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) {                                                                            \
-      cleanup();                                                                                       \
-      return fail(FNV_ERR_NO_DEVICE, std::string(#expr) + " failed: " + hipGetErrorString(_e));       \
-    }                                                                                                  \
-  } while (0)
-  UP_TRY(hipMemset(d_bad, 0, sizeof(int)));
+  HIP_TRY(hipMemset(d_bad, 0, sizeof(int)));
   const int word_ok = (node_size % 4 == 0 && data_size % 4 == 0) ? 1 : 0;
   for (uint64_t done = 0; done < count_nodes; done += chunk_nodes) {
     const uint64_t count = std::min(chunk_nodes, count_nodes - done);
     const uint64_t first = first_node + done;
-    UP_TRY(hipMemcpy(d_stage, (const uint8_t*)aos_rows + done * node_size, count * node_size, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_stage, (const uint8_t*)aos_rows + done * node_size, count * node_size, hipMemcpyHostToDevice));
     const uint32_t row_all = ix->row_bytes + ix->tail_bytes;  // bytes of a row over both tables
     const uint64_t units = count * (word_ok ? row_all / 4 : row_all);
     hipLaunchKernelGGL(relayout_vectors_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, 0, d_stage,
@@ -542,12 +438,10 @@ int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes,
                        const_cast<uint8_t*>(ix->tails()), word_ok);
     hipLaunchKernelGGL(relayout_links_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d_stage,
                        node_size, data_size, ix->M, first, count, id_limit, ix->d_links, ix->d_labels, d_bad);
-    UP_TRY(hipGetLastError());
-    UP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
   }
-  UP_TRY(hipMemcpy(bad_out, d_bad, sizeof(int), hipMemcpyDeviceToHost));
-  cleanup();
-#undef UP_TRY
+  HIP_TRY(hipMemcpy(bad_out, d_bad, sizeof(int), hipMemcpyDeviceToHost));
   return FNV_OK;
 }
 
@@ -639,19 +533,14 @@ int fnv_index_view(fnv_index_t src, fnv_index_t* out) {
   fnv_index_s* v = new fnv_index_s();
   v->owns_buffers = false;
   v->device = src->device;
-  v->dtype = src->dtype;
+  static_cast<PlanInputs&>(*v) = static_cast<const PlanInputs&>(*src);  // options, row geometry, capacity
   v->metric = src->metric;
-  v->M = src->M;
-  v->dim = src->dim;
-  v->row_bytes = src->row_bytes;
-  v->tail_bytes = src->tail_bytes;
   v->n_nodes = src->n_nodes.load();
-  v->capacity = src->capacity;
   v->d_vectors = src->d_vectors;
   v->d_links = src->d_links;
   v->d_labels = src->d_labels;
-  static_cast<IndexOptions&>(*v) = static_cast<const IndexOptions&>(*src);
   v->parent = src->parent ? src->parent : src;  // a view of a view hangs off the owner
+  v->parent_capacity = v->parent->capacity;
   DeviceScope scope(v->device);
   if (scope.err != hipSuccess) {
     delete v;
@@ -870,179 +759,7 @@ int fnv_search_batch_device(fnv_index_t ix, const void* d_queries, uint64_t nq, 
                             SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, d_out_nhops}, hip_stream);
 }
 
-// ---- launch configuration ---------------------------------------------------------------------------------
-// How a query slot's LDS is laid out depends on the kernel: the two-heap kernel keeps {query, neighbours heap,
-// candidates heap, visited table, staging}; the merged-beam kernel keeps {query, [beam array], visited table, staging}.
-enum { MODE_HEAPS = 0, MODE_MERGED_REGS = 1, MODE_MERGED_LDS = 2 };
-
-// Visited-table geometry for a table of `slots` (2^j or 3*2^j) and the LDS layout that follows from it; returns the
-// bytes of LDS one query slot needs.  16-bit tags whenever the per-bucket id range fits 14 bits: buckets =
-// mult*2^k, t = nbits - k, need t <= 14 (mult 1) or t <= 15 (mult 3).
-static uint32_t lay_out(const fnv_index_s* ix, SearchParams& p, uint32_t slots, int mode) {
-  uint32_t nbits = 1;
-  while (nbits < 32 && (1ull << nbits) < ix->capacity) nbits++;
-  const uint32_t mult = (slots % 3 == 0) ? 3u : 1u;
-  uint32_t k = 0;
-  for (uint32_t b = slots / 4 / mult; b > 1; b >>= 1) k++;
-  const bool can16 = !ix->visited_wide && ix->visited_tag_bits <= 16 && nbits <= 30 && k <= nbits && (nbits - k) <= (mult == 3 ? 15u : 14u);
-  // otherwise 64-bit buckets: three 21-bit tags (slots = 3 * 2^j) or two 32-bit tags (slots = 2^j)
-  const uint32_t w = can16 ? 16u : (slots % 3 == 0 ? 21u : 32u);
-  const uint32_t wbuckets = w == 21 ? slots / 3 : slots / 2;
-  uint32_t wk = 0;
-  for (uint32_t b = wbuckets; b > 1; b >>= 1) wk++;
-  const bool canw = !can16 && !ix->visited_wide && wk <= nbits && (nbits - wk) <= w - 2;
-  if (!can16 && !canw && mult == 3) slots = pow2_ceil(slots);  // the open-addressing table needs a power of two
-  p.vis_slots = slots;
-  p.vis_tag16 = (can16 || canw) ? 1u : 0u;
-  p.vis_w = w;
-  p.vis_mult = can16 ? mult : 1u;
-  p.vis_nmask = (uint32_t)((1ull << nbits) - 1ull);
-  p.vis_rshift = can16 ? nbits - k : (canw ? nbits - wk : 0);
-  p.vis_rmask = p.vis_tag16 ? (uint32_t)((1ull << p.vis_rshift) - 1ull) : 0;
-  p.vis_bytes = can16 ? slots * 2 : (canw ? wbuckets * 8 : slots * 4);
-  p.vis_shift = 32;
-  for (uint32_t sft = p.vis_slots; sft > 1; sft >>= 1) p.vis_shift--;
-  p.vis_limit = p.vis_slots / 4 * 3;
-
-  auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
-  uint32_t off = 0;
-  p.off_q = off;
-  off = align16(off + p.q_lds_bytes);
-  // neighbours heap (exact search) / sorted beam: arrays start at 16n + 8 so that child pairs are 16-byte aligned
-  p.off_nbr = off + 8;
-  // (merged-beam kernel: the same bytes stage a link row's distances, [WAVE + 1] floats, between two merges)
-  off = align16(off + 8 + std::max<uint32_t>(((uint32_t)p.B + 2) * 8, mode == MODE_MERGED_REGS ? (WAVE + 1) * 4 : 0));
-  p.off_stage_d = p.off_nbr;
-  if (mode == MODE_MERGED_LDS) {  // LDS form: the array is the beam itself, the staging area its own
-    p.off_stage_d = off;
-    off = align16(off + (WAVE + 1) * 4);
-  }
-  p.off_cand = off + 8;  // candidates heap of the exact search: cand_slots entries in LDS (0: all of it in HBM)
-  if (p.cand_slots) off = align16(off + 8 + (p.cand_slots + 1) * 8);
-  p.off_vis = off;
-  off = align16(off + p.vis_bytes);
-  p.off_stage_ids = off;
-  off = align16(off + (WAVE + 1) * 4);  // + one write-only slot for lanes with nothing to stage
-  p.off_ovf = off;
-  off = align16(off + (OVF_LIST + 2 + STASH) * 4);
-  return off;
-}
-
-// Chooses the visited-table size for `kern` in `mode`, fills p's geometry/layout fields; outputs the LDS bytes per
-// slot and the slots one CU keeps resident.
-// Table sizes, ascending: 256, 384, 512, 768, ...  The roomy size (visited_factor * B + 600, <= 60 % load on the
-// reference workloads) keeps every id in LDS; but LDS is also what limits how many queries a CU keeps in flight, and
-// a lone wave issues slowly -- below ~13 resident queries per CU the loss of latency hiding costs more than sending
-// part of the ids to the HBM bitmap (measured: profiles/r1_visited_sizing.md).  So: the largest size <= roomy that
-// still leaves `occupancy_target` queries per CU, but never below visited_floor slots.
-// gfx950 hands LDS out in 1280-byte granules (160 KiB = 128 of them): a workgroup that asks for 7712 bytes holds seven, and
-// a CU keeps 18 such workgroups, not the floor(163840 / 7712) = 21 that hipOccupancyMaxActiveBlocksPerMultiprocessor reports.
-// Measured in round 4 (tools/dev/probes/lds_granule.cpp: resident single-wave workgroups per CU against the dynamic LDS size
-// -- 7680 bytes: 21, 7681: 18; 8960: 18, 8961: 16; 10240: 16, 10241: 14; 32768: 4) after the launch timeline of the uint8 index
-// showed 18 busy slots per CU under a grid of 21 (profiles/r4_launch_timeline.md).
-constexpr uint32_t kLdsGranule = 1280, kLdsPerCu = 160u * 1024u;
-static inline uint32_t lds_allocated(uint32_t lds) { return (lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule; }
-
-static int configure_launch(fnv_index_s* ix, SearchParams& p, kernel_fn kern, int mode, uint32_t* lds_out, int* bpc_out,
-                            bool grow_free = true, uint32_t forced_slots = 0) {
-  // query slots one CU holds with this much LDS each, as the occupancy API counts them.  The table-size rules below were
-  // calibrated against THIS number in rounds 1-3 and keep using it (same layouts as measured); what a CU really keeps
-  // resident -- `really_resident` -- decides the granule trim at the end.
-  auto resident = [&](uint32_t lds) -> int {
-    if (lds > kLdsPerCu) return 0;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kern, WAVE, lds) != hipSuccess) n = 0;
-    return n;
-  };
-  auto really_resident = [&](uint32_t lds) -> int {  // registers and wave slots: the API; LDS: whole granules
-    return std::min<int>(resident(lds), (int)(kLdsPerCu / lds_allocated(std::max<uint32_t>(lds, 1u))));
-  };
-  uint32_t lds_bytes;
-  if (forced_slots == 0) forced_slots = (uint32_t)ix->visited_slots;
-  if (forced_slots) {
-    lds_bytes = lay_out(ix, p, forced_slots, mode);
-  } else {
-    const uint64_t want = std::max<uint64_t>((uint64_t)ix->visited_factor * (uint64_t)p.B + 600, 256);
-    std::vector<uint32_t> sizes;
-    for (uint32_t base = 256; base <= (1u << 15); base <<= 1) {
-      sizes.push_back(base);
-      if (base >= want) break;
-      if (base < (1u << 15)) {
-        sizes.push_back(base / 2 * 3);
-        if ((uint64_t)base / 2 * 3 >= want) break;
-      }
-    }
-    size_t pick = sizes.size() - 1;  // roomy
-    lds_bytes = lay_out(ix, p, sizes[pick], mode);
-    (void)raise_lds_limit((const void*)kern, ix->device, std::min<uint32_t>(lds_bytes, 160u * 1024u));
-    // (a table that holds every id is worth more than the last resident queries: it is kept down to
-    // `occupancy_roomy` (9) of them -- measured with the merged-beam kernel at ef 160-200: -4...-18 % time at 9-11 resident
-    // queries against a smaller table that overflows at 15; below that the smaller table wins again)
-    const int target = (mode != MODE_HEAPS && resident(lds_bytes) >= (int)ix->occupancy_roomy) ? 0 : (int)ix->occupancy_target;
-    const uint32_t roomy_tag16 = p.vis_tag16;
-    for (size_t cand = pick; cand-- > 0 && sizes[cand] >= (uint32_t)ix->visited_floor && resident(lds_bytes) < target;) {
-      const uint32_t smaller = lay_out(ix, p, sizes[cand], mode);
-      // not a step down: the tag format lost (too few buckets for this id width), or -- wider tags per slot -- no
-      // fewer bytes than the table already chosen
-      if (p.vis_tag16 != roomy_tag16 || smaller >= lds_bytes) continue;
-      pick = cand;
-      lds_bytes = smaller;
-    }
-    lds_bytes = lay_out(ix, p, sizes[pick], mode);
-    // A bigger table that costs no resident query is free: at ef=52 the 2048-slot table (60 % full at the end of a
-    // query) already sends ids to the HBM bitmap; 3072 slots fit the same 16 queries per CU (-7 % kernel time).
-    if (grow_free && pick + 1 == sizes.size()) {
-      for (int step = 0; step < 2; step++) {
-        const uint32_t have = p.vis_slots;
-        const uint32_t next = (have & (have - 1)) == 0 ? have / 2 * 3 : have / 3 * 4;
-        if (next > (1u << 15)) break;
-        SearchParams q = p;
-        const uint32_t bytes = lay_out(ix, q, next, mode);
-        if (q.vis_tag16 != p.vis_tag16 || q.vis_slots != next || bytes > kLdsPerCu || resident(bytes) < resident(lds_bytes)) break;
-        p = q;
-        lds_bytes = bytes;
-      }
-    }
-  }
-  if (lds_bytes > 160u * 1024u)
-    return fail(FNV_ERR_INVALID, "ef_search too large for the on-chip beam state (needs " + std::to_string(lds_bytes) +
-                                     " bytes of LDS, 163840 available); lower ef_search or the *_slots options");
-  HIP_TRY(raise_lds_limit((const void*)kern, ix->device, lds_bytes));
-  // A layout that ends a few bytes into a granule pays a whole granule per slot for them.  If dropping at most an eighth of
-  // the exact search's LDS heap entries (its overflow continues in the slot's HBM spill area; the heap is sized by rule of
-  // thumb: cand_factor * B + 192) brings the slot one granule down AND that keeps one more query resident, do so
-  // (the uint8 index at ef=52: 7712 -> 7680 bytes, 18 -> 21 slots per CU, +3 % queries/s, profiles/r4_launch_timeline.md).
-  if (ix->cand_slots == 0 && p.cand_slots > (uint32_t)p.B + 1) {
-    const uint32_t lower = lds_allocated(lds_bytes) - kLdsGranule;
-    const uint32_t over = lds_bytes - lower, entries = (over + 7) / 8;
-    if (lower > 0 && entries <= p.cand_slots / 8 && p.cand_slots - entries >= (uint32_t)p.B + 1 && really_resident(lower) > really_resident(lds_bytes)) {
-      SearchParams q = p;
-      q.cand_slots = p.cand_slots - entries;
-      uint32_t bytes = lay_out(ix, q, p.vis_slots, mode);
-      for (int i = 0; i < 2 && bytes > lower && q.cand_slots > (uint32_t)p.B + 2; i++) {  // (16-byte alignment of what follows the heap)
-        q.cand_slots--;
-        bytes = lay_out(ix, q, p.vis_slots, mode);
-      }
-      if (bytes <= lower && q.vis_slots == p.vis_slots && q.vis_tag16 == p.vis_tag16) {
-        p = q;
-        lds_bytes = bytes;
-      }
-    }
-  }
-  // The GRID is the slots a CU really keeps resident (round 5).  Rounds 1-4 launched the occupancy API's count, also where
-  // that is one more than the LDS granules allow (the surplus workgroup starts when the first slot exits, finds the dispenser
-  // empty and leaves): sizing the grid by `really_resident` lost 0.7-2.9 % then, because the exact tail is a percentage of the
-  // grid and 75 % of the API's count sat nearer the best tail length.  With the hand-over the configurations where the two
-  // counts differ run without a tail, and the two grids measure the same (c4 ef=110: 2.0857 vs 2.0837 ms, 10M x 768 ef=670:
-  // 102.37 vs 102.40 ms; gpurun r5 run 24) -- so `blocks_per_cu` now says what it means.  The table-size rules above keep
-  // comparing the API's counts (the layouts they choose are the measured ones).
-  int bpc = really_resident(lds_bytes);
-  if (bpc < 1) bpc = 1;
-  if (ix->blocks_per_cu > 0) bpc = std::min<int>(bpc, (int)ix->blocks_per_cu);
-  *lds_out = lds_bytes;
-  *bpc_out = bpc;
-  return FNV_OK;
-}
+// ---- launch configuration: launch_plan.hpp ---------------------------------------------------------------------
 
 // While fnv_tune / fnv_index_insert_batch run, their thread holds the handle's host_mu and lane_mu AND every lane's host_mu
 // (taken up front, so that no host-buffer search runs on a lane meanwhile: the existing lanes are locked, and none is created --
@@ -1095,23 +812,6 @@ static size_t release_idle_lanes(fnv_index_s* ix, const fnv_index_s* keep) {
   return release_idle_lanes_locked(ix, keep);
 }
 
-// Records of the hand-over log per query slot (kernels.hpp): a query logs ~6 records per beam entry on the reference workloads
-// (1M x 128 at ef=52: ~310; a hop is a header + the row's admissible neighbours); 24 per entry + 512, in [1024, 16384] records
-// of 8 bytes per slot = 8-128 KB, or what "tie_log_entries" says (in [WAVE + 2, 2^20]).  A log that overflows ends (the query
-// is searched again from scratch if equal keys meet).
-static uint32_t log_entries_for(const fnv_index_s* ix, int B) {
-  if (!ix->tie_replay) return 0u;
-  if (ix->tie_log_entries) return (uint32_t)std::min<int64_t>(1 << 20, std::max<int64_t>(WAVE + 2, ix->tie_log_entries));
-  return std::min<uint32_t>(16384u, std::max<uint32_t>(1024u, pow2_ceil(24ull * (uint64_t)B + 512)));
-}
-
-// Per query slot of a launch on this index: words of the visited set's HBM bitmap (whole 16-byte groups: wide clears) and
-// entries of the list of ids whose bitmap words need clearing.
-static uint32_t bitmap_words_of(const fnv_index_s* ix) { return (uint32_t)(((ix->capacity + 31) / 32 + 3) / 4 * 4); }
-static uint32_t ovf_cap_of(const fnv_index_s* ix) {
-  return ix->overflow_list >= 0 ? (uint32_t)ix->overflow_list : ((uint64_t)bitmap_words_of(ix) * 4 > (512u << 10) ? 16384u : 0u);
-}
-
 // HBM a launch of `nq` queries needs as per-slot workspace on a handle of this index (what grow_workspace grows).
 static size_t launch_workspace_bytes(fnv_index_s* ix, uint64_t nq) {
   std::lock_guard<std::mutex> lock(ix->mu);
@@ -1121,28 +821,6 @@ static size_t launch_workspace_bytes(fnv_index_s* ix, uint64_t nq) {
   const uint64_t log_entries = ix->plan.valid ? log_entries_for(ix, ix->plan.B) : (ix->tie_replay ? std::max<uint64_t>(16384u, (uint64_t)ix->tie_log_entries) : 0u);
   return (size_t)(slots * ((uint64_t)bitmap_words_of(ix) * 4 + (uint64_t)ovf_cap_of(ix) * 4 + (uint64_t)ix->spill_entries * 8 + log_entries * 8));
 }
-
-// How the kernels walk a row of this index: the row configuration, the chunks of a staged query, whether rows are whole spans.
-struct RowGeometry {
-  int cfg;
-  uint32_t nchunks, tail_chunks, q_chunks;
-  bool full;
-};
-static RowGeometry row_geometry(const fnv_index_s* ix) {
-  RowGeometry g;
-  g.nchunks = ix->row_bytes / 16;
-  g.tail_chunks = ix->tail_bytes / 16;
-  g.cfg = pick_row_cfg(g.nchunks, g.tail_chunks);
-  const uint32_t per_iter = (uint32_t)(kCfgs[g.cfg].G * kCfgs[g.cfg].CU);
-  g.q_chunks = (g.nchunks + per_iter - 1) / per_iter * per_iter;
-  if (g.tail_chunks) g.q_chunks = g.nchunks + (uint32_t)kCfgs[g.cfg].G;  // split rows: lane g also reads query chunk 24 + g (zero past the row)
-  g.full = g.tail_chunks == 0 && (g.nchunks % per_iter) == 0;  // rows are whole spans: the lean FULL kernels apply
-                                                                // (the three-line configuration's non-FULL form IS the split-row kernel)
-  return g;
-}
-
-// The adaptive choice keeps its measurements per (beam width, batch class: more than one round of queries or not).
-static int tuner_key(int B, bool multi_round) { return 2 * B + (multi_round ? 1 : 0); }
 
 // The status word of a launch -> the call's result (`advice`: how each caller has always ended the message).
 static int check_status(int32_t st, const char* advice = "raise the spill_entries option") {
@@ -1157,154 +835,73 @@ static int check_device_status(fnv_index_s* ix, const char* advice = "raise the 
 
 // ---- one search launch, step by step (search_device_impl runs them in this order under the handle's mutex) -----------
 // (a) The launch plan: depends on (beam width, K, live geometry, options) only -> cached between calls.
+// The HIP runtime as the planner sees it: the kernels of one (index, beam width) by MODE_*.
+struct PlanRuntime {
+  const fnv_index_s* ix;
+  RowGeometry g;
+  int B;
+  kernel_fn kernel(int mode, bool direct = false) const {
+    return mode == MODE_HEAPS ? pick_kernel(ix->dtype, ix->metric, g.cfg, g.full)
+                              : pick_sorted_kernel(ix->dtype, ix->metric, g.cfg, g.full, mode == MODE_MERGED_LDS, B, direct);
+  }
+  int occupancy(int mode, uint32_t lds) const {
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kernel(mode), WAVE, lds) == hipSuccess ? n : 0;
+  }
+  const char* raise_lds_limit(int mode, uint32_t lds) const {
+    const hipError_t e = ::raise_lds_limit((const void*)kernel(mode), ix->device, lds);
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  }
+};
 static int ensure_plan(fnv_index_s* ix, int B, int K) {
-  LaunchPlan& plan = ix->plan;
+  PlannedLaunch& plan = ix->plan;
   if (plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity && plan.options_version == ix->options_version)
     return FNV_OK;
-  plan = LaunchPlan();
-  const RowGeometry g = row_geometry(ix);
-  SearchParams p;
-  memset(&p, 0, sizeof(p));
-  p.vectors = ix->d_vectors;
-  p.tails = ix->tails();
-  p.tail_chunks = g.tail_chunks;
-  p.links = ix->d_links;
-  p.M = ix->M;
-  p.dim = ix->dim;
-  p.row_bytes = ix->row_bytes;
-  p.nchunks = g.nchunks;
-  p.K = K;
-  p.B = B;
-  p.q_chunks = g.q_chunks;
-  p.q_lds_bytes = cfg_query_in_regs(g.cfg) ? 0u : p.q_chunks * 16u;
-  p.cand_slots = ix->cand_slots ? (uint32_t)ix->cand_slots : (uint32_t)(ix->cand_factor * p.B + 192);
-  p.cand_slots = std::max<uint32_t>(p.cand_slots, (uint32_t)p.B + 1);  // also hosts the final result list
-  p.spill_entries = (uint32_t)ix->spill_entries;
-  p.bitmap_words = bitmap_words_of(ix);
-  p.ovf_cap = ovf_cap_of(ix);
-  p.log_entries = log_entries_for(ix, p.B);
-  plan.cfg = g.cfg;
-  plan.full = g.full;
-
-  // the exact two-heap kernel: always configured (it also replays what a merged-beam kernel hands over)
-  plan.heaps = p;
-  plan.kern = pick_kernel(ix->dtype, ix->metric, g.cfg, g.full);
-  int rc = configure_launch(ix, plan.heaps, plan.kern, MODE_HEAPS, &plan.lds, &plan.bpc);
-  if (rc) return rc;
-
-  // Merged-beam kernel (merged_beam.hpp): the beam as one sorted array, one merge per link row -- in registers for
-  // beams of at most 256 entries ("beam_registers" = 0: never), else in LDS; queries in which equal keys meet at a
-  // decision are searched again by the same wave with the exact two-heap code.  Same results.  "sorted_beam":
-  // 0 = never, 1 = always, 2 (default) = adaptive: measured against the two-heap kernel per beam width (below).
-  const bool tagged = plan.heaps.vis_tag16 != 0;
-  const bool want = ix->sorted_beam != 0 && B >= ix->sorted_beam_min && ix->capacity < (1ull << 31);
-  plan.mode = (!tagged || !want) ? MODE_HEAPS : (B <= MB_MAX_BEAM && ix->beam_registers != 0) ? MODE_MERGED_REGS : MODE_MERGED_LDS;
-  if (plan.mode != MODE_HEAPS) {
-    plan.skern = pick_sorted_kernel(ix->dtype, ix->metric, g.cfg, g.full, plan.mode == MODE_MERGED_LDS, B);
-    plan.skern_direct = pick_sorted_kernel(ix->dtype, ix->metric, g.cfg, g.full, plan.mode == MODE_MERGED_LDS, B, true);
-    // a layout that fnv_tune measured for this beam width overrides the rules below (heap home, table size)
-    fnv_index_s::LayoutChoice lc;
-    if (auto it = ix->layouts.find(B); it != ix->layouts.end()) lc = it->second;
-    const int64_t cand_lds_mode = lc.cand_lds >= 0 ? lc.cand_lds : ix->sorted_cand_lds;
-    const uint32_t forced = lc.vis_slots;
-    // the exact re-run's candidates heap: in LDS if that costs neither resident queries nor visited-table
-    // slots, else entirely in the slot's HBM spill area (slower for the few queries that need it)
-    SearchParams with = p, without = p;
-    without.cand_slots = 0;
-    uint32_t lds_w = 0, lds_wo = 0;
-    int bpc_w = 0, bpc_wo = 0;
-    rc = configure_launch(ix, without, plan.skern, plan.mode, &lds_wo, &bpc_wo, false, forced);
-    if (rc) return rc;
-    const int rc_w = configure_launch(ix, with, plan.skern, plan.mode, &lds_w, &bpc_w, false, forced);
-    // (an exact re-run whose candidates heap lives in HBM pays a global round trip per heap operation: a handful of
-    // such queries per launch are stragglers that cost 10 % of it -- measured at ef=100 on float data with 5 re-runs
-    // in 10 000 queries -- so up to beams of 128 the LDS home is worth going down to 9 resident queries; wider beams'
-    // heaps cost more LDS than the stragglers cost time)
-    bool keep_lds = rc_w == FNV_OK && (cand_lds_mode == 1 ||
-                                       (cand_lds_mode == 2 && ((bpc_w >= bpc_wo && with.vis_slots >= without.vis_slots) ||
-                                                               (B <= 2 * WAVE && bpc_w >= (int)ix->occupancy_roomy))));
-    // both candidates once more with the free table growth; an LDS home that costs residency AND table slots is not taken
-    SearchParams fin_w = p, fin_wo = p;
-    // (p's own heap size, not `with`'s: configure_launch may already have trimmed that one by up to an eighth to fit an LDS
-    //  granule, and the trim must be applied once, to the final layout)
-    fin_w.cand_slots = p.cand_slots;
-    fin_wo.cand_slots = 0u;
-    uint32_t flds_w = 0, flds_wo = 0;
-    int fbpc_w = 0, fbpc_wo = 0;
-    rc = configure_launch(ix, fin_wo, plan.skern, plan.mode, &flds_wo, &fbpc_wo, true, forced);
-    if (rc) return rc;
-    if (keep_lds) {
-      rc = configure_launch(ix, fin_w, plan.skern, plan.mode, &flds_w, &fbpc_w, true, forced);
-      if (rc) return rc;
-      if (cand_lds_mode == 2 && fin_w.vis_slots < fin_wo.vis_slots && fbpc_w < fbpc_wo) keep_lds = false;
-    }
-    plan.sorted = keep_lds ? fin_w : fin_wo;
-    plan.slds = keep_lds ? flds_w : flds_wo;
-    plan.sbpc = keep_lds ? fbpc_w : fbpc_wo;
-    if (!plan.sorted.vis_tag16) plan.mode = MODE_HEAPS;
-    if ((uint64_t)plan.sorted.cand_slots + plan.sorted.spill_entries < 3ull * (uint64_t)B + 256) plan.mode = MODE_HEAPS;
+  plan = PlannedLaunch();
+  const PlanRuntime rt{ix, row_geometry(ix), B};
+  LayoutChoice lc;  // a layout that fnv_tune measured for this beam width overrides the planner's rules (heap home, table size)
+  if (auto it = ix->layouts.find(B); it != ix->layouts.end()) lc = it->second;
+  std::string err;
+  const int rc = plan_launch(ix, B, K, lc, rt, err, plan);
+  if (rc) return fail(rc, err);
+  for (SearchParams* p : {&plan.heaps, &plan.sorted}) {
+    p->vectors = ix->d_vectors;
+    p->tails = ix->tails();
+    p->links = ix->d_links;
   }
-  plan.B = B;
-  plan.K = K;
-  plan.capacity = ix->capacity;
+  plan.kern = rt.kernel(MODE_HEAPS);
+  if (plan.mode != MODE_HEAPS) {
+    plan.skern = rt.kernel(plan.mode);
+    plan.skern_direct = rt.kernel(plan.mode, true);
+  }
   plan.options_version = ix->options_version;
   plan.valid = true;
   return FNV_OK;
 }
 
-// (b) Which kernel variant the launch runs, and whether it is a sample for the adaptive choice.
-struct KernelChoice {
-  bool sorted;  // the merged-beam kernel (else the two-heap kernel, or its filtered form)
-  int variant;
-  bool multi_round, sample = false, exploratory = false;
-  int64_t tail_pct;
-};
+// (b) Which kernel variant the launch runs, and whether it is a sample for the adaptive choice (KernelChoice and the rules
+// of each pick: launch_plan.hpp).
+// (tests/launch_plan_harness.cpp, lph_launch, repeats the pinned branch below and search_device_impl's choice of bpc / LDS bytes /
+// DIRECT form to shape launches on the CPU: a change here or there belongs in that twin as well)
 static KernelChoice choose_kernel(fnv_index_s* ix, int B, uint64_t nq, int force_variant, bool filtered) {
   const LaunchPlan& plan = ix->plan;
-  // Adaptive choice ("sorted_beam" = 2): both kernels give the same answers; which one is faster depends on how often
-  // equal keys force the merged-beam kernel to search a query twice (rarely on float data, often on integer-valued
-  // data with wide beams) -- so it is measured: launches of at least 2048 queries are timed by the events that bracket
-  // them anyway, harvested when a later call finds them complete, first one kernel, then the other, then the faster.
-  // A filtered launch always runs the two-heap kernel's filtered form: no merged beam, no samples for the adaptive choice
-  // (the tuner's measurements are left alone), no hand-over, tie log or shadows.
-  KernelChoice c;
-  c.sorted = plan.mode != MODE_HEAPS && !filtered;
-  c.variant = c.sorted ? 1 : 0;
-  // The merged-beam kernel's stragglers: a query that is searched twice finishes a whole exact-search latency late, and
-  // in the last round of a launch that lengthens the launch itself (one such query costs as much as hundreds).  With
-  // "sorted_tail_exact_pct" = p the last p % of one round of queries skip the sorted pass (the exact search is slower but
-  // never needs a second one): -15 % on the integer-valued SIFT stand-in at ef=52, +0-4 % on float data without ties --
-  // so by default (-1) it is one more variant that the adaptive choice measures.
-  const uint64_t round_slots = (uint64_t)plan.sbpc * (uint64_t)ix->num_cus;
-  c.multi_round = c.sorted && nq > round_slots;
-  c.tail_pct = ix->sorted_tail_exact_pct < 0 ? 0 : ix->sorted_tail_exact_pct;
+  KernelChoice c = default_choice(ix, plan, nq, filtered);  // (what the plan prefers; below: what was pinned or measured)
   const bool multi_round = c.multi_round;
   const int pinned = force_variant >= 0 ? force_variant : (int)ix->sorted_variant;  // fnv_tune / "sorted_variant"
   const bool shadows_on = ix->shadow_exact != 0;
   const bool try_tail = ix->sorted_tail_exact_pct < 0;
   if (c.sorted && pinned >= 0) {
-    c.variant = variant_allowed(pinned, multi_round, true, shadows_on, true) ? pinned : 1;
-    c.sorted = c.variant != 0;
-    if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
+    c.variant = pinned_variant(pinned, multi_round, shadows_on);
   } else if (c.sorted && ix->sorted_beam == 2 && ix->is_lane) {
     // a hidden lane runs what its owner has measured (copied by sync_lane) and never explores or samples: a production
     // caller that happens to land on a lane must not pay for 3 x variants exploratory launches per lane
-    if (nq >= 2048) {
-      if (auto it = ix->tuner.find(tuner_key(B, multi_round)); it != ix->tuner.end()) {
-        const fnv_index_s::Tuner& t = it->second;
-        int best = -1;
-        for (int v = 0; v < kNumVariants; v++)
-          if (variant_allowed(v, multi_round, try_tail, shadows_on) && t.samples[v] > 0 && (best < 0 || t.best[v] < t.best[best])) best = v;
-        if (best >= 0) c.variant = best;
-      }
-      c.sorted = c.variant != 0;
-      if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
-    }
+    if (auto it = ix->tuner.find(tuner_key(B, multi_round)); nq >= 2048 && it != ix->tuner.end())
+      if (const int best = lane_variant(it->second, multi_round, try_tail, shadows_on); best >= 0) c.variant = best;
   } else if (c.sorted && ix->sorted_beam == 2) {
     if (ix->sample_kernel >= 0 && ix->launched && hipEventQuery(ix->ev1) == hipSuccess) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) == hipSuccess && ms > 0.f) {
-        fnv_index_s::Tuner& t = ix->tuner[ix->sample_B];
+        Tuner& t = ix->tuner[ix->sample_B];
         const float per_q = ms / (float)ix->sample_nq;
         if (t.samples[ix->sample_kernel] == 0 || per_q < t.best[ix->sample_kernel]) t.best[ix->sample_kernel] = per_q;
         t.samples[ix->sample_kernel]++;
@@ -1313,25 +910,17 @@ static KernelChoice choose_kernel(fnv_index_s* ix, int B, uint64_t nq, int force
       ix->sample_kernel = -1;
     }
     if (nq >= 2048) {
-      fnv_index_s::Tuner& t = ix->tuner[tuner_key(B, multi_round)];
+      Tuner& t = ix->tuner[tuner_key(B, multi_round)];
       // three samples each (the first launch of a kernel is a cold one; the best of the rest decides), then the fastest
       // (fnv_tune takes all the samples in one call, so that no caller's launch is an exploratory one)
-      c.variant = -1;
-      for (int v : {1, 0, 6, 4, 3, 2, 5})
-        if (variant_allowed(v, multi_round, try_tail, shadows_on) && c.variant < 0 && t.samples[v] < 3) c.variant = v;
+      c.variant = owner_next_sample(t, multi_round, try_tail, shadows_on);
       c.exploratory = c.variant >= 0;
-      if (c.variant < 0) {
-        c.variant = 0;
-        for (int v = 1; v < kNumVariants; v++)
-          if (variant_allowed(v, multi_round, try_tail, shadows_on) && t.samples[v] > 0 &&
-              (t.best[v] < t.best[c.variant] || (v == 1 && t.best[1] <= t.best[0])))
-            c.variant = v;
-      }
+      if (c.variant < 0) c.variant = owner_final_variant(t, multi_round, try_tail, shadows_on);
       c.sample = t.samples[c.variant] < 4;
-      c.sorted = c.variant != 0;
-      if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
     }
   }
+  c.sorted = c.variant != 0;  // (unchanged where nothing was pinned or measured: variant 1 of a merged-beam plan, else 0)
+  if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
   return c;
 }
 
@@ -1356,37 +945,7 @@ static int grow_workspace(fnv_index_s* ix, uint32_t max_slots, uint64_t nq, bool
   return rc;
 }
 
-// (d) Small launches on small indexes (round 5): when a bitmap of ALL node ids fits the LDS of the slots the launch needs, the
-// visited set is that bitmap (csrc/visited.hpp visited_insert_direct: one LDS round trip per link row, nothing overflows)
-// instead of the tag table, and the launch runs the kernel's DIRECT instantiation -- a launch that leaves the GPU mostly idle
-// is a chain of dependent latencies, and the tag table is 1.8 k of a lone hop's 7.9 k cycles.  The table is the last but
-// two of the slot's LDS areas: only what follows it moves.
-// Only in launches that fill at most a quarter of the slots, and not when the caller has pinned the table's shape
-// ("visited_slots", "visited_tag_bits", "visited_wide"); "visited_direct" = 0 turns it off.
-static bool lay_out_direct(const fnv_index_s* ix, SearchParams& p, uint32_t* lds_bytes, int bpc, uint32_t nslots) {
-  if (ix->visited_direct == 0 || ix->visited_slots != 0 || ix->visited_tag_bits != 0 || ix->visited_wide != 0 || !p.vis_tag16) return false;
-  const uint64_t ids = std::max<uint64_t>(ix->capacity, ix->parent ? ix->parent->capacity : 0);
-  const uint64_t bytes = ((ids + 7) / 8 + 15) / 16 * 16;
-  auto align16 = [](uint32_t v) { return (v + 15u) & ~15u; };
-  if (bytes + p.off_vis + 1024 <= kLdsPerCu) {
-    SearchParams d = p;
-    d.vis_w = 1;
-    d.vis_bytes = (uint32_t)bytes;
-    d.vis_slots = (uint32_t)(bytes * 8);  // (what fnv_last_launch_geometry reports: one slot per node id)
-    uint32_t off = align16(d.off_vis + d.vis_bytes);
-    d.off_stage_ids = off;
-    off = align16(off + (WAVE + 1) * 4);
-    d.off_ovf = off;
-    off = align16(off + (OVF_LIST + 2 + STASH) * 4);
-    const uint64_t per_cu = std::min<uint64_t>((uint64_t)bpc, kLdsPerCu / lds_allocated(off));
-    if (off <= kLdsPerCu && (uint64_t)nslots <= per_cu * (uint64_t)ix->num_cus) {
-      p = d;
-      *lds_bytes = off;
-      return true;
-    }
-  }
-  return false;
-}
+// (d) Small launches on small indexes run the kernel's DIRECT form on a bitmap of all node ids: lay_out_direct (launch_plan.hpp).
 
 static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
                               const SearchOutputs& out, void* hip_stream, const SearchOptions& opt) {
@@ -1405,7 +964,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   const int B = std::max(ef_search, K);  // Index.h:392
   int rc = ensure_plan(ix, B, K);
   if (rc) return rc;
-  LaunchPlan& plan = ix->plan;
+  PlannedLaunch& plan = ix->plan;
   if (filter && !plan.fkern) {
     plan.fkern = pick_filtered_kernel(ix->dtype, ix->metric, plan.cfg, plan.full);
     HIP_TRY(raise_lds_limit((const void*)plan.fkern, ix->device, plan.lds));
@@ -1417,19 +976,13 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   const bool sorted = c.sorted;
   const int bpc = sorted ? plan.sbpc : opt.filter ? plan.fbpc : plan.bpc;
   uint32_t lds_bytes = sorted ? plan.slds : plan.lds;
-  // Shadow mode (search_params.h): a launch that fills at most a quarter of the resident slots starts, next to the
-  // merged-beam search of every query, an exact search of the same query on another slot.  A query in which equal keys
-  // meet at a decision is then answered after ONE exact-search latency from the start of the launch instead of a
-  // merged-beam pass plus a re-run (batch of 64 at ef=100 on the integer-valued data: p50 0.80 -> 0.47 ms); the shadow of
-  // a query that needs none stops at its next hop.  Same bytes either way.
-  const bool small_launch = 4 * nq <= (uint64_t)bpc * (uint64_t)ix->num_cus;
-  const bool shadow = sorted && ix->shadow_exact != 0 && small_launch;
-  const uint32_t nslots = shadow ? (uint32_t)(2 * nq) : (uint32_t)std::min<uint64_t>(nq, (uint64_t)bpc * (uint64_t)ix->num_cus);
-  // Tail shadows (variant 6, search_params.h): one exact shadow per slot at most -- of the queries dispensed last
-  const uint32_t tail_shadows = (sorted && !shadow && c.variant == kVariantTailShadows) ? (uint32_t)std::min<uint64_t>(nq, nslots) : 0u;
-  const uint32_t max_slots = std::max<uint32_t>(nslots, (uint32_t)std::min<uint64_t>(nq, (uint64_t)std::max(plan.bpc, plan.sbpc) * (uint64_t)ix->num_cus));
+  // (shadow mode, tail shadows, the grid: launch_shape, launch_plan.hpp)
+  const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
+  const LaunchShape shape = launch_shape(ix, plan, c, bpc, nq, num_initializations, live);
+  const bool small_launch = shape.small_launch, shadow = shape.shadow;
+  const uint32_t nslots = shape.nslots, tail_shadows = shape.tail_shadows;
 
-  rc = grow_workspace(ix, max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr);
+  rc = grow_workspace(ix, shape.max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr);
   if (rc) return rc;
 
   SearchParams p = sorted ? plan.sorted : plan.heaps;
@@ -1443,14 +996,10 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   p.out_count = out.count;
   p.out_ndist = out.ndist;
   p.out_nhops = out.nhops;
-  const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
   p.n_nodes = live;
   p.nq = (uint32_t)nq;
-  // Index.h:851-861: step = max(1, N / n_init); nodes 0, step, 2*step, ... < N
-  uint64_t step = live / (uint64_t)num_initializations;
-  if (step == 0) step = 1;
-  p.scan_step = (uint32_t)step;
-  p.n_scan = (uint32_t)((live + step - 1) / step);
+  p.scan_step = shape.scan_step;  // Index.h:851-861
+  p.n_scan = shape.n_scan;
   p.ovf_bitmap = ix->ws.bitmap.as<uint32_t>();
   p.ovf_glist = ix->ws.ovf.as<uint32_t>();
   p.cand_spill = ix->ws.spill.as<unsigned long long>();
@@ -1461,7 +1010,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   p.host_status = opt.host_status;
   p.redo_count = ix->d_dispenser + 3;  // [3] queries searched exactly after a tie, [4..7] by reason
   p.phase_cycles = ix->d_phase;
-  p.tail_exact = c.multi_round && sorted ? (uint32_t)std::min<uint64_t>((uint64_t)c.tail_pct * nslots / 100, nq) : 0u;
+  p.tail_exact = shape.tail_exact;
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));
   if (filter) {  // the label bitmap -> this handle's node bitmap (labels as they are now: after reorder(), device builds ...)
@@ -2088,42 +1637,15 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
   // table one size up / down -- with the merged-beam kernel alone and with its whole last round straight to the exact
   // search, and keeps the fastest.  Skipped for whatever the caller pinned with an option.
   // (from the plan, not from the probing launch's geometry record: a DIRECT launch reports its bitmap's bits there)
-  uint32_t base_slots = 0;
+  uint32_t base_slots = 0, base_vis_w = 0;
   bool base_heap_lds = false;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
     base_slots = ix->plan.sorted.vis_slots;
+    base_vis_w = ix->plan.sorted.vis_w;
     base_heap_lds = ix->plan.sorted.cand_slots != 0;
   }
-  std::vector<fnv_index_s::LayoutChoice> cands(1);  // [0]: the rules
-  if (ix->tune_layout && ix->sorted_cand_lds == 2) {
-    fnv_index_s::LayoutChoice c;
-    c.cand_lds = base_heap_lds ? 0 : 1;
-    cands.push_back(c);
-  }
-  if (ix->tune_layout && ix->visited_slots == 0 && base_slots >= 512) {
-    const bool pow2 = (base_slots & (base_slots - 1)) == 0;
-    const uint32_t up = pow2 ? base_slots / 2 * 3 : base_slots / 3 * 4, down = pow2 ? base_slots / 4 * 3 : base_slots / 3 * 2;
-    // ... and two sizes up (round 5): beyond 2^24 nodes the tag format alternates with the size -- three 21-bit tags per
-    // 8-byte bucket at 3 * 2^j slots, two 32-bit tags at 2^j -- so one size up from 3072 slots (4096: same bytes as 6144, a
-    // third fewer tags) is a step DOWN in tags per byte and hides the layout that is 18 % faster on 50M x 128 Gaussian rows
-    // (6144 slots at 8 queries per CU: 3.06 ms against the rules' 3072 slots at 12 per CU: 3.74 ms; profiles/r5_table_sizes_50m.txt)
-    // (only where tags are wide: with 16-bit tags every size has the same format and the neighbours above suffice)
-    const uint32_t up2 = ix->plan.sorted.vis_w != 16u ? base_slots * 2 : 0u;  // 3 * 2^j -> 3 * 2^(j+1): the same tag format
-    // (two sizes DOWN was measured in round 6 and is not a candidate: on 50M x 128 uint8 -- 128-byte rows, 12 resident queries
-    //  per CU -- 1536 slots keep 18-20 queries resident and are 32-48 % SLOWER than 3072 slots at 12: what a smaller table sends
-    //  to the HBM bitmap costs more than the queries in flight it buys; profiles/r6_table_sizes_50m_uint8.txt)
-    for (uint32_t slots : {up, down, up2}) {
-      if (slots < 256 || slots > (1u << 15)) continue;
-      fnv_index_s::LayoutChoice c;
-      c.vis_slots = slots;
-      cands.push_back(c);
-      if (ix->sorted_cand_lds == 2) {
-        c.cand_lds = base_heap_lds ? 0 : 1;
-        cands.push_back(c);
-      }
-    }
-  }
+  const std::vector<LayoutChoice> cands = tune_layout_candidates(ix, base_slots, base_vis_w, base_heap_lds);
   const bool tune_log = getenv("FLATNAV_TUNE_LOG") != nullptr;  // developer aid: every measurement on stderr
   size_t best_layout = 0;
   float best_layout_t = -1.f;
@@ -2213,7 +1735,7 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
 
   // ---- 2. the kernel variant on that layout --------------------------------------------------------------------------
   const bool multi_round = nq > (uint64_t)ix->plan.sbpc * (uint64_t)ix->num_cus;
-  fnv_index_s::Tuner t;
+  Tuner t;
   for (int v = 0; v < kNumVariants; v++) {
     if (!variant_allowed(v, multi_round, ix->sorted_tail_exact_pct < 0, ix->shadow_exact != 0)) continue;
     rc = time_variant(v, 4, &t.best[v]);

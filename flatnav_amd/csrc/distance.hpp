@@ -1,4 +1,4 @@
-// distance.hpp -- part of the gfx950 search engine (device code; included only by beam_search.hip).
+// distance.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
 // Cross-lane reductions, per-chunk distance arithmetic and the batched gather/distance primitive.
 #pragma once
 #include "search_params.h"

@@ -1,4 +1,4 @@
-// kernels.hpp -- part of the gfx950 search engine (device code; included only by beam_search.hip).
+// kernels.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
 // Entry-point scan, the K0 batch kernel, the exact (two-heap) search of one query and its kernel.
 #pragma once
 #include "distance.hpp"
@@ -347,7 +347,7 @@ struct ExactResume {
   bool ovf;
 };
 
-// `stop` (null: never) = a word another wavefront sets once the same query has been answered (shadow mode, search_params.h):
+// `stop` (null: never) = a word another wavefront sets once the same query has been answered (shadow mode, search_types.h):
 // polled once per hop; the search then gives up -- no results written, per-slot state left clean.
 // `resumed` (false: a search from scratch): heaps, visited set and counters come from a replayed log (`rs`); the search starts
 // at the loop head.  (A run-time flag, not a template parameter: the merged-beam kernel inlines this function ONCE for both;

@@ -1,4 +1,4 @@
-// merged_beam.hpp -- part of the gfx950 search engine (device code; included only by beam_search.hip / kernel_inst.hip).
+// merged_beam.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units; by beam_search.hip in developer builds).
 //
 // beam_search_merged_kernel -- the default search kernel: the same traversal as beam_search_kernel (the libstdc++-exact
 // two-heap kernel) with the beam held as ONE SORTED ARRAY of at most B entries -- closest first, an "expanded" flag
@@ -109,7 +109,7 @@ __device__ __forceinline__ float lane_of(const float (&a)[R], int r, int l) {
 }
 
 // DIRECT (round 5): the instantiations that small launches on small indexes run -- the visited set is a bitmap of all node ids
-// in LDS (visited.hpp visited_insert_direct; search_params.h vis_w == 1), the tag-table code is compiled out.
+// in LDS (visited.hpp visited_insert_direct; search_types.h vis_w == 1), the tag-table code is compiled out.
 template <typename T, int METRIC, int G, int CU, bool FULL, int R, bool DIRECT = false>
 __global__ __launch_bounds__(WAVE, CU == 1 ? 5 : R == MB_R ? 3 : waves_per_simd<G>(FNV_SORTED_WAVES_PER_SIMD)) void beam_search_merged_kernel(const SearchParams p) {
   // (128-byte rows: 97 registers as compiled for four waves per SIMD -- one over the budget of five, which they fit.
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(WAVE, CU == 1 ? 5 : R == MB_R ? 3 : waves_per_simd<
 #ifdef FNV_TIMELINE  // developer build (tools/dev/launch_timeline.py): the per-query counters carry start / end clock readings instead
     const unsigned long long tl_start = wall_clock64();
 #endif
-    // shadows (search_params.h): items >= shadow_base are exact searches of the LAST queries, most recent first
+    // shadows (search_types.h): items >= shadow_base are exact searches of the LAST queries, most recent first
     const uint32_t shadow_base = cold_args()->shadow_base;
     const bool shadow = shadow_base != 0u && (uint32_t)item >= shadow_base;
     const int qi = shadow ? 2 * (int)shadow_base - 1 - item : item;

@@ -1,4 +1,4 @@
-// visited.hpp -- part of the gfx950 search engine (device code; included only by beam_search.hip).
+// visited.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
 // Exact visited sets in LDS (32-bit open addressing and the 16-bit-tag bucketed table).
 #pragma once
 #include "search_params.h"
@@ -56,7 +56,7 @@ __device__ __forceinline__ void tag16_slot(const VisGeom& g, uint32_t h, uint32_
   tag = (rem << 1) + 1u + which;
 }
 
-// The stash (search_params.h): lanes whose id found both its buckets full come here before the HBM bitmap (a wave-uniform
+// The stash (search_types.h): lanes whose id found both its buckets full come here before the HBM bitmap (a wave-uniform
 // branch around the call: rare).  A second, tiny table of FULL ids: STASH / 4 buckets of four (one 16-byte LDS read), the
 // bucket chosen by a third hash; an id is looked up in its bucket, else put into the bucket's first free word (stored as
 // id + 1, 0 = free), else -- bucket full -- left to the bitmap.  Nothing is ever removed, so "its stash bucket is full ->
@@ -247,7 +247,7 @@ __device__ __forceinline__ bool visited_insert_tagw(unsigned long long* tab, con
   return isnew != 0u;
 }
 
-// Round 5, small launches on small indexes (search_params.h, vis_w == 1): the visited set is a plain bitmap of ALL node ids in
+// Round 5, small launches on small indexes (search_types.h, vis_w == 1): the visited set is a plain bitmap of ALL node ids in
 // LDS -- one atomic OR with return per id: a single LDS round trip, nothing to overflow, no stash, no HBM bitmap.  (A lone wave
 // spends 1.8 k of its hop's 7.9 k cycles in the tag table: profiles/r5_phase_cycles_c2.txt.)
 __device__ __forceinline__ bool visited_insert_direct(uint32_t* tab, bool act, uint32_t id) {
