@@ -2,8 +2,9 @@
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container as well as on the MI355X box.
 The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 88
-objects (kernel_inst.hip: 11 kernel families x 4 element types x 2 metrics) in parallel, plus beam_search.hip (host
-code, C ABI, re-layout kernels), and linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
+objects (kernel_inst.hip: 11 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
+half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), plus beam_search.hip (host code, C ABI, re-layout kernels), and
+linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
                                            "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "relayout.hpp",
-                                           "launch_plan.hpp")] + [
+                                           "launch_plan.hpp", "half_rows.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
 MAIN = os.path.join(CSRC, "beam_search.hip")
 INST = os.path.join(CSRC, "kernel_inst.hip")
@@ -29,6 +30,9 @@ METRICS = [(0, "l2"), (1, "ip")]
 FAMILIES = [(0, "exact"), (3, "wire"), (4, "merged"), (5, "merged1"), (6, "merged0"), (7, "merged2"),
             (8, "merged_d"), (9, "merged1_d"), (10, "merged0_d"), (11, "merged2_d"),  # 8-11: the DIRECT forms (small launches)
             (12, "exact_f")]  # the filtered two-heap kernel
+# the row format f32h (csrc/half_rows.hpp; kernel_table.h's FNV_FOR_EACH_HALF_ROWS_FAMILY): the families that read mirror rows
+HALF_ROWS_TYPE = ("fnv_dev::f32h", "f32h")
+HALF_ROWS_FAMILIES = [f for f in FAMILIES if f[0] == 0 or 4 <= f[0] <= 11]  # exact, merged beam and its DIRECT forms
 
 
 def hipcc() -> str:
@@ -41,12 +45,13 @@ def hipcc() -> str:
 def _units(defines):
     """(object path, source, extra -D flags) for every translation unit."""
     units = [(os.path.join(OBJ, "beam_search.o"), MAIN, [])]
-    for ctype, tag in TYPES:
+    for (ctype, tag), families, extra in [(t, FAMILIES, []) for t in TYPES] + [(HALF_ROWS_TYPE, HALF_ROWS_FAMILIES,
+                                                                                 ["-DFNV_INST_HALF_ROWS"])]:
         for metric, mtag in METRICS:
-            for fam, fname in FAMILIES:
+            for fam, fname in families:
                 units.append((os.path.join(OBJ, "inst_%s_%s_%s.o" % (fname, tag, mtag)), INST,
                               ["-DFNV_INST_T=" + ctype, "-DFNV_INST_TAG=" + tag, "-DFNV_INST_METRIC=%d" % metric,
-                               "-DFNV_INST_MTAG=" + mtag, "-DFNV_INST_FAMILY=%d" % fam, "-DFNV_INST_FNAME=" + fname]))
+                               "-DFNV_INST_MTAG=" + mtag, "-DFNV_INST_FAMILY=%d" % fam, "-DFNV_INST_FNAME=" + fname] + extra))
     return [(o, s, f + ["-D" + d for d in defines]) for o, s, f in units]
 
 

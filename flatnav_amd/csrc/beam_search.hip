@@ -132,7 +132,8 @@ hipError_t raise_lds_limit(const void* kern, int device, uint32_t bytes) {
 #define FNV_DEV_METRIC FNV_METRIC_L2
 #endif
 #define FNV_DEV_KERNEL(K, ...) K<FNV_DEV_T, FNV_DEV_METRIC, FNV_DEV_G, FNV_DEV_CU, true __VA_ARGS__>
-const KernelTable& kernel_table(int, int) {
+constexpr bool kHalfRowsBuilt = false;  // (one instantiation per kernel: no mirror-row kernels)
+const KernelTable& kernel_table(int, int, bool = false) {
   static KernelTable t = [] {
     KernelTable k;
     const kernel_fn merged[kNumBeamForms][2] = {
@@ -157,8 +158,11 @@ const KernelTable& kernel_table(int, int) {
 #undef FNV_DEV_KERNEL
 #else
 // Product builds: the instantiations live in kernel_inst.hip objects (one per family x element type x metric).
-const KernelTable& kernel_table(int dtype, int metric) {
-  static KernelTable tables[8];
+// `half_rows`: the tables of the row format f32h (float32 queries on mirror rows, half_rows.hpp; float32 indexes only) -- the
+// exact and merged-beam kernels of the row configurations a mirror exists for, null everywhere else.
+constexpr bool kHalfRowsBuilt = true;
+const KernelTable& kernel_table(int dtype, int metric, bool half_rows = false) {
+  static KernelTable tables[10];  // (static: zero-initialised -- the slots no filler writes are null)
   static std::once_flag once;
   std::call_once(once, [] {
     int i = 0;
@@ -168,8 +172,14 @@ const KernelTable& kernel_table(int dtype, int metric) {
     i++;
     FNV_FOR_EACH_TYPE_METRIC(FNV_FILL)
 #undef FNV_FILL
+#define FNV_FILL(M, mtag)                                          \
+    FNV_FOR_EACH_HALF_ROWS_FAMILY(FNV_FILL_FAMILY, f32h, mtag) \
+    i++;
+    FNV_FOR_EACH_HALF_ROWS_METRIC(FNV_FILL)
+#undef FNV_FILL
 #undef FNV_FILL_FAMILY
   });
+  if (half_rows) return tables[8 + (metric == FNV_METRIC_IP ? 1 : 0)];
   int t;  // order of FNV_FOR_EACH_TYPE_METRIC; every caller has passed validate_geometry (dtype_size != 0)
   switch (dtype) {
     case FNV_DTYPE_FLOAT32: t = 0; break;
@@ -182,23 +192,28 @@ const KernelTable& kernel_table(int dtype, int metric) {
 }
 #endif
 
-kernel_fn pick_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).exact[cfg][full]; }
-kernel_fn pick_filtered_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).exact_f[cfg][full]; }
 kernel_fn pick_scan_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).scan[cfg][full]; }
-kernel_fn pick_sorted_kernel(int dtype, int metric, int cfg, bool full, bool lds, int B, bool direct = false) {
-  return kernel_table(dtype, metric).merged[beam_form(lds, B)][direct][cfg][full];
-}
 wire_fn pick_wire_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).select[cfg][full]; }
 wire_fn pick_connect_kernel(int dtype, int metric, int cfg, bool full) { return kernel_table(dtype, metric).connect[cfg][full]; }
 
 }  // namespace
 
 // The cached launch plan of a handle (launch_plan.hpp) and the kernels that run it.
+// A search kernel TOGETHER WITH the vector table it reads (bind_search_kernel is the only place that makes one): a launch
+// takes the function and `vectors` / `row_bytes` of its parameter block from the same BoundKernel, so a float32 kernel on
+// mirror rows -- or the reverse, either of which reads out of bounds -- cannot be written down.
+struct BoundKernel {
+  kernel_fn fn = nullptr;
+  const uint8_t* rows = nullptr;  // what SearchParams::vectors must be for fn
+  uint32_t stride = 0;            // ... and SearchParams::row_bytes
+  bool half_rows = false;         // fn reads the half-width mirror
+};
 struct PlannedLaunch : LaunchPlan {
-  kernel_fn kern = nullptr, skern = nullptr;  // exact two-heap kernel; merged-beam kernel (mode != 0)
-  kernel_fn skern_direct = nullptr;           // ... its DIRECT form (small launches on small indexes)
-  kernel_fn fkern = nullptr;  // filtered search: the two-heap kernel's filtered form on the `heaps` layout (set at first use)
+  BoundKernel kern, skern;    // exact two-heap kernel; merged-beam kernel (mode != 0)
+  BoundKernel skern_direct;   // ... its DIRECT form (small launches on small indexes)
+  BoundKernel fkern;          // filtered search: the two-heap kernel's filtered form on the `heaps` layout (set at first use)
   int fbpc = 0;               // ... and the slots one CU keeps resident with it
+  bool half_rows = false;     // planned for the half-width mirror (another kernel: its own occupancy, its own measurements)
 };
 
 // Filtered search (fnv_search_batch_filtered*): the caller's bitmap over label values, in device memory.
@@ -295,6 +310,18 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
   std::atomic<uint64_t> n_nodes{0};  // live nodes: what a search sees (entry scan, id range); a view reads its source's at
                                      // every launch while the source may be growing -> atomic
   uint8_t* d_vectors = nullptr;
+  // The half-width mirror of a float32 table (half_rows.hpp): an allocation of its own, kept by the handle that
+  // made it (the owner of the buffers, or an adopted handle after fnv_index_build_half_rows).  Views and hidden lanes read
+  // their source's at every launch, as they read n_nodes -> atomics; `rows` is published before `state` turns HALF_LIVE.
+  struct HalfRows {
+    std::atomic<uint8_t*> rows{nullptr};  // [capacity][row_bytes / 2]
+    std::atomic<int> state{HALF_NONE};
+    std::atomic<uint64_t> covered{0};     // rows [0, covered) are converted (a contiguous watermark from row 0)
+    std::atomic<size_t> bytes{0};
+    bool off = false;                     // FLATNAV_HALF_ROWS=0 when the handle was made: never built
+  } half;
+  int measured_half = -1;  // tuner / layouts hold measurements of launches with (1) / without (0) the mirror; -1: none yet
+  bool last_half = false;  // the most recent launch read the mirror
   uint32_t* d_links = nullptr;
   int32_t* d_labels = nullptr;
   std::string gcn_arch;  // hipDeviceProp_t::gcnArchName: replicas on the same GPU model inherit the source's measurements
@@ -328,7 +355,8 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
   DeviceBuf d_nodebits;   // uint32, filtered search: [capacity / 32] words, bit per node id (node_filter_kernel)
   DeviceBuf d_allowed;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM
   DeviceBuf d_wirebuf;    // fnv_index_insert_batch: [count*keep] x {req_target, req_index, sorted_target, sorted_req} | sort scratch
-  DeviceBuf d_nodestage;  // write_nodes: AoS staging chunk + bad flag
+  DeviceBuf d_nodestage;  // write_nodes: AoS staging chunk + bad flag + "not lossless" flag of the mirror's conversion
+  DeviceBuf d_halfflag;   // fnv_index_build_half_rows: the conversion's "not lossless" flag
   DeviceBuf d_linkstage;  // fnv_index_write_links: [count] ids | [count][M] rows | bad flag
   // staging for the host-buffer entry point
   DeviceBuf d_q, d_out;
@@ -385,6 +413,7 @@ int index_common_init(fnv_index_s* ix) {
     ix->lane_budget_bytes = total_b / 8;
     if (const char* env = getenv("FLATNAV_LANE_BUDGET_MB")) ix->lane_budget_bytes = (size_t)strtoull(env, nullptr, 10) << 20;
   }
+  if (const char* env = getenv("FLATNAV_HALF_ROWS")) ix->half.off = env[0] == '0';
   HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreate(&ix->ev0));
   HIP_TRY(hipEventCreate(&ix->ev1));
@@ -413,8 +442,78 @@ int alloc_buffers(fnv_index_s* ix) {  // the caller is on ix->device
   return index_common_init(ix);
 }
 
+// ---- the half-width mirror (half_rows.hpp) ---------------------------------------------------------------------
+// The handle whose mirror a launch on `ix` reads: a view's / hidden lane's source, else the handle itself.
+const fnv_index_s* rows_source(const fnv_index_s* ix) { return ix->parent ? ix->parent : ix; }
+// Whether this handle's rows can have one at all: float32 rows of an eligible geometry, in a build that has the kernels.
+bool half_rows_possible(const fnv_index_s* ix) {
+  return kHalfRowsBuilt && !ix->half.off && half_rows_eligible(ix->dtype, row_geometry(ix));
+}
+// The mirror is given up: searches stop using it at their next launch.  The memory goes back at once unless a view (or hidden
+// lane) may be launching on it this very moment -- then it stays until the handle is freed.  The caller is on ix->device.
+void half_rows_drop(fnv_index_s* ix) {
+  fnv_index_s::HalfRows& h = ix->half;
+  h.state = HALF_DROPPED;
+  h.covered = 0;
+  if (h.rows.load() && ix->n_views.load() == 0) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(h.rows.load());
+    h.rows = nullptr;
+    h.bytes = 0;
+  }
+}
+// Room for the mirror of every row the buffers hold.  A failed allocation is not an error: there is no mirror then.
+bool half_rows_allocate(fnv_index_s* ix) {
+  fnv_index_s::HalfRows& h = ix->half;
+  if (h.rows.load()) return true;
+  void* p = nullptr;
+  const size_t bytes = (size_t)ix->capacity * (ix->row_bytes / 2);
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  h.rows = (uint8_t*)p;
+  h.bytes = bytes;
+  return true;
+}
+// Converts rows [first, first + count) of d_vectors into the mirror on the null stream; *d_lossy is ORed.  The caller waits.
+void half_rows_convert(fnv_index_s* ix, uint64_t first, uint64_t count, int* d_lossy) {
+  const RowGeometry g = row_geometry(ix);
+  const uint64_t units = count * (ix->row_bytes / 32);
+  hipLaunchKernelGGL(half_rows_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, 0, ix->d_vectors, ix->row_bytes, first,
+                     count, (uint32_t)kCfgs[g.cfg].G, (uint32_t)kCfgs[g.cfg].CU, ix->half.rows.load(), d_lossy);
+}
+// (Re)builds the mirror of rows [0, n_live) from d_vectors; the caller holds ix->mu and is on ix->device.  *built: a live mirror resulted.
+int half_rows_build(fnv_index_s* ix, int* built) {
+  *built = 0;
+  if (ix->parent) return fail(FNV_ERR_INVALID, "fnv_index_build_half_rows: call it on the view's source (a view reads its source's mirror)");
+  if (!half_rows_possible(ix)) return FNV_OK;
+  const uint64_t live = ix->n_nodes.load();
+  if (!half_rows_allocate(ix)) {
+    half_rows_drop(ix);
+    return FNV_OK;
+  }
+  int rc = ix->d_halfflag.grow(16);
+  if (rc) return rc;
+  HIP_TRY(hipMemset(ix->d_halfflag.ptr, 0, sizeof(int)));
+  half_rows_convert(ix, 0, live, ix->d_halfflag.as<int>());
+  HIP_TRY(hipGetLastError());
+  int lossy = 0;
+  HIP_TRY(hipMemcpy(&lossy, ix->d_halfflag.ptr, sizeof(int), hipMemcpyDeviceToHost));  // (waits for the null stream)
+  if (lossy) {
+    half_rows_drop(ix);
+    return FNV_OK;
+  }
+  ix->half.covered = live;
+  ix->half.state = HALF_LIVE;
+  *built = 1;
+  return FNV_OK;
+}
+
 // Copy AoS node records [data][M links][label] (reference Index.h:61-63) for nodes first..first+count-1 into the
 // SoA device buffers, 256 MB at a time.  Link ids >= id_limit are flagged (and replaced by a self-loop).
+// The half-width mirror follows the rows written here: converted chunk by chunk right behind the re-layout while the writes
+// stay contiguous from row 0 and every value is lossless; a gap, a lossy value or a failed allocation ends it for good.
 int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes, const void* aos_rows,
                      uint64_t node_size, uint64_t data_size, uint64_t id_limit, int* bad_out) {
   ON_DEVICE(ix->device);
@@ -424,8 +523,19 @@ int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes,
   int rcg = ix->d_nodestage.grow(need);
   if (rcg) return rcg;
   uint8_t* d_stage = ix->d_nodestage.as<uint8_t>();
-  int* d_bad = (int*)(d_stage + (need - 16));
-  HIP_TRY(hipMemset(d_bad, 0, sizeof(int)));
+  int* d_bad = (int*)(d_stage + (need - 16));  // [0] bad link ids, [1] the mirror's "not lossless" flag
+  HIP_TRY(hipMemset(d_bad, 0, 2 * sizeof(int)));
+  bool mirror = false;  // this call converts what it writes
+  if (ix->parent) {     // written through a view: its source's mirror no longer matches the rows (the memory stays the source's)
+    if (ix->parent->half.state.load() == HALF_LIVE) ix->parent->half.state = HALF_DROPPED;
+  } else if (half_rows_possible(ix) && ix->half.state.load() != HALF_DROPPED) {
+    fnv_index_s::HalfRows& h = ix->half;
+    if (first_node > h.covered.load()) half_rows_drop(ix);  // a gap: the rows before it came from somewhere the library did not see
+    else if (ix->owns_buffers || h.rows.load()) {           // (an adopted handle only keeps up a mirror it was asked to build)
+      mirror = half_rows_allocate(ix);
+      if (!mirror) half_rows_drop(ix);
+    }
+  }
   const int word_ok = (node_size % 4 == 0 && data_size % 4 == 0) ? 1 : 0;
   for (uint64_t done = 0; done < count_nodes; done += chunk_nodes) {
     const uint64_t count = std::min(chunk_nodes, count_nodes - done);
@@ -436,12 +546,28 @@ int write_nodes_impl(fnv_index_s* ix, uint64_t first_node, uint64_t count_nodes,
     hipLaunchKernelGGL(relayout_vectors_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, 0, d_stage,
                        node_size, data_size, ix->row_bytes, ix->tail_bytes, first, count, ix->d_vectors,
                        const_cast<uint8_t*>(ix->tails()), word_ok);
+    if (mirror) half_rows_convert(ix, first, count, d_bad + 1);
     hipLaunchKernelGGL(relayout_links_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, d_stage,
                        node_size, data_size, ix->M, first, count, id_limit, ix->d_links, ix->d_labels, d_bad);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
+    if (mirror) {  // a lossy value ends the mirror at once: the chunks that follow are not converted for nothing
+      int lossy = 0;
+      HIP_TRY(hipMemcpy(&lossy, d_bad + 1, sizeof(int), hipMemcpyDeviceToHost));
+      if (lossy) {
+        half_rows_drop(ix);
+        mirror = false;
+      }
+    }
   }
-  HIP_TRY(hipMemcpy(bad_out, d_bad, sizeof(int), hipMemcpyDeviceToHost));
+  int flags[2] = {0, 0};
+  HIP_TRY(hipMemcpy(flags, d_bad, sizeof(flags), hipMemcpyDeviceToHost));
+  *bad_out = flags[0];
+  if (mirror && flags[1]) half_rows_drop(ix);
+  else if (mirror) {
+    ix->half.covered = std::max<uint64_t>(ix->half.covered.load(), first_node + count_nodes);
+    ix->half.state = HALF_LIVE;
+  }
   return FNV_OK;
 }
 
@@ -613,7 +739,7 @@ int fnv_index_info(fnv_index_t ix, uint64_t info[8]) {
   info[4] = ix->dim;
   info[5] = (uint64_t)ix->metric;
   info[6] = (uint64_t)ix->device;
-  info[7] = ix->capacity * ((uint64_t)ix->row_bytes + ix->tail_bytes + 4ull * ix->M + 4) + ix->ws.bitmap.bytes + ix->ws.spill.bytes;
+  info[7] = ix->capacity * ((uint64_t)ix->row_bytes + ix->tail_bytes + 4ull * ix->M + 4) + ix->ws.bitmap.bytes + ix->ws.spill.bytes + ix->half.bytes.load();
   return FNV_OK;
 }
 
@@ -629,13 +755,35 @@ int fnv_index_free(fnv_index_t ix) {
   if (ix->stream) (void)hipStreamSynchronize(ix->stream);
   if (ix->parent) ix->parent->n_views.fetch_sub(1);
   if (!ix->owns_buffers) ix->d_vectors = nullptr, ix->d_links = nullptr, ix->d_labels = nullptr;
-  for (void* b : {(void*)ix->d_vectors, (void*)ix->d_links, (void*)ix->d_labels, (void*)ix->d_dispenser, (void*)ix->d_phase})
+  for (void* b : {(void*)ix->half.rows.load(), (void*)ix->d_vectors, (void*)ix->d_links, (void*)ix->d_labels, (void*)ix->d_dispenser, (void*)ix->d_phase})
     if (b) (void)hipFree(b);
   if (ix->h_pin) (void)hipHostFree(ix->h_pin);
   if (ix->ev0) (void)hipEventDestroy(ix->ev0);
   if (ix->ev1) (void)hipEventDestroy(ix->ev1);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
   delete ix;  // (every DeviceBuf frees itself)
+  return FNV_OK;
+}
+
+int fnv_index_build_half_rows(fnv_index_t ix, int* built) {
+  if (!ix) return fail(FNV_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(ix->mu);
+  ON_DEVICE(ix->device);
+  int made = 0;
+  const int rc = half_rows_build(ix, &made);
+  if (built) *built = made;
+  return rc;
+}
+
+int fnv_index_half_rows(fnv_index_t ix, uint64_t info[4]) {
+  if (!ix || !info) return fail(FNV_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(ix->mu);
+  const fnv_index_s* src = rows_source(ix);
+  const int state = src->half.state.load();
+  info[0] = (uint64_t)(!half_rows_eligible(ix->dtype, row_geometry(ix)) ? HALF_INELIGIBLE : state);
+  info[1] = state == HALF_LIVE ? src->half.covered.load() : 0;
+  info[2] = src->half.bytes.load();
+  info[3] = ix->last_half ? 1 : 0;
   return FNV_OK;
 }
 
@@ -732,6 +880,7 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   }
   else if (n == "visited_direct") ix->visited_direct = value;  // (read per launch)
   else if (n == "host_zero_copy") ix->host_zero_copy = value;  // (read per host-buffer call)
+  else if (n == "half_rows") ix->half_rows = value;  // (read per launch; the mirror's launches are another kernel's: measurements go)
   else return fail(FNV_ERR_INVALID, "unknown option: " + n);
   // What fnv_tune measured (kernel variant, LDS layout) stays valid across options that change neither the launch plan
   // nor the kernel choice: Index.h::addBatchDevice flips output_node_ids around every device build, and a tune costs
@@ -836,14 +985,39 @@ static int check_device_status(fnv_index_s* ix, const char* advice = "raise the 
 // ---- one search launch, step by step (search_device_impl runs them in this order under the handle's mutex) -----------
 // (a) The launch plan: depends on (beam width, K, live geometry, options) only -> cached between calls.
 // The HIP runtime as the planner sees it: the kernels of one (index, beam width) by MODE_*.
+// A launch reads the mirror only while it is live, covers every live row and the option is on.
+static bool half_rows_usable(const fnv_index_s* ix, uint64_t live) {
+  const fnv_index_s* src = rows_source(ix);
+  return ix->half_rows != 0 && half_rows_possible(ix) && src->half.state.load() == HALF_LIVE && src->half.covered.load() >= live &&
+         src->half.rows.load() != nullptr;
+}
+// THE place where a search kernel meets its table (BoundKernel): the exact and the merged-beam kernels (DIRECT forms included)
+// read the mirror when `half_rows` asks for it (the row format f32h); the filtered kernel has no such instantiation and keeps
+// reading the float32 table, with the same results.
+enum KernelKind { KERNEL_EXACT, KERNEL_MERGED, KERNEL_MERGED_DIRECT, KERNEL_FILTERED };
+static BoundKernel bind_search_kernel(const fnv_index_s* ix, const RowGeometry& g, KernelKind kind, bool lds, int B, bool half_rows) {
+  auto pick = [&](const KernelTable& t) -> kernel_fn {
+    switch (kind) {
+      case KERNEL_EXACT: return t.exact[g.cfg][g.full];
+      case KERNEL_FILTERED: return t.exact_f[g.cfg][g.full];
+      default: return t.merged[beam_form(lds, B)][kind == KERNEL_MERGED_DIRECT][g.cfg][g.full];
+    }
+  };
+  if (half_rows && kind != KERNEL_FILTERED)
+    if (kernel_fn fn = pick(kernel_table(ix->dtype, ix->metric, true)))
+      return BoundKernel{fn, rows_source(ix)->half.rows.load(), ix->row_bytes / 2, true};
+  return BoundKernel{pick(kernel_table(ix->dtype, ix->metric)), ix->d_vectors, ix->row_bytes, false};
+}
 struct PlanRuntime {
   const fnv_index_s* ix;
   RowGeometry g;
   int B;
-  kernel_fn kernel(int mode, bool direct = false) const {
-    return mode == MODE_HEAPS ? pick_kernel(ix->dtype, ix->metric, g.cfg, g.full)
-                              : pick_sorted_kernel(ix->dtype, ix->metric, g.cfg, g.full, mode == MODE_MERGED_LDS, B, direct);
+  bool half_rows;
+  BoundKernel bound(int mode, bool direct = false) const {
+    return bind_search_kernel(ix, g, mode == MODE_HEAPS ? KERNEL_EXACT : direct ? KERNEL_MERGED_DIRECT : KERNEL_MERGED,
+                              mode == MODE_MERGED_LDS, B, half_rows);
   }
+  kernel_fn kernel(int mode) const { return bound(mode).fn; }
   int occupancy(int mode, uint32_t lds) const {
     int n = 0;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kernel(mode), WAVE, lds) == hipSuccess ? n : 0;
@@ -853,27 +1027,29 @@ struct PlanRuntime {
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
   }
 };
-static int ensure_plan(fnv_index_s* ix, int B, int K) {
+static int ensure_plan(fnv_index_s* ix, int B, int K, bool half_rows) {
   PlannedLaunch& plan = ix->plan;
-  if (plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity && plan.options_version == ix->options_version)
+  // (a mirror that was dropped and built again is another allocation: the plan's kernels carry the table they read)
+  const bool same_rows = plan.half_rows == half_rows && (!half_rows || plan.kern.rows == rows_source(ix)->half.rows.load());
+  if (plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity && plan.options_version == ix->options_version && same_rows)
     return FNV_OK;
   plan = PlannedLaunch();
-  const PlanRuntime rt{ix, row_geometry(ix), B};
+  const PlanRuntime rt{ix, row_geometry(ix), B, half_rows};
   LayoutChoice lc;  // a layout that fnv_tune measured for this beam width overrides the planner's rules (heap home, table size)
   if (auto it = ix->layouts.find(B); it != ix->layouts.end()) lc = it->second;
   std::string err;
   const int rc = plan_launch(ix, B, K, lc, rt, err, plan);
   if (rc) return fail(rc, err);
-  for (SearchParams* p : {&plan.heaps, &plan.sorted}) {
-    p->vectors = ix->d_vectors;
+  for (SearchParams* p : {&plan.heaps, &plan.sorted}) {  // (`vectors` / `row_bytes`: per launch, from the kernel it runs)
     p->tails = ix->tails();
     p->links = ix->d_links;
   }
-  plan.kern = rt.kernel(MODE_HEAPS);
+  plan.kern = rt.bound(MODE_HEAPS);
   if (plan.mode != MODE_HEAPS) {
-    plan.skern = rt.kernel(plan.mode);
-    plan.skern_direct = rt.kernel(plan.mode, true);
+    plan.skern = rt.bound(plan.mode);
+    plan.skern_direct = rt.bound(plan.mode, true);
   }
+  plan.half_rows = half_rows;
   plan.options_version = ix->options_version;
   plan.valid = true;
   return FNV_OK;
@@ -962,14 +1138,26 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   const SearchFilter* filter = opt.filter;
 
   const int B = std::max(ef_search, K);  // Index.h:392
-  int rc = ensure_plan(ix, B, K);
+  const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
+  // The half-width mirror (half_rows.hpp): its state is the source's, read at every launch.  Launches with and without it run
+  // different kernels, so what was measured in the other mode (kernel variant, LDS layout) is discarded with the plan.
+  const bool half_rows = half_rows_usable(ix, live);
+  if (ix->measured_half >= 0 && ix->measured_half != (int)half_rows) {
+    ix->tuner.clear();
+    ix->layouts.clear();
+    ix->sample_kernel = -1;
+    ix->tune_epoch++;
+    ix->plan.valid = false;
+  }
+  ix->measured_half = (int)half_rows;
+  int rc = ensure_plan(ix, B, K, half_rows);
   if (rc) return rc;
   PlannedLaunch& plan = ix->plan;
-  if (filter && !plan.fkern) {
-    plan.fkern = pick_filtered_kernel(ix->dtype, ix->metric, plan.cfg, plan.full);
-    HIP_TRY(raise_lds_limit((const void*)plan.fkern, ix->device, plan.lds));
+  if (filter && !plan.fkern.fn) {
+    plan.fkern = bind_search_kernel(ix, row_geometry(ix), KERNEL_FILTERED, false, B, half_rows);
+    HIP_TRY(raise_lds_limit((const void*)plan.fkern.fn, ix->device, plan.lds));
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern, WAVE, plan.lds) != hipSuccess) n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern.fn, WAVE, plan.lds) != hipSuccess) n = 0;
     plan.fbpc = std::max(1, std::min(plan.bpc, n));
   }
   const KernelChoice c = choose_kernel(ix, B, nq, opt.force_variant, filter != nullptr);
@@ -977,7 +1165,6 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   const int bpc = sorted ? plan.sbpc : opt.filter ? plan.fbpc : plan.bpc;
   uint32_t lds_bytes = sorted ? plan.slds : plan.lds;
   // (shadow mode, tail shadows, the grid: launch_shape, launch_plan.hpp)
-  const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
   const LaunchShape shape = launch_shape(ix, plan, c, bpc, nq, num_initializations, live);
   const bool small_launch = shape.small_launch, shadow = shape.shadow;
   const uint32_t nslots = shape.nslots, tail_shadows = shape.tail_shadows;
@@ -989,6 +1176,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   const bool direct = sorted && small_launch && lay_out_direct(ix, p, &lds_bytes, bpc, nslots);
 
   // (e) the per-call fields, and the launch
+  const BoundKernel& kern = filter ? plan.fkern : !sorted ? plan.kern : direct ? plan.skern_direct : plan.skern;
   p.labels = (opt.node_ids || ix->output_node_ids != 0) ? nullptr : ix->d_labels;  // ("output_node_ids": read under the handle's mutex)
   p.queries = (const uint8_t*)d_queries;
   p.out_dist = out.dist;
@@ -1027,6 +1215,8 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     if (rc) return rc;
     p.entry_node_out = ix->d_entry.as<uint32_t>();
     p.entry_dist_out = (float*)(ix->d_entry.as<uint8_t>() + (size_t)nq * 4);
+    p.vectors = ix->d_vectors;  // (K0 stages float32 rows in LDS whichever table the search kernel reads)
+    p.row_bytes = ix->row_bytes;
     p.scan_tile_stride = p.row_bytes + 16;
     const uint32_t fixed = SCAN_WAVES * p.q_chunks * 16 + SCAN_QPB * 8;
     p.scan_tile_rows = std::max<uint32_t>(1, std::min<uint32_t>(p.n_scan, (64u * 1024u) / p.scan_tile_stride));
@@ -1052,9 +1242,10 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     p.nq = (uint32_t)(2 * nq);
     p.tail_exact = 0u;
   }
-  kernel_fn kern = filter ? plan.fkern : !sorted ? plan.kern : direct ? plan.skern_direct : plan.skern;
-  HIP_TRY(raise_lds_limit((const void*)kern, ix->device, lds_bytes));
-  hipLaunchKernelGGL(kern, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
+  p.vectors = kern.rows;  // the kernel and the table it reads: one BoundKernel
+  p.row_bytes = kern.stride;
+  HIP_TRY(raise_lds_limit((const void*)kern.fn, ix->device, lds_bytes));
+  hipLaunchKernelGGL(kern.fn, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ix->ev1, stream));
   // (f) what the launch was: for the adaptive choice's next harvest, and for the fnv_last_* calls
@@ -1065,6 +1256,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   ix->last_exploratory = c.exploratory;
   if (c.exploratory) ix->explored_launches++;
   ix->last_shadow = shadow;
+  ix->last_half = kern.half_rows;
   ix->last_stream = stream;
   ix->launched = true;
   if (!ix->is_lane) ix->last_served = nullptr;  // the handle's own launch is its most recent one
@@ -1339,6 +1531,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
     ix->last_variant = lane->last_variant;
     ix->last_exploratory = lane->last_exploratory;
     ix->last_shadow = lane->last_shadow;
+    ix->last_half = lane->last_half;
     for (int i = 0; i < 8; i++) ix->geom[i] = lane->geom[i];
     ix->last_served = lane;  // (lanes live as long as the handle)
   }
@@ -1426,6 +1619,7 @@ static void inherit_measurements(const fnv_index_s* src, fnv_index_s* r) {
     r->layouts.clear();  // measured under the old options (a stale table size could even change the kernel mode)
   }
   r->sample_kernel = -1;
+  r->measured_half = same_model ? src->measured_half : -1;  // (a replica without the source's mirror discards them at its first launch)
   r->replica_epoch = src->tune_epoch;
   r->tune_epoch++;  // (the replica's own lanes re-copy)
 }
@@ -1496,6 +1690,16 @@ int fnv_replica_refresh(fnv_index_t src, int n_replicas, fnv_index_t* replicas) 
       have.push_back(to);
     }
   }
+  // a source that is searched from its half-width mirror gives every replica one: rebuilt there from the rows just copied
+  if (src->half.state.load() == HALF_LIVE && src->half.covered.load() >= live)
+    for (int i = 0; i < n_replicas; i++) {
+      fnv_index_t r = replicas[i];
+      std::lock_guard<std::mutex> rl(r->mu);
+      HIP_TRY(hipSetDevice(r->device));
+      int built = 0;
+      const int rc = half_rows_build(r, &built);
+      if (rc) return rc;
+    }
   return FNV_OK;
 }
 

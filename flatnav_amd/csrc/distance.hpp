@@ -1,8 +1,24 @@
 // distance.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
 // Cross-lane reductions, per-chunk distance arithmetic and the batched gather/distance primitive.
 #pragma once
+#include "half_rows.hpp"
 #include "search_params.h"
 namespace fnv_dev {
+
+// The ROW FORMAT a kernel is instantiated for (its T argument) names two things that differ in one case: the element type of
+// the rows and the element type of the queries.  `f32h` = float32 queries on the half-width mirror of a float32 table
+// (half_rows.hpp); for every other format both are T.
+struct f32h {};
+template <typename T>
+struct RowFormat {
+  typedef T query_t;
+  static constexpr bool half_rows = false;
+};
+template <>
+struct RowFormat<f32h> {
+  typedef float query_t;
+  static constexpr bool half_rows = true;
+};
 
 // ---------------------------------------------------------------------------------------------
 // Cross-lane sums over aligned groups of G lanes (DPP inside a 16-lane row, bpermute above).
@@ -57,6 +73,48 @@ struct Dist<float, METRIC> {
     } else {
       acc = __builtin_elementwise_fma(x0, y0, acc);
       acc = __builtin_elementwise_fma(x1, y1, acc);
+    }
+    return acc;
+  }
+  static __device__ __forceinline__ float lane_sum(f32x2 a, int) { return a.x + a.y; }
+  static __device__ __forceinline__ float finish(float s) { return METRIC == FNV_METRIC_L2 ? s : 1.0f - s; }
+};
+
+// float32 queries on mirror rows (half_rows.hpp): one UNIT = two float32 chunks' worth of binary16 values, the first chunk in
+// y.x / y.y, the second in y.z / y.w.  Per chunk the float path's operations on the same values in the same order: L2 forms
+// fma(x, 1.0, -y) with x in f32 and y widened exactly by v_fma_mix_f32 -- the correctly rounded f32 difference, as v_pk_add_f32
+// gives on the float32 row -- and squares with the same two v_pk_fma_f32; IP is fma(x, y, acc) with y widened in the
+// instruction, the packed fma's two halves one by one.
+template <int METRIC>
+struct Dist<f32h, METRIC> {
+  typedef f32x2 acc_t;
+  typedef int qacc_t;  // unused
+  static __device__ __forceinline__ f32x2 zero() { return f32x2{0.f, 0.f}; }
+  static __device__ __forceinline__ int qzero() { return 0; }
+  static __device__ __forceinline__ int qchunk(int q, const uint4&) { return q; }
+  // {x0 - lo(y), x1 - hi(y)}
+  static __device__ __forceinline__ f32x2 diff(uint32_t x0, uint32_t x1, uint32_t y) {
+    f32x2 t;
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(t.x) : "v"(x0), "v"(y));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t.y) : "v"(x1), "v"(y));
+    return t;
+  }
+  // {fma(x0, lo(y), acc.x), fma(x1, hi(y), acc.y)}
+  static __device__ __forceinline__ f32x2 mul_add(uint32_t x0, uint32_t x1, uint32_t y, f32x2 acc) {
+    f32x2 r;
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(r.x) : "v"(x0), "v"(y), "v"(acc.x));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r.y) : "v"(x1), "v"(y), "v"(acc.y));
+    return r;
+  }
+  // one float32 query chunk against the four binary16 values in (ya, yb)
+  static __device__ __forceinline__ f32x2 half_chunk(f32x2 acc, const uint4& x, uint32_t ya, uint32_t yb) {
+    if (METRIC == FNV_METRIC_L2) {
+      const f32x2 t0 = diff(x.x, x.y, ya), t1 = diff(x.z, x.w, yb);
+      acc = __builtin_elementwise_fma(t0, t0, acc);
+      acc = __builtin_elementwise_fma(t1, t1, acc);
+    } else {
+      acc = mul_add(x.x, x.y, ya, acc);
+      acc = mul_add(x.z, x.w, yb, acc);
     }
     return acc;
   }
@@ -258,6 +316,31 @@ __device__ __forceinline__ void batch_dists(const uint8_t* rows, uint32_t row_st
 #pragma unroll
     for (int pu = 0; pu < PU; pu++)
       if (pu < npass) acc[pu] = D::chunk(acc[pu], xt, yt[pu]);
+  } else if constexpr (RowFormat<T>::half_rows) {
+    // the half-width mirror of FULL float32 rows (half_rows.hpp): `rows` / `row_stride` address mirror rows, `nchunks` and the
+    // staged query stay the float32 row's.  Lane g loads units c0/2 + j*G + g and meets chunks c0 + (2j)*G + g, c0 + (2j+1)*G + g
+    // in the float32 path's order.
+    static_assert(FULL && CU % 2 == 0, "mirror rows exist for FULL rows with an even CU only");
+    constexpr int HU = CU / 2;
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++) rowp[pu] += g * 16;
+    for (int c0 = 0; c0 < nchunks; c0 += G * CU) {
+      uint4 y[PU][HU];
+#pragma unroll
+      for (int pu = 0; pu < PU; pu++) {
+        if (pu < npass) {
+#pragma unroll
+          for (int j = 0; j < HU; j++) y[pu][j] = *reinterpret_cast<const uint4*>(rowp[pu] + (c0 / 2 + j * G) * 16);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < HU; j++) {
+        const uint4 xa = q.lds[c0 + (2 * j) * G + g], xb = q.lds[c0 + (2 * j + 1) * G + g];
+#pragma unroll
+        for (int pu = 0; pu < PU; pu++)
+          if (pu < npass) acc[pu] = D::half_chunk(D::half_chunk(acc[pu], xa, y[pu][j].x, y[pu][j].y), xb, y[pu][j].z, y[pu][j].w);
+      }
+    }
   } else if (FULL) {
     // rows are a whole number of G*CU-chunk spans (e.g. d=128 f32: 32 chunks = 8 lanes x 4): no clamping, no
     // tail select; one address per pass, the CU loads use immediate offsets

@@ -35,9 +35,21 @@ struct KernelTable {
   X(5, merged1, __VA_ARGS__) X(6, merged0, __VA_ARGS__) X(7, merged2, __VA_ARGS__) X(8, merged_d, __VA_ARGS__)   \
   X(9, merged1_d, __VA_ARGS__) X(10, merged0_d, __VA_ARGS__) X(11, merged2_d, __VA_ARGS__)
 
+// The row format f32h (float32 queries on the half-width mirror of a float32 table, half_rows.hpp) has the exact family (without
+// the entry scan) and the merged-beam families with their DIRECT forms only, for the FULL rows with an even CU; its tables'
+// other slots are null.  X(metric ordinal, tag)
+#define FNV_FOR_EACH_HALF_ROWS_METRIC(X) X(0, l2) X(1, ip)
+#define FNV_FOR_EACH_HALF_ROWS_FAMILY(X, ...)                                                                            \
+  X(0, exact, __VA_ARGS__) X(4, merged, __VA_ARGS__) X(5, merged1, __VA_ARGS__) X(6, merged0, __VA_ARGS__)               \
+  X(7, merged2, __VA_ARGS__) X(8, merged_d, __VA_ARGS__) X(9, merged1_d, __VA_ARGS__) X(10, merged0_d, __VA_ARGS__)      \
+  X(11, merged2_d, __VA_ARGS__)
+
 #define FNV_DECLARE_FILLER(ordinal, family, tag, mtag) void fill_##family##_##tag##_##mtag(KernelTable& t);
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_FOR_EACH_FAMILY(FNV_DECLARE_FILLER, tag, mtag)
 FNV_FOR_EACH_TYPE_METRIC(FNV_DECLARE_FILLERS)
+#undef FNV_DECLARE_FILLERS
+#define FNV_DECLARE_FILLERS(M, mtag) FNV_FOR_EACH_HALF_ROWS_FAMILY(FNV_DECLARE_FILLER, f32h, mtag)
+FNV_FOR_EACH_HALF_ROWS_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #undef FNV_DECLARE_FILLER
 

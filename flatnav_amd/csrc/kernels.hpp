@@ -123,9 +123,11 @@ __device__ __forceinline__ void reset_visited(uint32_t* vis, uint32_t* ovf_list,
 
 // The query of work item qi: staged in LDS (zero padded to q_chunks), or -- rows of one 192-chunk span, distance.hpp --
 // straight from the caller's array into the lane's registers (no LDS is reserved for it then).
-template <typename T, int G, int CU>
+// (RT: the kernel's row format; the query's element type is RowFormat<RT>::query_t, distance.hpp)
+template <typename RT, int G, int CU>
 __device__ __forceinline__ void stage_query(Query<G, CU>& q, uint4* qlds, uint32_t* vis, uint32_t* ovf_list, int qi, bool tagged,
                                             int lane) {
+  typedef typename RowFormat<RT>::query_t T;
   ColdArgs c = cold_args();
   const uint32_t dim = c->dim;
   const T* qsrc = reinterpret_cast<const T*>(c->queries) + (uint64_t)qi * dim;

@@ -41,6 +41,7 @@ struct IndexOptions {
           sorted_beam_min = 1, sorted_cand_lds = 2, sorted_tail_exact_pct = -1, beam_registers = 1,
           sorted_variant = -1, tune_layout = 1, shadow_exact = 1, tie_replay = 1, tie_log_entries = 0, visited_direct = 1,
           host_zero_copy = 1 << 20;  // (every call that fits the pinned staging buffer)
+  int64_t half_rows = 1;  // searches read the half-width mirror of a float32 table while one is live (half_rows.hpp)
   int64_t overflow_list = -1;  // -1: automatic (a list in HBM only when the bitmap is larger than 512 KB)
 };
 

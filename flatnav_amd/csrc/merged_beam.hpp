@@ -228,7 +228,7 @@ __global__ __launch_bounds__(WAVE, CU == 1 ? 5 : R == MB_R ? 3 : waves_per_simd<
     // nothing and cost ~20 M scalar instructions per launch, 162 -> 143 M in profiles/r3_sq_counters.json)
     auto guess_next = [&](const int nd, const int runner_up) {
 #ifndef FNV_NO_SPEC_ROW
-      if constexpr (sizeof(T) > 1) {
+      if constexpr (sizeof(typename RowFormat<T>::query_t) > 1) {
         if (runner_up != spec_node || nd == spec_node) {  // (a guess that is still the runner-up keeps its row)
           spec_node = runner_up;
           if (runner_up >= 0) spec_row = load_row(runner_up);

@@ -78,6 +78,32 @@ __global__ void relayout_vectors_kernel(const uint8_t* __restrict__ aos, uint64_
   }
 }
 
+// The half-width mirror (half_rows.hpp) of rows [first, first + count) of the float32 table: one thread per 16-byte mirror unit
+// (two float32 chunks in, eight binary16 values out).  A value that binary16 does not hold exactly raises *lossy_flag.
+__global__ __launch_bounds__(256) void half_rows_kernel(const uint8_t* __restrict__ vectors, uint32_t row_bytes, uint64_t first,
+                                                        uint64_t count, uint32_t G, uint32_t CU, uint8_t* __restrict__ mirror,
+                                                        int* lossy_flag) {
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t units = row_bytes / 32;  // per row
+  const uint64_t row = tid / units;
+  const uint32_t u = (uint32_t)(tid % units);
+  if (row >= count) return;
+  const uint32_t ca = half_first_chunk_of_unit(u, G, CU);
+  const uint8_t* src = vectors + (first + row) * row_bytes;
+  const uint4 a = *reinterpret_cast<const uint4*>(src + ca * 16u), b = *reinterpret_cast<const uint4*>(src + (ca + G) * 16u);
+  const uint32_t f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  uint32_t h[8];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    h[k] = half_bits_trunc(f[k]);
+    ok = ok && half_bits_widen((uint16_t)h[k]) == f[k];
+  }
+  *reinterpret_cast<uint4*>(mirror + (first + row) * (uint64_t)(row_bytes / 2) + u * 16u) =
+      make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+  if (!ok) atomicOr(lossy_flag, 1);
+}
+
 __global__ void relayout_links_kernel(const uint8_t* __restrict__ aos, uint64_t node_size, uint64_t data_size,
                                       uint32_t M, uint64_t first_node, uint64_t count, uint64_t n_nodes,
                                       uint32_t* __restrict__ links, int32_t* __restrict__ labels, int* bad_flag) {

@@ -27,7 +27,7 @@ C_ABI_SYMBOLS = [
     "fnv_index_read_links", "fnv_last_replayed_queries", "fnv_replicate", "fnv_replica_refresh",
     "fnv_search_batch_multi", "fnv_index_view", "fnv_tune", "fnv_last_launch_info", "fnv_gather_ceiling",
     "fnv_index_adopt", "fnv_lane_info", "fnv_last_handover_stats", "fnv_row_layout",
-    "fnv_search_batch_filtered", "fnv_search_batch_filtered_device",
+    "fnv_search_batch_filtered", "fnv_search_batch_filtered_device", "fnv_index_build_half_rows", "fnv_index_half_rows",
 ]
 
 _lib = None
@@ -95,6 +95,9 @@ def lib() -> C.CDLL:
     for name in ("fnv_lane_info", "fnv_last_handover_stats"):
         if hasattr(L, name) or LIB_PATH == os.path.join(HERE, "libflatnav_hip.so"):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    if hasattr(L, "fnv_index_half_rows"):  # (older builds under the A/B tools lack the half-width mirror)
+        L.fnv_index_build_half_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.fnv_index_half_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -297,6 +300,21 @@ class DeviceIndex:
         check(lib().fnv_replica_refresh(self._h, len(replicas), arr))
         for r in replicas:
             r.n_nodes = self.n_nodes
+
+    # ---- the half-width mirror of a float32 index (include/flatnav_hip.h) -------------------------
+    def build_half_rows(self) -> bool:
+        """(Re)convert rows [0, n_live) into the half-width mirror (fnv_index_build_half_rows): needed after vectors were
+        written through device_buffers().  True when a live mirror resulted."""
+        built = C.c_int(0)
+        check(lib().fnv_index_build_half_rows(self._h, C.byref(built)))
+        return bool(built.value)
+
+    def half_rows(self) -> dict:
+        """State of the mirror this handle's searches read (fnv_index_half_rows)."""
+        r = (C.c_uint64 * 4)()
+        check(lib().fnv_index_half_rows(self._h, r))
+        return {"state": ["none", "live", "dropped", "ineligible"][int(r[0])], "rows": int(r[1]), "bytes": int(r[2]),
+                "used_by_last_launch": bool(int(r[3]))}
 
     def set_option(self, name: str, value: int) -> None:
         check(lib().fnv_set_option(self._h, name.encode(), int(value)))

@@ -89,6 +89,14 @@ def replicate_index(dev, device: int, src: int = 0, group=None, piece_bytes: int
     stats = broadcast_buffers(views, src=src, group=group, piece_bytes=piece_bytes, sync=lambda: torch.cuda.synchronize(device))
     for name, st in zip(names, stats):
         st["buffer"] = name
+    # The broadcasts wrote this rank's vectors through raw pointers, which the library does not see: a receiving rank builds the
+    # half-width mirror of its float32 rows itself (include/flatnav_hip.h; a no-op for rows that have none).
+    build = getattr(dev, "build_half_rows", None)
+    if build is not None:
+        import torch.distributed as dist
+
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_rank(group) != src:
+            build()
     return stats
 
 

@@ -124,8 +124,30 @@ int fnv_index_adopt(const void* vectors, const void* links, const void* labels, 
  * each row's dim elements.  (No reference interface: the reference's layout is the AoS node record, Index.h:61-63, 555-573.) */
 int fnv_row_layout(uint32_t dim, int data_type, uint64_t capacity, uint32_t* row_bytes, uint32_t* tail_bytes);
 
-/* Device pointers and byte sizes of the three index buffers: [0]=vectors (split rows: table + side table) [1]=links [2]=labels. */
+/* Device pointers and byte sizes of the three index buffers: [0]=vectors (split rows: table + side table) [1]=links [2]=labels.
+ * (The half-width mirror below is not among them: sizes and fnv_index_info's row_bytes describe the float32 table.)
+ * A caller that WRITES vectors through these pointers on a handle whose mirror is live (fnv_index_half_rows) must call
+ * fnv_index_build_half_rows afterwards: the library does not see such writes, and searches would go on reading the old rows. */
 int fnv_index_device_buffers(fnv_index_t index, void* ptrs[3], uint64_t sizes[3]);
+
+/* ---- the half-width mirror of a float32 index -------------------------------------------------
+ * A float32 index whose rows hold only values that IEEE binary16 represents exactly (SIFT / BIGANN / MNIST delivered as float32,
+ * small integers, coarsely quantised embeddings) is searched from a private copy of its rows at half the bytes, with float32
+ * queries and float32 arithmetic on exactly the same values in the same order: every result keeps its bits, for every query.
+ * The copy is made as rows are written (fnv_index_upload, fnv_index_write_nodes) while the writes are contiguous from row 0;
+ * one value that binary16 does not hold, a write that leaves a gap or a failed allocation drops it for the life of the
+ * handle and frees it.  It costs row_bytes / 2 per row of capacity (counted in fnv_index_info's total_device_bytes) and exists
+ * for rows of 64, 128, 256, 512 and 1024 k float32 elements and rows padded to those.  Handles of fnv_index_alloc filled through
+ * fnv_index_device_buffers and handles of fnv_index_adopt start without one; views read their source's; fnv_replicate /
+ * fnv_replica_refresh build one on every replica of a source that has one.  Option "half_rows" = 0: searches ignore it;
+ * FLATNAV_HALF_ROWS=0 in the environment when a handle is made: it is never built.
+ *
+ * fnv_index_build_half_rows (re)converts rows [0, n_live) from the float32 table; *built (may be null) = 1 when a live mirror
+ * resulted, 0 when the rows are not lossless, the geometry has none, it is switched off or memory ran out (not errors).
+ * fnv_index_half_rows: info[4] = {state: 0 none, 1 live, 2 dropped, 3 the geometry has none; rows covered; bytes held;
+ * 1 when the handle's most recent launch read the mirror}. */
+int fnv_index_build_half_rows(fnv_index_t index, int* built);
+int fnv_index_half_rows(fnv_index_t index, uint64_t info[4]);
 
 /* info[8] = {data_type, M, row_bytes | tail_bytes << 32, n_nodes, dim, metric, device, total_device_bytes}.
  * row_bytes = stride of the vector table.  tail_bytes != 0 ("split rows", round 6): rows of three whole 128-byte lines plus at
@@ -226,6 +248,9 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *                     call (one query at ef=50 on 1M x 128: 0.157 -> 0.143 ms wall).  Larger calls whose arrays (queries AND
  *                     every output passed) are already pinned host memory -- hipHostMalloc, hipHostRegister, torch's
  *                     pin_memory -- run zero-copy on the caller's own memory.  0 = every call copies in and out.  Same bytes.
+ *   "half_rows"       1 (default): searches of a float32 index read its half-width mirror while one is live and covers every
+ *                     live row (see fnv_index_half_rows); 0 = they read the float32 table.  Changing it discards what fnv_tune /
+ *                     the adaptive choice measured (another kernel).  Same bytes.
  *   "tune_layout"     1 (default): fnv_tune also measures the LDS layout (see fnv_tune); 0 = kernel variants only
  *   "sorted_beam_min" smallest beam width the merged-beam kernel is used for (default 1)
  *   "sorted_cand_lds" where the exact re-run of the merged-beam kernel keeps its candidates heap: 2 (default) = in LDS

@@ -132,7 +132,7 @@ def apply(spec, undo=False):
 DEFAULTS = dict(visited_factor=27, visited_slots=0, visited_floor=2048, occupancy_target=13, occupancy_roomy=9, cand_factor=2,
                 cand_slots=0, blocks_per_cu=0, sorted_beam=2, sorted_cand_lds=2, sorted_tail_exact_pct=-1, beam_registers=1,
                 sorted_variant=-1, tune_layout=1, shadow_exact=1, entry_kernel=0, visited_tag_bits=0, overflow_list=-1,
-                wide_table_max=-1, query_regs=1, tie_replay=1, tie_log_entries=0)
+                wide_table_max=-1, query_regs=1, tie_replay=1, tie_log_entries=0, half_rows=1)
 
 
 def timed(dev, ef, steps):
