@@ -54,6 +54,7 @@
 #include "merged_beam.hpp"
 #endif
 #include "relayout.hpp"
+#include "scan.hpp"
 
 using namespace fnv_dev;
 
@@ -150,6 +151,7 @@ const KernelTable& kernel_table(int, int, bool = false) {
           for (int d = 0; d < 2; d++) k.merged[form][d][c][f] = merged[form][d];
         k.select[c][f] = FNV_DEV_KERNEL(wire_select_kernel);
         k.connect[c][f] = FNV_DEV_KERNEL(wire_connect_kernel);
+        k.flat[c][f] = FNV_DEV_KERNEL(exhaustive_scan_kernel);
       }
     return k;
   }();
@@ -249,6 +251,8 @@ struct SearchOptions {
                                     // the same handle is never forced)
   int32_t* host_status = nullptr;   // zero-copy small searches: the error flag's copy in the caller's pinned slab
   const SearchFilter* filter = nullptr;  // filtered search: every query runs the filtered two-heap kernel
+  bool exhaustive = false;          // fnv_search_batch_exhaustive: no graph search at all -- the scan of scan.hpp (over the
+                                    // filter's nodes, if there is one)
 };
 
 // A host-buffer search that went through a pinned slab: what search_host_finish copies where.
@@ -346,14 +350,16 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
     DeviceBuf ovf;     // uint32 [nslots][ovf_cap] ids whose bitmap words need clearing (big indexes)
     DeviceBuf spill;   // uint64 [nslots][spill_entries]: what the candidates heap does not keep in LDS
     DeviceBuf tielog;  // uint64, merged-beam kernel: [nslots][log_entries] hand-over log (round 5)
-    size_t bytes() const { return bitmap.bytes + ovf.bytes + spill.bytes + tielog.bytes; }
-    size_t release() { return bitmap.release() + ovf.release() + spill.release() + tielog.release(); }
+    DeviceBuf scan;    // uint64, exhaustive search: [nq][segments][K] partial lists (scan.hpp)
+    size_t bytes() const { return bitmap.bytes + ovf.bytes + spill.bytes + tielog.bytes + scan.bytes; }
+    size_t release() { return bitmap.release() + ovf.release() + spill.release() + tielog.release() + scan.release(); }
   } ws;
   // further buffers, each grown on demand
   DeviceBuf d_entry;      // [nq] uint32 entry nodes | [nq] float entry distances (K0 output)
   DeviceBuf d_done;       // uint32, shadow mode: [nq] "answered" flags
   DeviceBuf d_nodebits;   // uint32, filtered search: [capacity / 32] words, bit per node id (node_filter_kernel)
   DeviceBuf d_allowed;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM
+  DeviceBuf d_scanids;    // uint32, filtered exhaustive search: [0] the count, [4 ...) the allowed node ids (capacity of them)
   DeviceBuf d_wirebuf;    // fnv_index_insert_batch: [count*keep] x {req_target, req_index, sorted_target, sorted_req} | sort scratch
   DeviceBuf d_nodestage;  // write_nodes: AoS staging chunk + bad flag + "not lossless" flag of the mirror's conversion
   DeviceBuf d_halfflag;   // fnv_index_build_half_rows: the conversion's "not lossless" flag
@@ -880,12 +886,13 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   }
   else if (n == "visited_direct") ix->visited_direct = value;  // (read per launch)
   else if (n == "host_zero_copy") ix->host_zero_copy = value;  // (read per host-buffer call)
+  else if (n == "scan_segment_rows") ix->scan_segment_rows = value;  // (read per exhaustive launch)
   else if (n == "half_rows") ix->half_rows = value;  // (read per launch; the mirror's launches are another kernel's: measurements go)
   else return fail(FNV_ERR_INVALID, "unknown option: " + n);
   // What fnv_tune measured (kernel variant, LDS layout) stays valid across options that change neither the launch plan
   // nor the kernel choice: Index.h::addBatchDevice flips output_node_ids around every device build, and a tune costs
   // dozens of launches.  (output_node_ids is read per launch; shadow_exact per launch; tune_layout by fnv_tune itself.)
-  const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy";
+  const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows";
   if (!keeps_tuning) {
     ix->options_version++;
     ix->tuner.clear();
@@ -1123,9 +1130,120 @@ static int grow_workspace(fnv_index_s* ix, uint32_t max_slots, uint64_t nq, bool
 
 // (d) Small launches on small indexes run the kernel's DIRECT form on a bitmap of all node ids: lay_out_direct (launch_plan.hpp).
 
+// ---- exhaustive search (scan.hpp): the launch ---------------------------------------------------------------------
+// How a launch of `nq` queries for K results is cut up: queries per tile (as many as a block's LDS budget holds next to their
+// result lists, at most 32), row segments (enough blocks to fill the device, at most 64 and at most what keeps the partial
+// lists within 256 MB; or what "scan_segment_rows" asks for).
+constexpr uint32_t kScanLdsBudget = 20u << 10;  // per block: eight blocks per CU = two wavefronts per SIMD
+constexpr uint32_t kScanMaxTile = 32, kScanMaxSegments = 64, kScanForcedSegments = 1024;
+constexpr uint64_t kScanPartialBudget = 256ull << 20;
+struct ScanShape {
+  uint32_t tile, tiles, segments, lds;
+};
+static ScanShape scan_shape(const fnv_index_s* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
+  ScanShape s;
+  const uint32_t per_query = g.q_chunks * 16u + (uint32_t)K * 8u;
+  s.tile = std::max(1u, std::min(kScanMaxTile, kScanLdsBudget / per_query));
+  s.tile = (uint32_t)std::min<uint64_t>(s.tile, nq);
+  s.lds = s.tile * per_query;
+  s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);
+  uint64_t seg;
+  if (ix->scan_segment_rows > 0) {
+    seg = std::min<uint64_t>((live + (uint64_t)ix->scan_segment_rows - 1) / (uint64_t)ix->scan_segment_rows, kScanForcedSegments);
+  } else {
+    const uint64_t want_blocks = (uint64_t)std::max(1, ix->num_cus) * 8u;
+    seg = std::min<uint64_t>((want_blocks + s.tiles - 1) / s.tiles, std::max<uint64_t>(1, live / 1024));
+    seg = std::min<uint64_t>(seg, kScanMaxSegments);
+    seg = std::min<uint64_t>(seg, std::max<uint64_t>(1, kScanPartialBudget / (nq * (uint64_t)K * 8u)));
+  }
+  seg = std::min<uint64_t>(seg, 0x7FFFFFFFull / s.tiles);
+  s.segments = (uint32_t)std::max<uint64_t>(1, seg);
+  return s;
+}
+
+static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, const SearchOutputs& out, void* hip_stream,
+                            const SearchOptions& opt) {
+  if (K < 1 || K > SCAN_MAX_K) return fail(FNV_ERR_INVALID, "K of an exhaustive search must be between 1 and 1024");
+  if (nq == 0) return FNV_OK;
+  if (!d_queries || !out.dist || !out.labels) return fail(FNV_ERR_INVALID, "null buffer");
+  if (nq > 0x7FFFFFFFull) return fail(FNV_ERR_INVALID, "too many queries in one batch");
+  std::lock_guard<std::mutex> lock(ix->mu);
+  ON_DEVICE(ix->device);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const SearchFilter* filter = opt.filter;
+  const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
+  const RowGeometry g = row_geometry(ix);
+  const ScanShape shape = scan_shape(ix, g, nq, K, live);
+  if (shape.lds > 160u * 1024u) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
+  const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
+
+  int rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
+  if (!rc && filter) rc = ix->d_nodebits.grow((size_t)(ix->capacity + 31) / 32 * 4);
+  if (!rc && filter) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
+  ix->ws_bytes = ix->ws.bytes();
+  if (rc) return rc;
+
+  ScanParams p;
+  memset(&p, 0, sizeof(p));
+  p.vectors = ix->d_vectors;
+  p.tails = ix->tails();
+  p.labels = (opt.node_ids || ix->output_node_ids != 0) ? nullptr : ix->d_labels;
+  p.queries = (const uint8_t*)d_queries;
+  p.partial = ix->ws.scan.as<uint64_t>();
+  p.out_dist = out.dist;
+  p.out_labels = out.labels;
+  p.out_count = out.count;
+  p.out_ndist = out.ndist;
+  p.n_live = live;
+  p.nq = (uint32_t)nq;
+  p.dim = ix->dim;
+  p.row_bytes = ix->row_bytes;
+  p.nchunks = g.nchunks;
+  p.q_chunks = g.q_chunks;
+  p.tail_chunks = g.tail_chunks;
+  p.K = (uint32_t)K;
+  p.segments = shape.segments;
+  p.tile_queries = shape.tile;
+  p.tiles = shape.tiles;
+
+  HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));  // (the status word: this path never sets it)
+  if (filter) {  // the label bitmap -> this handle's node bitmap -> the list of allowed node ids
+    const uint64_t words = (ix->capacity + 31) / 32;
+    uint32_t* const ids = ix->d_scanids.as<uint32_t>();
+    hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
+                       live, words, filter->bits, filter->n_bits, ix->d_nodebits.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(ids, 0, 16, stream));
+    hipLaunchKernelGGL(exhaustive_compact_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, stream,
+                       (const uint32_t*)ix->d_nodebits.as<uint32_t>(), live, ids + 4, ids);
+    HIP_TRY(hipGetLastError());
+    p.cand_ids = ids + 4;
+    p.cand_count = ids;
+  }
+  ix->sample_kernel = -1;  // ev0 / ev1 no longer bracket a graph-search launch: a pending sample of the adaptive choice is dropped
+  HIP_TRY(hipEventRecord(ix->ev0, stream));
+  HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
+  hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, p);
+  HIP_TRY(hipGetLastError());
+  const uint32_t merge_lds = 3u * (uint32_t)K * 8u;
+  hipLaunchKernelGGL(exhaustive_merge_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ix->ev1, stream));
+  ix->last_stream = stream;
+  ix->launched = true;
+  if (!ix->is_lane) ix->last_served = nullptr;
+  ix->geom[0] = (uint64_t)shape.tiles * shape.segments;
+  ix->geom[1] = WAVE;
+  ix->geom[2] = shape.lds;
+  for (int i = 3; i < 8; i++) ix->geom[i] = 0;
+  ix->geom[6] = 3;  // (fnv_last_launch_geometry: the exhaustive scan)
+  return FNV_OK;
+}
+
 static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
                               const SearchOutputs& out, void* hip_stream, const SearchOptions& opt) {
   if (!ix) return fail(FNV_ERR_INVALID, "index is null");
+  if (opt.exhaustive) return scan_device_impl(ix, d_queries, nq, K, out, hip_stream, opt);
   // Index.h:847-849
   if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
   if (K <= 0 || ef_search <= 0) return fail(FNV_ERR_INVALID, "K and ef_search must be positive");
@@ -1288,10 +1406,12 @@ static uint64_t now_ns() {
 // ix->host_mu) and finish (wait, report a capacity error).
 // `host_filter` (filtered search): the label bitmap in host memory; it is staged into this handle's HBM first.
 static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search,
-                               int num_initializations, const SearchOutputs& user, const SearchFilter* host_filter = nullptr) {
+                               int num_initializations, const SearchOutputs& user, const SearchFilter* host_filter = nullptr,
+                               bool exhaustive = false) {
   ON_DEVICE(ix->device);
   SearchFilter dev_filter{nullptr, 0};
   SearchOptions opt;
+  opt.exhaustive = exhaustive;
   if (host_filter) {
     const size_t fbytes = (size_t)((host_filter->n_bits + 7) / 8);
     if (fbytes) {
@@ -1461,7 +1581,7 @@ static void sync_lane(fnv_index_t ix, fnv_index_s* lane) {
 // them from pinned host memory behind a gate word, results written straight back (every touch of host memory from a
 // running wave costs microseconds: 1.7-2.6 ms).  Neither is in the tree.
 static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
-                             const SearchOutputs& out, const SearchFilter* host_filter) {
+                             const SearchOutputs& out, const SearchFilter* host_filter, bool exhaustive = false) {
   int rc = check_search_args(ix, queries, nq, K, ef_search, num_initializations, out.dist, out.labels);
   if (rc || nq == 0) return rc;
   // one caller at a time per lane (a lane's staging areas, stream and workspace are its caller's for the whole call); a
@@ -1511,7 +1631,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
   }
   if (!host_lock.owns_lock()) host_lock = std::unique_lock<std::mutex>(ix->host_mu);
   if (lane != ix) sync_lane(ix, lane);
-  rc = search_host_enqueue(lane, queries, nq, K, ef_search, num_initializations, out, host_filter);
+  rc = search_host_enqueue(lane, queries, nq, K, ef_search, num_initializations, out, host_filter, exhaustive);
   if (rc == FNV_ERR_NO_DEVICE && lane != ix) {
     // a lane could not get its workspace (another copy of the per-slot bitmaps and spill areas: 19 GB at 50M nodes): the
     // call waits for the handle's own lane instead, like any caller did before there were lanes
@@ -1519,7 +1639,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
     host_lock.unlock();  // (never hold a lane while waiting for the handle: fnv_tune takes them in the other order)
     host_lock = std::unique_lock<std::mutex>(ix->host_mu);
     lane = ix;
-    rc = search_host_enqueue(ix, queries, nq, K, ef_search, num_initializations, out, host_filter);
+    rc = search_host_enqueue(ix, queries, nq, K, ef_search, num_initializations, out, host_filter, exhaustive);
   }
   if (rc) return rc;
   rc = search_host_finish(lane);
@@ -1574,6 +1694,35 @@ int fnv_search_batch_filtered_device(fnv_index_t ix, const void* d_queries, uint
   opt.filter = &f;
   return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations,
                             SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, d_out_nhops}, hip_stream, opt);
+}
+
+// ---- exhaustive search: the exact K nearest among the live nodes, or among those whose label is allowed (scan.hpp) -----
+static int check_exhaustive_args(fnv_index_t ix, int K, int use_filter, const void* allowed_bits, uint64_t n_bits) {
+  if (!ix) return fail(FNV_ERR_INVALID, "index is null");
+  if (K < 1 || K > SCAN_MAX_K) return fail(FNV_ERR_INVALID, "K of an exhaustive search must be between 1 and 1024");
+  return use_filter ? check_filter_args(allowed_bits, n_bits) : FNV_OK;
+}
+
+int fnv_search_batch_exhaustive(fnv_index_t ix, const void* queries, uint64_t nq, int K, int use_filter, const void* allowed_bits,
+                                uint64_t n_bits, float* out_dist, int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist) {
+  int rc = check_exhaustive_args(ix, K, use_filter, allowed_bits, n_bits);
+  if (rc) return rc;
+  const SearchFilter f{(const uint8_t*)allowed_bits, n_bits};
+  return search_batch_host(ix, queries, nq, K, /*ef_search=*/1, /*num_initializations=*/1,
+                           SearchOutputs{out_dist, out_labels, out_count, out_ndist, nullptr}, use_filter ? &f : nullptr, true);
+}
+
+int fnv_search_batch_exhaustive_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int use_filter,
+                                       const void* d_allowed_bits, uint64_t n_bits, float* d_out_dist, int32_t* d_out_labels,
+                                       int32_t* d_out_count, uint64_t* d_out_ndist, void* hip_stream) {
+  int rc = check_exhaustive_args(ix, K, use_filter, d_allowed_bits, n_bits);
+  if (rc) return rc;
+  const SearchFilter f{n_bits ? (const uint8_t*)d_allowed_bits : nullptr, n_bits};
+  SearchOptions opt;
+  opt.filter = use_filter ? &f : nullptr;
+  opt.exhaustive = true;
+  return search_device_impl(ix, d_queries, nq, K, 1, 1, SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, nullptr},
+                            hip_stream, opt);
 }
 
 // ---- several GPUs behind one call -----------------------------------------------------------------

@@ -43,6 +43,7 @@ struct IndexOptions {
           host_zero_copy = 1 << 20;  // (every call that fits the pinned staging buffer)
   int64_t half_rows = 1;  // searches read the half-width mirror of a float32 table while one is live (half_rows.hpp)
   int64_t overflow_list = -1;  // -1: automatic (a list in HBM only when the bitmap is larger than 512 KB)
+  int64_t scan_segment_rows = 0;  // exhaustive search: candidate rows per block's segment (0: automatic)
 };
 
 // What the planner reads of an index (fnv_index_s inherits it): the options, the table geometry, the device's size.

@@ -146,17 +146,10 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     return py::make_tuple(dist, labels);
   }
 
-  // search_filtered(queries, K, ef_search, allowed, num_initializations=100) -> (float32[Q,K], int32[Q,K]): the k-NN among the
-  // nodes whose label is allowed; `allowed` = 1-D bool mask indexed by label, or 1-D integer array of labels (order and
-  // duplicates ignored, a negative label raises ValueError).  Short rows are padded with (+inf, -1), never raised on.
-  py::tuple searchFiltered(const py::array& queries_any, int K, int ef_search, const py::array& allowed_any, int num_initializations) {
-    py::array queries = elements(queries_any);
-    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
-    if (K <= 0) throw std::invalid_argument("K must be positive.");
+  // `allowed` (1-D bool mask indexed by label, or 1-D integer array of labels) -> the C ABI's bitmap over label values
+  static void packAllowed(const py::array& allowed_any, std::vector<uint8_t>& bits, uint64_t& n_bits) {
     if (allowed_any.ndim() != 1) throw std::invalid_argument("allowed must be a 1-D bool mask or a 1-D array of labels.");
     constexpr uint64_t kMaxBits = uint64_t(1) << 31;
-    std::vector<uint8_t> bits;
-    uint64_t n_bits = 0;
     if (allowed_any.dtype().kind() == 'b') {
       auto mask = allowed_any.cast<dense_array<bool>>();
       n_bits = static_cast<uint64_t>(mask.size());
@@ -178,6 +171,18 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     } else {
       throw std::invalid_argument("allowed must be a bool mask or an integer array of labels.");
     }
+  }
+
+  // search_filtered(queries, K, ef_search, allowed, num_initializations=100) -> (float32[Q,K], int32[Q,K]): the k-NN among the
+  // nodes whose label is allowed; `allowed` = 1-D bool mask indexed by label, or 1-D integer array of labels (order and
+  // duplicates ignored, a negative label raises ValueError).  Short rows are padded with (+inf, -1), never raised on.
+  py::tuple searchFiltered(const py::array& queries_any, int K, int ef_search, const py::array& allowed_any, int num_initializations) {
+    py::array queries = elements(queries_any);
+    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
+    if (K <= 0) throw std::invalid_argument("K must be positive.");
+    std::vector<uint8_t> bits;
+    uint64_t n_bits = 0;
+    packAllowed(allowed_any, bits, n_bits);
     const py::ssize_t nq = queries.shape(0);
     py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
     py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
@@ -188,6 +193,35 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
       py::gil_scoped_release release;
       _index->searchBatchFiltered(qptr, static_cast<uint64_t>(nq), K, ef_search, num_initializations, bits.empty() ? nullptr : bits.data(),
                                   n_bits, dptr, lptr, nullptr);
+    }
+    return py::make_tuple(dist, labels);
+  }
+
+  // search_exhaustive(queries, K, allowed=None) -> (float32[Q,K], int32[Q,K]): the exact K nearest among all nodes, or among
+  // those whose label is allowed (`allowed` as for search_filtered), by one device scan; sorted by (distance, node id).
+  // Short rows are padded with (+inf, -1), never raised on.
+  py::tuple searchExhaustive(const py::array& queries_any, int K, const py::object& allowed_obj) {
+    py::array queries = elements(queries_any);
+    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
+    if (K <= 0 || K > 1024) throw std::invalid_argument("K of an exhaustive search must be between 1 and 1024.");
+    std::vector<uint8_t> bits;
+    uint64_t n_bits = 0;
+    const bool use_filter = !allowed_obj.is_none();
+    if (use_filter) {
+      py::array allowed_any = py::array::ensure(allowed_obj);
+      if (!allowed_any) throw std::invalid_argument("allowed must be a bool mask or an integer array of labels.");
+      packAllowed(allowed_any, bits, n_bits);
+    }
+    const py::ssize_t nq = queries.shape(0);
+    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
+    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
+    {
+      const void* qptr = queries.data();
+      float* dptr = dist.mutable_data();
+      int* lptr = labels.mutable_data();
+      py::gil_scoped_release release;
+      _index->searchBatchExhaustive(qptr, static_cast<uint64_t>(nq), K, bits.empty() ? nullptr : bits.data(), n_bits, use_filter, dptr,
+                                    lptr, nullptr);
     }
     return py::make_tuple(dist, labels);
   }
@@ -273,6 +307,10 @@ void bindIndex(py::module_& m, const char* name) {
            py::arg("num_initializations") = 100,
            "Batched k-NN among the nodes whose label is allowed (`allowed`: bool mask indexed by label, or integer labels) "
            "-> (distances[Q,K] float32, labels[Q,K] int32), rows padded with (+inf, -1) when fewer than K are allowed.")
+      .def("search_exhaustive", &T::searchExhaustive, py::arg("queries"), py::arg("K"), py::arg("allowed") = py::none(),
+           "Exact k-NN by one device scan over all nodes, or over the nodes whose label is allowed (`allowed` as for "
+           "search_filtered) -> (distances[Q,K] float32, labels[Q,K] int32) sorted by (distance, node id), rows padded with "
+           "(+inf, -1) when there are fewer than K candidates.  1 <= K <= 1024.")
       .def("get_query_distance_computations", &T::getQueryDistanceComputations,
            "Distance evaluations since the last call (needs collect_stats=True); resets the counter.")
       .def("save", &T::save, py::arg("filename"), "Write the index in flatnav's binary format.")

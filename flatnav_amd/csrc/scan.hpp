@@ -1,0 +1,223 @@
+// scan.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's `scan` units and by beam_search.hip).
+// The EXHAUSTIVE search (fnv_search_batch_exhaustive): the exact K nearest among the live nodes, or among the allowed ones.
+//
+//   1. filtered calls: node_filter_kernel (relayout.hpp) turns the label bitmap into a node bitmap, exhaustive_compact_kernel
+//      turns that into the list of allowed node ids (any order: the selection's order is total, scan_select.hpp).
+//   2. exhaustive_scan_kernel, one wavefront per (query tile, row segment): the tile's queries are staged in LDS, a lane group
+//      loads the chunks of PU rows into registers ONCE and scores them against every query of the tile -- the row traffic of a
+//      launch is  ceil(nq / tile) * candidates * row_bytes  instead of nq * candidates * row_bytes.  Per (query, row) the
+//      arithmetic is batch_dists' (distance.hpp): lane g of the row's group accumulates chunks g, g + G, ... in that order with
+//      Dist<T, METRIC>, group_sum adds the lanes -- so a distance has the bits the graph search reports for the same pair.
+//      Every query keeps a sorted list of its K best keys in LDS; a row that does not beat the K-th is dropped by one compare,
+//      one that does (about K ln(n / K) per query) is inserted by the whole wave.
+//   3. exhaustive_merge_kernel, one wavefront per query: the segments' lists merged by rank (scan_select.hpp), keys back to
+//      (distance, label), padding, counters.
+#pragma once
+#include "distance.hpp"
+#include "heaps.hpp"
+#include "scan_select.hpp"
+namespace fnv_dev {
+
+// key into the sorted list[0, K) (wave-uniform arguments; the caller has checked key < list[K - 1]): the last entry falls out
+__device__ __forceinline__ void scan_insert(uint64_t* list, int K, uint64_t key, int lane) {
+  const int pos = (int)scan_lower_bound(list, (uint32_t)K, key);
+  for (int top = K - 1; top > pos; top -= WAVE) {  // entries (max(pos, top - 64), top] move up by one, the highest first
+    const int j = top - lane;
+    const bool act = j > pos;
+    uint64_t e = 0;
+    if (act) e = list[j - 1];
+    wave_sync();
+    if (act) list[j] = e;
+    wave_sync();
+  }
+  if (lane == 0) list[pos] = key;
+  wave_sync();
+}
+
+template <typename T, int METRIC, int G, int CU, bool FULL>
+__global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int PU = passes<G, CU>();
+  constexpr int VPW = WAVE / G;
+  constexpr int SPAN = G * CU;
+  constexpr bool TAIL = row_has_tail<G, CU, FULL>();
+  typedef Dist<T, METRIC> D;
+  typedef typename D::acc_t acc_t;
+  const int lane = threadIdx.x, g = lane % G, v = lane / G;
+  const uint32_t tile = blockIdx.x % p.tiles, seg = blockIdx.x / p.tiles;
+  const uint32_t q0 = tile * p.tile_queries;
+  const uint32_t nqb = min(p.tile_queries, p.nq - q0);
+  const int K = (int)p.K;
+  const uint32_t q_chunks = p.q_chunks;
+  const int nchunks = (int)p.nchunks;
+  uint4* const qlds = reinterpret_cast<uint4*>(smem);                                               // [tile][q_chunks]
+  uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * q_chunks * 16u);  // [tile][K]
+
+  {  // the tile's queries, zero padded to q_chunks; every list empty
+    const int padded = (int)(q_chunks * 16u / sizeof(T));
+    const int dim = (int)p.dim;
+    for (uint32_t qq = 0; qq < nqb; qq++) {
+      const T* qsrc = reinterpret_cast<const T*>(p.queries) + (uint64_t)(q0 + qq) * p.dim;
+      T* qdst = reinterpret_cast<T*>(qlds + (size_t)qq * q_chunks);
+      for (int i = lane; i < padded; i += WAVE) qdst[i] = i < dim ? qsrc[i] : T(0);
+    }
+    for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) lists[i] = SCAN_PAD;
+  }
+  wave_sync();
+
+  // this block's share of the candidates
+  const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
+  const uint64_t lo = ncand * seg / p.segments, hi = ncand * (seg + 1) / p.segments;
+  const bool one_span = nchunks <= SPAN;  // (every row configuration but rows beyond 4 KB)
+  const uint32_t tc = p.tail_chunks;
+
+  for (uint64_t base = lo; base < hi; base += VPW * PU) {
+    uint32_t id[PU];
+    bool val[PU];
+    const uint8_t* rowp[PU];
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++) {  // lanes past the end re-read the last candidate; their results are ignored
+      const uint64_t slot = base + (uint64_t)(pu * VPW + v);
+      val[pu] = slot < hi;
+      const uint64_t idx = val[pu] ? slot : hi - 1;
+      id[pu] = p.cand_ids ? p.cand_ids[idx] : (uint32_t)idx;
+      rowp[pu] = p.vectors + (uint64_t)id[pu] * p.row_bytes;
+    }
+    uint4 y[PU][CU], yt[PU];
+    // lane g's chunks c0 + g, c0 + G + g, ... of every row of the batch; zero beyond the row (the staged query is zero there too)
+    auto load_span = [&](int c0) {
+#pragma unroll
+      for (int pu = 0; pu < PU; pu++) {
+#pragma unroll
+        for (int cu = 0; cu < CU; cu++) {
+          const int c = c0 + cu * G + g;
+          y[pu][cu] = make_uint4(0u, 0u, 0u, 0u);
+          if (FULL || TAIL || c < nchunks) y[pu][cu] = *reinterpret_cast<const uint4*>(rowp[pu] + (uint32_t)c * 16u);
+        }
+      }
+    };
+    if (one_span) load_span(0);
+    if constexpr (TAIL) {  // split rows: chunk 24 + g from the side table
+#pragma unroll
+      for (int pu = 0; pu < PU; pu++) {
+        yt[pu] = make_uint4(0u, 0u, 0u, 0u);
+        if ((uint32_t)g < tc) yt[pu] = *reinterpret_cast<const uint4*>(p.tails + ((uint64_t)id[pu] * tc + (uint32_t)g) * 16u);
+      }
+    }
+
+    for (uint32_t qq = 0; qq < nqb; qq++) {
+      const uint4* qv = qlds + (size_t)qq * q_chunks;
+      acc_t acc[PU];
+      typename D::qacc_t qacc = D::qzero();
+#pragma unroll
+      for (int pu = 0; pu < PU; pu++) acc[pu] = D::zero();
+      for (int c0 = 0; c0 < nchunks; c0 += SPAN) {
+        if (!one_span) load_span(c0);
+#pragma unroll
+        for (int cu = 0; cu < CU; cu++) {
+          const uint4 x = qv[c0 + cu * G + g];
+          qacc = D::qchunk(qacc, x);
+#pragma unroll
+          for (int pu = 0; pu < PU; pu++) acc[pu] = D::chunk(acc[pu], x, y[pu][cu]);
+        }
+      }
+      if constexpr (TAIL) {
+        const uint4 xt = qv[SPAN + g];
+        qacc = D::qchunk(qacc, xt);
+#pragma unroll
+        for (int pu = 0; pu < PU; pu++) acc[pu] = D::chunk(acc[pu], xt, yt[pu]);
+      }
+      uint64_t* const list = lists + (size_t)qq * K;
+      uint64_t kth = list[K - 1];  // one address for the wave: a broadcast read
+#pragma unroll
+      for (int pu = 0; pu < PU; pu++) {
+        const float d = D::finish(group_sum<G>(D::lane_sum(acc[pu], qacc)));
+        const uint64_t key = scan_key(__float_as_uint(d), id[pu]);
+        unsigned long long pm = __ballot(g == 0 && val[pu] && scan_key_less(key, kth));
+        while (pm) {  // rare: about K ln(n / K) rows per query ever get here
+          const int i = __ffsll((long long)pm) - 1;
+          pm &= pm - 1;
+          const uint64_t k = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), i) << 32) |
+                             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, i);
+          if (scan_key_less(k, kth)) {
+            scan_insert(list, K, k, lane);
+            kth = list[K - 1];
+          }
+        }
+      }
+    }
+  }
+
+  wave_sync();
+  for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) {
+    const uint32_t qq = i / (uint32_t)K, k = i % (uint32_t)K;
+    p.partial[((uint64_t)(q0 + qq) * p.segments + seg) * (uint64_t)K + k] = lists[i];
+  }
+}
+
+#ifndef FNV_INST_FAMILY  // (the two kernels below are not templates: beam_search.hip alone emits them, not kernel_inst.hip's units)
+// The allowed node ids of a node bitmap (bit i & 31 of word i >> 5), compacted wave by wave: the order is whatever the
+// atomics make it, which the selection does not see.  *count must be zero at launch; ids holds n_live entries.
+static __global__ __launch_bounds__(256) void exhaustive_compact_kernel(const uint32_t* node_bits, uint64_t n_live, uint32_t* ids,
+                                                                        uint32_t* count) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool ok = i < n_live && ((node_bits[i >> 5] >> (i & 31)) & 1u);
+  const unsigned long long m = __ballot(ok);
+  if (m == 0ull) return;
+  const int lane = (int)(threadIdx.x & (WAVE - 1));
+  uint32_t first = 0;
+  if (lane == __ffsll((long long)m) - 1) first = atomicAdd(count, (uint32_t)__popcll(m));
+  first = (uint32_t)__shfl((int)first, __ffsll((long long)m) - 1, WAVE);
+  if (ok) ids[first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)i;
+}
+
+// One wavefront per query: its `segments` sorted lists -> the K first of their union -> the caller's arrays.
+// LDS: three lists of K keys.
+static __global__ __launch_bounds__(WAVE) void exhaustive_merge_kernel(const ScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const uint32_t q = blockIdx.x, K = p.K;
+  uint64_t* a = reinterpret_cast<uint64_t*>(smem);
+  uint64_t* b = a + K;
+  uint64_t* const c = b + K;
+  const uint64_t* part = p.partial + (uint64_t)q * p.segments * K;
+  for (uint32_t i = lane; i < K; i += WAVE) a[i] = part[i];
+  wave_sync();
+  for (uint32_t s = 1; s < p.segments; s++) {
+    const uint64_t* src = part + (uint64_t)s * K;
+    if (!scan_key_less(src[0], a[K - 1])) continue;  // (wave-uniform) nothing of this segment ranks before the K-th so far
+    for (uint32_t i = lane; i < K; i += WAVE) c[i] = src[i];
+    wave_sync();
+    for (uint32_t i = lane; i < K; i += WAVE) {
+      const uint64_t ka = a[i], kc = c[i];
+      const uint32_t pa = scan_merge_pos_a(i, ka, c, K), pc = scan_merge_pos_b(i, kc, a, K);
+      if (pa < K) b[pa] = ka;
+      if (pc < K) b[pc] = kc;
+    }
+    wave_sync();
+    uint64_t* t = a;
+    a = b;
+    b = t;
+  }
+  const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
+  for (uint32_t k = lane; k < K; k += WAVE) {
+    const uint64_t key = a[k];
+    float od = std::numeric_limits<float>::infinity();
+    int32_t ol = -1;
+    if (key != SCAN_PAD) {
+      od = __uint_as_float(scan_key_dist_bits(key));
+      const uint32_t node = scan_key_node(key);
+      ol = p.labels ? p.labels[node] : (int32_t)node;
+    }
+    p.out_dist[(uint64_t)q * K + k] = od;
+    p.out_labels[(uint64_t)q * K + k] = ol;
+  }
+  if (lane == 0) {
+    if (p.out_count) p.out_count[q] = (int32_t)(ncand < (uint64_t)K ? ncand : (uint64_t)K);
+    if (p.out_ndist) p.out_ndist[q] = ncand;
+  }
+}
+
+#endif  // FNV_INST_FAMILY
+
+}  // namespace fnv_dev

@@ -1,0 +1,105 @@
+// scan_select.hpp -- part of the gfx950 search engine, free of HIP (device code includes it through scan.hpp, the host code
+// through kernel_table.h, tests/scan_select_harness.cpp as it is).  The SELECTION rules of the exhaustive search
+// (fnv_search_batch_exhaustive): how a (distance, node id) pair becomes one sortable key, and how two sorted partial lists of K
+// keys become the K smallest of their union -- each stated here once, used by the scan kernel's per-query lists, by the merge
+// kernel and by the CPU test.
+//
+// Order.  Ascending by (distance, node id); a NaN distance ranks after every number, +inf included; among NaNs by node id.  That
+// is a TOTAL order on distinct node ids, so a result depends neither on how rows were tiled into segments nor on which lane
+// saw a row first.  (The graph search orders equal distances as libstdc++'s heaps leave them; this order is not that one.)
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define FNV_SCAN_HD __host__ __device__
+#else
+#define FNV_SCAN_HD
+#endif
+
+namespace fnv_dev {
+
+constexpr int SCAN_MAX_K = 1024;          // the widest result list of an exhaustive search
+constexpr uint64_t SCAN_PAD = ~0ull;      // "no entry": sorts after every real key (a real node id is never 0xFFFFFFFF)
+constexpr uint32_t SCAN_NAN_ORD = 0xFFFFFFFFu;
+
+// float32 bits -> an unsigned integer that orders like the number; every NaN -> SCAN_NAN_ORD (above +inf); -0 and +0 coincide.
+FNV_SCAN_HD inline uint32_t scan_dist_ord(uint32_t bits) {
+  const uint32_t mag = bits & 0x7FFFFFFFu;
+  if (mag > 0x7F800000u) return SCAN_NAN_ORD;
+  if (mag == 0u) return 0x80000000u;
+  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+}
+// ... and back: the distance's bits (a NaN comes back as the quiet NaN 0x7FC00000, a zero as +0).
+FNV_SCAN_HD inline uint32_t scan_ord_dist(uint32_t ord) {
+  if (ord == SCAN_NAN_ORD) return 0x7FC00000u;
+  return (ord & 0x80000000u) ? (ord & 0x7FFFFFFFu) : ~ord;
+}
+FNV_SCAN_HD inline uint64_t scan_key(uint32_t dist_bits, uint32_t node) {
+  return ((uint64_t)scan_dist_ord(dist_bits) << 32) | node;
+}
+FNV_SCAN_HD inline uint32_t scan_key_dist_bits(uint64_t key) { return scan_ord_dist((uint32_t)(key >> 32)); }
+FNV_SCAN_HD inline uint32_t scan_key_node(uint64_t key) { return (uint32_t)key; }
+// a ranks before b
+FNV_SCAN_HD inline bool scan_key_less(uint64_t a, uint64_t b) { return a < b; }
+
+// Entries of the sorted list[0, n) that rank before `key` / that do not rank after it.
+FNV_SCAN_HD inline uint32_t scan_lower_bound(const uint64_t* list, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (scan_key_less(list[mid], key)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+FNV_SCAN_HD inline uint32_t scan_upper_bound(const uint64_t* list, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (!scan_key_less(key, list[mid])) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Merge of two sorted lists a[0, K), b[0, K) (each padded with SCAN_PAD), by RANK: a[i] lands at i + (entries of b before it),
+// b[j] at j + (entries of a not after it).  Real keys are distinct (a node is in one list), equal keys are pads, and the two
+// rules send equal keys of a before those of b: every position below K is written exactly once, by whoever holds it -- one
+// independent binary search per entry, which is what lets 64 lanes do a merge without talking to each other.
+FNV_SCAN_HD inline uint32_t scan_merge_pos_a(uint32_t i, uint64_t key, const uint64_t* b, uint32_t K) {
+  return i + scan_lower_bound(b, K, key);
+}
+FNV_SCAN_HD inline uint32_t scan_merge_pos_b(uint32_t j, uint64_t key, const uint64_t* a, uint32_t K) {
+  return j + scan_upper_bound(a, K, key);
+}
+// out[0, K) = the K first of a merged with b (out overlaps neither)
+inline void scan_merge_lists(const uint64_t* a, const uint64_t* b, uint64_t* out, uint32_t K) {
+  for (uint32_t i = 0; i < K; i++) {
+    const uint32_t pa = scan_merge_pos_a(i, a[i], b, K), pb = scan_merge_pos_b(i, b[i], a, K);
+    if (pa < K) out[pa] = a[i];
+    if (pb < K) out[pb] = b[i];
+  }
+}
+
+// Parameter block of the exhaustive search's kernels (scan.hpp).
+struct ScanParams {
+  const uint8_t* vectors;      // [capacity][row_bytes]: the table the filtered search kernel reads
+  const uint8_t* tails;        // split rows: the side table, else null
+  const int32_t* labels;       // null: node ids go out
+  const uint8_t* queries;      // [nq][dim] elements
+  const uint32_t* cand_ids;    // filtered: the allowed node ids, in any order; null: the candidates are nodes [0, n_live)
+  const uint32_t* cand_count;  // filtered: how many (device memory: the host never waits for it)
+  uint64_t* partial;           // [nq][segments][K] keys: every (query, segment)'s sorted list
+  float* out_dist;             // [nq][K]
+  int32_t* out_labels;         // [nq][K]
+  int32_t* out_count;          // [nq] or null
+  uint64_t* out_ndist;         // [nq] or null
+  uint64_t n_live;
+  uint32_t nq, dim, row_bytes, nchunks, q_chunks, tail_chunks;
+  uint32_t K;
+  uint32_t segments;           // row segments: block b scans segment b / tiles for query tile b % tiles
+  uint32_t tile_queries;       // queries staged in LDS per block: that many share one load of a row
+  uint32_t tiles;              // ceil(nq / tile_queries)
+};
+
+}  // namespace fnv_dev

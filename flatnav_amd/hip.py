@@ -28,6 +28,7 @@ C_ABI_SYMBOLS = [
     "fnv_search_batch_multi", "fnv_index_view", "fnv_tune", "fnv_last_launch_info", "fnv_gather_ceiling",
     "fnv_index_adopt", "fnv_lane_info", "fnv_last_handover_stats", "fnv_row_layout",
     "fnv_search_batch_filtered", "fnv_search_batch_filtered_device", "fnv_index_build_half_rows", "fnv_index_half_rows",
+    "fnv_search_batch_exhaustive", "fnv_search_batch_exhaustive_device",
 ]
 
 _lib = None
@@ -76,6 +77,11 @@ def lib() -> C.CDLL:
                                                 C.c_uint64] + [C.c_void_p] * 5
         L.fnv_search_batch_filtered_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                                        C.c_void_p, C.c_uint64] + [C.c_void_p] * 6
+    if hasattr(L, "fnv_search_batch_exhaustive"):  # (older builds under the A/B tools lack the exhaustive search)
+        L.fnv_search_batch_exhaustive.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_uint64] + [C.c_void_p] * 4
+        L.fnv_search_batch_exhaustive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                                         C.c_uint64] + [C.c_void_p] * 5
     L.fnv_search_status.argtypes = [C.c_void_p]
     L.fnv_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.fnv_last_replayed_queries.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
@@ -361,6 +367,29 @@ class DeviceIndex:
             return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
         return d, l
 
+    def search_exhaustive(self, queries, K: int, allowed=None, stats: bool = False):
+        """Exhaustive search (fnv_search_batch_exhaustive): the exact K nearest among the live nodes, or -- `allowed` given, see
+        pack_allowed -- among those whose label is allowed -> (dist float32[Q,K], labels int32[Q,K][, stats]).  Sorted by
+        (distance, node id), NaN distances last.  Rows with fewer than K candidates are padded with (+inf, -1);
+        stats = {"count": real entries per row, "n_dist": rows evaluated per query = the number of candidates}."""
+        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("Queries have incorrect dimensions.")
+        nq = q.shape[0]
+        if K <= 0 or K > 1024:
+            raise ValueError("K of an exhaustive search must be between 1 and 1024")
+        bits, n_bits = pack_allowed(allowed) if allowed is not None else (None, 0)
+        d = np.empty((nq, K), dtype=np.float32)
+        l = np.empty((nq, K), dtype=np.int32)
+        cnt = np.empty(nq, dtype=np.int32)
+        nd = np.zeros(nq, dtype=np.uint64)
+        check(lib().fnv_search_batch_exhaustive(self._h, q.ctypes.data, nq, K, 0 if allowed is None else 1,
+                                                bits.ctypes.data if n_bits else None, n_bits, d.ctypes.data, l.ctypes.data,
+                                                cnt.ctypes.data, nd.ctypes.data))
+        if stats:
+            return d, l, {"count": cnt, "n_dist": nd}
+        return d, l
+
     def search_into(self, queries: np.ndarray, K: int, ef_search: int, dist: np.ndarray, labels: np.ndarray,
                     num_initializations: int = 100) -> None:
         """Host-buffer batched search into arrays the CALLER owns (no allocation, no conversion): queries [Q, dim] of the index's
@@ -392,6 +421,16 @@ class DeviceIndex:
         check(lib().fnv_search_batch_filtered_device(self._h, q_ptr, nq, K, ef_search, num_initializations, bits_ptr or None,
                                                      int(n_bits), dist_ptr, label_ptr, count_ptr or None, ndist_ptr or None,
                                                      nhops_ptr or None, stream or None))
+
+    def search_device_exhaustive(self, q_ptr: int, nq: int, K: int, dist_ptr: int, label_ptr: int, count_ptr: int = 0,
+                                 ndist_ptr: int = 0, bits_ptr: int = 0, n_bits: int = 0, use_filter: bool = False,
+                                 stream=None) -> None:
+        """Device-buffer exhaustive search (fnv_search_batch_exhaustive_device): every pointer is device memory; with
+        `use_filter` the label bitmap `bits_ptr` of `n_bits` bits restricts the candidates (n_bits = 0: the empty filter).
+        Enqueued on `stream` (raw hipStream_t handle, None / 0 = null stream) without synchronising."""
+        check(lib().fnv_search_batch_exhaustive_device(self._h, q_ptr, nq, K, 1 if use_filter else 0, bits_ptr or None,
+                                                       int(n_bits), dist_ptr, label_ptr, count_ptr or None, ndist_ptr or None,
+                                                       stream or None))
 
     def tune(self, queries, K: int, ef_search: int, num_initializations: int = 100, nq: int = 0) -> None:
         """Settle the adaptive kernel choice for (K, ef_search, this batch size) in one call (fnv_tune): afterwards no
@@ -449,7 +488,7 @@ class DeviceIndex:
         check(lib().fnv_last_launch_geometry(self._h, g))
         keys = ["grid_blocks", "block_threads", "lds_bytes", "blocks_per_cu", "visited_slots", "cand_slots"]
         out = {k: int(g[i]) for i, k in enumerate(keys)}
-        out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds"][int(g[6])]
+        out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds", "exhaustive_scan"][int(g[6])]
         out["tail_exact"] = int(g[7])
         return out
 

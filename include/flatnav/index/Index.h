@@ -886,6 +886,40 @@ class Index {
     return results;
   }
 
+  // Exhaustive search (flatnav_hip.h, fnv_search_batch_exhaustive): the EXACT K nearest neighbours among the live nodes, or
+  // (use_filter) among those whose label is set in allowed_bits (as searchBatchFiltered reads it), by one device scan: no graph,
+  // no ef_search, no capacity limit.  Sorted by (distance, node id), NaN distances last.  1 <= K <= 1024.  Rows with fewer than
+  // K candidates are padded with (+inf, -1) and out_count says how many are real: not an error.  Always on this index's
+  // primary GPU.  (No reference counterpart: the reference has no brute-force search.)
+  void searchBatchExhaustive(const void* queries, uint64_t nq, int K, const uint8_t* allowed_bits, uint64_t n_bits, bool use_filter,
+                             float* out_dist, label_t* out_labels, int32_t* out_count = nullptr) {
+    std::lock_guard<std::mutex> g(_device_guard);
+    ensureDevice();
+    std::vector<uint64_t> ndist;
+    if (_collect_stats) ndist.resize(nq);
+    detail::throwOnDeviceError(fnv_search_batch_exhaustive(_device_index, queries, nq, K, use_filter ? 1 : 0, allowed_bits, n_bits,
+                                                           out_dist, reinterpret_cast<int32_t*>(out_labels), out_count,
+                                                           _collect_stats ? ndist.data() : nullptr));
+    if (_collect_stats) {  // one evaluation per candidate row and query
+      uint64_t total = 0;
+      for (uint64_t v : ndist) total += v;
+      _distance_computations.fetch_add(total);
+    }
+  }
+
+  // One query: up to K (distance, label) pairs, ascending by (distance, node id) (fewer when there are fewer candidates).
+  std::vector<dist_label_t> searchExhaustive(const void* query, const int K, const uint8_t* allowed_bits = nullptr,
+                                             uint64_t n_bits = 0, bool use_filter = false) {
+    std::vector<float> dist(static_cast<size_t>(std::max(K, 0)));
+    std::vector<label_t> labels(static_cast<size_t>(std::max(K, 0)));
+    int32_t count = 0;
+    searchBatchExhaustive(query, 1, K, allowed_bits, n_bits, use_filter, dist.data(), labels.data(), &count);
+    std::vector<dist_label_t> results;
+    results.reserve(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) results.emplace_back(dist[static_cast<size_t>(i)], labels[static_cast<size_t>(i)]);
+    return results;
+  }
+
   // ---- reordering (reference Index.h:412-440, 872-926) ---------------------------------------
   void doGraphReordering(const std::vector<std::string>& reordering_methods) {
     for (const auto& method : reordering_methods) {

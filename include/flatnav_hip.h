@@ -248,6 +248,9 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *                     call (one query at ef=50 on 1M x 128: 0.157 -> 0.143 ms wall).  Larger calls whose arrays (queries AND
  *                     every output passed) are already pinned host memory -- hipHostMalloc, hipHostRegister, torch's
  *                     pin_memory -- run zero-copy on the caller's own memory.  0 = every call copies in and out.  Same bytes.
+ *   "scan_segment_rows"  exhaustive search (fnv_search_batch_exhaustive): candidate rows that one block's row segment covers;
+ *                     0 (default) = automatic (enough segments to fill the device, at most 64); tests force many segments and
+ *                     a real merge on a small index with it (at most 1024 segments).  Same bytes.
  *   "half_rows"       1 (default): searches of a float32 index read its half-width mirror while one is live and covers every
  *                     live row (see fnv_index_half_rows); 0 = they read the float32 table.  Changing it discards what fnv_tune /
  *                     the adaptive choice measured (another kernel).  Same bytes.
@@ -327,6 +330,41 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
                                      float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count,
                                      uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream);
 
+/* Exhaustive search: for each query the EXACT K nearest neighbours among the live nodes [0, n_live) (the live count the graph
+ * searches see; a view reads its source's), or among those whose label is allowed -- by one device scan, without the graph:
+ * neither ef_search nor a capacity limit comes into it, and FNV_ERR_CAPACITY is never reported.  The call for selective
+ * filters (a filtered graph search spends its time walking nodes it may not return) and for ground truth that carries the
+ * search kernels' own distance bits.  No reference counterpart (the reference has no brute-force search).
+ *   use_filter == 0: every live node is a candidate; allowed_bits / n_bits are ignored.
+ *   use_filter != 0: the nodes whose label is set in allowed_bits -- meaning and limits exactly as for fnv_search_batch_filtered
+ *     (bit order, negative labels and labels >= n_bits not allowed, n_bits <= 2^31, NULL only with n_bits == 0 = the empty filter).
+ *   Distances: each reported distance has the bits fnv_search_batch reports for the same (query, node), for every element type,
+ *     both metrics and every row layout (the same per-lane chunk order and cross-lane sum as the search kernels).  The float32
+ *     table is read, never the half-width mirror.
+ *   Order: ascending by (distance, NODE ID); a NaN distance ranks after every number, +inf included, NaNs among themselves by
+ *     node id (a NaN is reported as the quiet NaN 0x7FC00000).  The tie order is BY NODE ID -- a total order, so the result does not
+ *     depend on how the scan was cut up; the graph searches order equal distances as libstdc++'s heaps leave them, which is
+ *     another order.
+ *   Output: out_labels holds labels (node ids with option "output_node_ids"); rows with fewer than K candidates are padded with
+ *     (+inf, -1); out_count[q] (nullable) = real entries; out_ndist[q] (nullable) = rows evaluated for that query = the number
+ *     of candidates.  Fewer than K results is not an error.
+ *   Limits: 1 <= K <= 1024, else FNV_ERR_INVALID; nq == 0 is a no-op.
+ *   Memory: the distance matrix is never materialised.  Temporary HBM, in the workspace of whichever handle or lane runs the
+ *     call (given back with it): nq x K x S x 8 bytes of partial result lists, S = row segments <= 64, chosen so that the lists
+ *     stay within 256 MB whenever S > 1 ("scan_segment_rows" forces S, up to 1024); filtered calls add capacity / 8 bytes (node
+ *     bitmap) + 4 x capacity + 16 bytes (allowed node ids).
+ * fnv_search_batch_exhaustive: host buffers (allowed_bits included); thread safety and lanes as fnv_search_batch.
+ * fnv_search_batch_exhaustive_device: every buffer, allowed_bits included, in the index's device memory, enqueued on `hip_stream`
+ *   without synchronising; one launch in flight per handle, as fnv_search_batch_device.
+ * Neither takes samples for the adaptive kernel choice nor changes what it or fnv_tune measured; fnv_last_kernel_ms reports the
+ * scan and its merge; fnv_last_launch_geometry reports {grid_blocks, 64, lds_bytes, 0, 0, 0, kernel = 3, 0}. */
+int fnv_search_batch_exhaustive(fnv_index_t index, const void* queries, uint64_t nq, int K, int use_filter,
+                                const void* allowed_bits, uint64_t n_bits, float* out_dist, int32_t* out_labels,
+                                int32_t* out_count, uint64_t* out_ndist);
+int fnv_search_batch_exhaustive_device(fnv_index_t index, const void* d_queries, uint64_t nq, int K, int use_filter,
+                                       const void* d_allowed_bits, uint64_t n_bits, float* d_out_dist, int32_t* d_out_labels,
+                                       int32_t* d_out_count, uint64_t* d_out_ndist, void* hip_stream);
+
 /* ---- several GPUs of one node: index replicated, query rows sharded, no per-query collective -------
  * The reference parallelises a batch over host threads that share one index in memory (executeInParallel over rows,
  * python-bindings/src/flatnav/bindings.cpp:198-211, include/flatnav/util/Multithreading.h:19-48); here every GPU
@@ -366,7 +404,7 @@ int fnv_last_replayed_queries(fnv_index_t index, uint64_t out[5]);
 
 /* Launch geometry of the most recent search: geom[8] = {grid_blocks, block_threads, lds_bytes,
  * blocks_per_cu, visited_slots, cand_slots (LDS entries of the exact search's candidates heap), kernel: 0 = two-heap
- * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, tail_exact: the last that-many queries of the launch
+ * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, tail_exact: the last that-many queries of the launch
  * went straight to the exact search (merged-beam kernel, see the "sorted_tail_exact_pct" option)}.
  * blocks_per_cu = the query slots a CU keeps resident = the grid's share per CU (round 5; gfx950 hands LDS out in 1280-byte
  * granules, so this is min(what the HIP occupancy API counts, 163840 / (ceil(lds_bytes / 1280) * 1280)); rounds 1-4 launched the
