@@ -1,8 +1,8 @@
 """Builds the in-tree gfx950 shared library (C ABI of include/flatnav_hip.h) with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container as well as on the MI355X box.
-The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 96
-objects (kernel_inst.hip: 12 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
+The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 104
+objects (kernel_inst.hip: 13 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
 half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), plus beam_search.hip (host code, C ABI, re-layout kernels), and
 linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
@@ -30,7 +30,8 @@ METRICS = [(0, "l2"), (1, "ip")]
 FAMILIES = [(0, "exact"), (3, "wire"), (4, "merged"), (5, "merged1"), (6, "merged0"), (7, "merged2"),
             (8, "merged_d"), (9, "merged1_d"), (10, "merged0_d"), (11, "merged2_d"),  # 8-11: the DIRECT forms (small launches)
             (12, "exact_f"),  # the filtered two-heap kernel
-            (13, "scan")]  # the exhaustive search's scan (csrc/scan.hpp)
+            (13, "scan"),  # the exhaustive search's scan (csrc/scan.hpp)
+            (14, "scan_g")]  # ... with one filter per query (fnv_search_batch_exhaustive_grouped)
 # the row format f32h (csrc/half_rows.hpp; kernel_table.h's FNV_FOR_EACH_HALF_ROWS_FAMILY): the families that read mirror rows
 HALF_ROWS_TYPE = ("fnv_dev::f32h", "f32h")
 HALF_ROWS_FAMILIES = [f for f in FAMILIES if f[0] == 0 or 4 <= f[0] <= 11]  # exact, merged beam and its DIRECT forms

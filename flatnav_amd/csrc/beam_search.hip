@@ -152,6 +152,7 @@ const KernelTable& kernel_table(int, int, bool = false) {
         k.select[c][f] = FNV_DEV_KERNEL(wire_select_kernel);
         k.connect[c][f] = FNV_DEV_KERNEL(wire_connect_kernel);
         k.flat[c][f] = FNV_DEV_KERNEL(exhaustive_scan_kernel);
+        k.flat_g[c][f] = FNV_DEV_KERNEL(exhaustive_scan_grouped_kernel);
       }
     return k;
   }();
@@ -222,6 +223,12 @@ struct PlannedLaunch : LaunchPlan {
 struct SearchFilter {
   const uint8_t* bits;  // byte L >> 3, bit L & 7 = label L allowed (null when n_bits == 0)
   uint64_t n_bits;
+  // Grouped calls (fnv_search_batch_*_grouped): `bits` is a table of n_filters such bitmaps `stride` bytes apart, and query q
+  // uses the one query_filter[q] names (scan_select.hpp, filter_row).  A single-filter call is not a grouped call with one row.
+  bool grouped = false;
+  uint64_t n_filters = 0, stride = 0;
+  const int32_t* query_filter = nullptr;  // [nq]
+  uint64_t rows() const { return n_filters + 2; }  // the node bitmaps of a grouped launch
 };
 
 // Where a search writes: [nq][K] distances and labels, and per query (each optional) the result count and the counters.
@@ -351,14 +358,20 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
     DeviceBuf spill;   // uint64 [nslots][spill_entries]: what the candidates heap does not keep in LDS
     DeviceBuf tielog;  // uint64, merged-beam kernel: [nslots][log_entries] hand-over log (round 5)
     DeviceBuf scan;    // uint64, exhaustive search: [nq][segments][K] partial lists (scan.hpp)
-    size_t bytes() const { return bitmap.bytes + ovf.bytes + spill.bytes + tielog.bytes + scan.bytes; }
-    size_t release() { return bitmap.release() + ovf.release() + spill.release() + tielog.release() + scan.release(); }
+    DeviceBuf group;   // uint32, grouped exhaustive search: the grouping arrays (GroupArrays), O(nq + n_filters)
+    DeviceBuf rows;    // uint32, grouped searches: [n_filters + 2][capacity / 32] node bitmaps (node_filter_table_kernel) -- here,
+                       // not in d_nodebits: the caller's n_filters sizes them, so lane admission and ws_bytes must see them
+    size_t bytes() const { return bitmap.bytes + ovf.bytes + spill.bytes + tielog.bytes + scan.bytes + group.bytes + rows.bytes; }
+    size_t release() {
+      return bitmap.release() + ovf.release() + spill.release() + tielog.release() + scan.release() + group.release() + rows.release();
+    }
   } ws;
   // further buffers, each grown on demand
   DeviceBuf d_entry;      // [nq] uint32 entry nodes | [nq] float entry distances (K0 output)
   DeviceBuf d_done;       // uint32, shadow mode: [nq] "answered" flags
   DeviceBuf d_nodebits;   // uint32, filtered search: [capacity / 32] words, bit per node id (node_filter_kernel)
-  DeviceBuf d_allowed;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM
+  DeviceBuf d_allowed;    // filtered search, host-buffer entry point: the caller's label bitmap staged in HBM (grouped calls:
+                          // the filter table, then query_filter)
   DeviceBuf d_scanids;    // uint32, filtered exhaustive search: [0] the count, [4 ...) the allowed node ids (capacity of them)
   DeviceBuf d_wirebuf;    // fnv_index_insert_batch: [count*keep] x {req_target, req_index, sorted_target, sorted_req} | sort scratch
   DeviceBuf d_nodestage;  // write_nodes: AoS staging chunk + bad flag + "not lossless" flag of the mirror's conversion
@@ -1130,6 +1143,46 @@ static int grow_workspace(fnv_index_s* ix, uint32_t max_slots, uint64_t nq, bool
 
 // (d) Small launches on small indexes run the kernel's DIRECT form on a bitmap of all node ids: lay_out_direct (launch_plan.hpp).
 
+// ---- grouped filters: the node bitmaps of a launch with one filter per query ---------------------------------------
+// ws.rows for the n_filters + 2 rows of a grouped launch.  The one allocation of the library whose size the caller's
+// n_filters decides: its failure says how much that was, and a host-buffer caller's lane is admitted with it counted.
+static size_t filter_rows_bytes(const fnv_index_s* ix, const SearchFilter& f) {
+  return (size_t)f.rows() * (size_t)((ix->capacity + 31) / 32) * 4;
+}
+static int grow_filter_rows(fnv_index_s* ix, const SearchFilter& f) {
+  const size_t need = filter_rows_bytes(ix, f);
+  const int rc = ix->ws.rows.grow(need);
+  ix->ws_bytes = ix->ws.bytes();
+  if (rc == FNV_OK) return FNV_OK;
+  (void)hipGetLastError();
+  return fail(FNV_ERR_RUNTIME, "the filter rows of this launch need " + std::to_string(need) + " bytes of device memory (" +
+                                   std::to_string(f.rows()) + " node bitmaps), which could not be allocated");
+}
+// ... filled from the filter table and the labels as they are now; row_count (null: not wanted, else zero): nodes set per row
+static int launch_filter_rows(fnv_index_s* ix, const SearchFilter& f, uint64_t live, hipStream_t stream, uint32_t* row_count) {
+  const uint64_t words = (ix->capacity + 31) / 32;
+  const dim3 grid((unsigned)((words * 32 + 255) / 256), (unsigned)std::min<uint64_t>(f.rows(), 65535));
+  hipLaunchKernelGGL(node_filter_table_kernel, grid, dim3(256), 0, stream, (const int32_t*)ix->d_labels, live, words, f.bits, f.stride,
+                     f.n_bits, (uint32_t)f.n_filters, ix->ws.rows.as<uint32_t>(), row_count);
+  HIP_TRY(hipGetLastError());
+  return FNV_OK;
+}
+// The grouping arrays of a grouped scan (scan.hpp's group_* kernels), as uint32 offsets into one buffer.
+struct GroupArrays {
+  size_t query_row, perm, counts, cursor, row_count, slot_start, tile_start, tiles, bytes;
+  GroupArrays(uint64_t nq, uint64_t rows, uint64_t tile_bound) {
+    query_row = 0;
+    perm = query_row + nq;
+    counts = perm + nq;  // counts | cursor | row_count: cleared by one memset
+    cursor = counts + rows;
+    row_count = cursor + rows;
+    slot_start = row_count + rows;
+    tile_start = slot_start + rows + 1;
+    tiles = tile_start + rows + 1;
+    bytes = (tiles + 3 * tile_bound) * 4;
+  }
+};
+
 // ---- exhaustive search (scan.hpp): the launch ---------------------------------------------------------------------
 // How a launch of `nq` queries for K results is cut up: queries per tile (as many as a block's LDS budget holds next to their
 // result lists, at most 32), row segments (enough blocks to fill the device, at most 64 and at most what keeps the partial
@@ -1140,13 +1193,16 @@ constexpr uint64_t kScanPartialBudget = 256ull << 20;
 struct ScanShape {
   uint32_t tile, tiles, segments, lds;
 };
-static ScanShape scan_shape(const fnv_index_s* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
+// `filter_rows` != 0: a grouped launch over that many filter rows -- the id queue comes out of the block's LDS budget, and
+// `tiles` is the bound on the data-dependent tile count that the launch covers (scan_select.hpp, group_tile_bound).
+static ScanShape scan_shape(const fnv_index_s* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows = 0) {
   ScanShape s;
   const uint32_t per_query = g.q_chunks * 16u + (uint32_t)K * 8u;
-  s.tile = std::max(1u, std::min(kScanMaxTile, kScanLdsBudget / per_query));
+  const uint32_t queue = filter_rows ? SCAN_QUEUE_IDS * 4u : 0u;
+  s.tile = std::max(1u, std::min(kScanMaxTile, (kScanLdsBudget - queue) / per_query));
   s.tile = (uint32_t)std::min<uint64_t>(s.tile, nq);
-  s.lds = s.tile * per_query;
-  s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);
+  s.lds = s.tile * per_query + queue;
+  s.tiles = (uint32_t)(filter_rows ? group_tile_bound(nq, filter_rows, s.tile) : (nq + s.tile - 1) / s.tile);
   uint64_t seg;
   if (ix->scan_segment_rows > 0) {
     seg = std::min<uint64_t>((live + (uint64_t)ix->scan_segment_rows - 1) / (uint64_t)ix->scan_segment_rows, kScanForcedSegments);
@@ -1173,13 +1229,18 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const SearchFilter* filter = opt.filter;
   const uint64_t live = ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load();  // a view follows its source's growth
   const RowGeometry g = row_geometry(ix);
-  const ScanShape shape = scan_shape(ix, g, nq, K, live);
+  const bool grouped = filter && filter->grouped;
+  const ScanShape shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
   if (shape.lds > 160u * 1024u) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
   const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
+  const scan_grouped_fn kern_g = kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full];
+  const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
   int rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
-  if (!rc && filter) rc = ix->d_nodebits.grow((size_t)(ix->capacity + 31) / 32 * 4);
-  if (!rc && filter) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
+  if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
+  if (!rc && grouped) rc = ix->ws.group.grow(ga.bytes);
+  if (!rc && filter && !grouped) rc = ix->d_nodebits.grow((size_t)(ix->capacity + 31) / 32 * 4);
+  if (!rc && filter && !grouped) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
   ix->ws_bytes = ix->ws.bytes();
   if (rc) return rc;
 
@@ -1207,7 +1268,31 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   p.tiles = shape.tiles;
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));  // (the status word: this path never sets it)
-  if (filter) {  // the label bitmap -> this handle's node bitmap -> the list of allowed node ids
+  GroupedScanParams gp;
+  memset(&gp, 0, sizeof(gp));
+  if (grouped) {  // the filter table -> this handle's node bitmaps and their popcounts; the queries grouped by row into tiles
+    uint32_t* const w = ix->ws.group.as<uint32_t>();
+    const uint32_t rows = (uint32_t)filter->rows(), n = (uint32_t)nq;
+    HIP_TRY(hipMemsetAsync(w + ga.counts, 0, (size_t)3 * rows * 4, stream));  // counts | cursor | row_count
+    rc = launch_filter_rows(ix, *filter, live, stream, w + ga.row_count);
+    if (rc) return rc;
+    hipLaunchKernelGGL(group_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, filter->query_filter, n,
+                       (uint32_t)filter->n_filters, w + ga.query_row, w + ga.counts);
+    hipLaunchKernelGGL(group_prefix_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t*)(w + ga.counts), rows, shape.tile,
+                       w + ga.slot_start, w + ga.tile_start);
+    hipLaunchKernelGGL(group_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t*)(w + ga.query_row), n,
+                       (const uint32_t*)(w + ga.slot_start), w + ga.cursor, w + ga.perm);
+    hipLaunchKernelGGL(group_tiles_kernel, dim3((shape.tiles + 255) / 256), dim3(256), 0, stream, (const uint32_t*)(w + ga.slot_start),
+                       (const uint32_t*)(w + ga.tile_start), rows, shape.tile, shape.tiles, (GroupTile*)(w + ga.tiles));
+    HIP_TRY(hipGetLastError());
+    gp.node_bits = ix->ws.rows.as<uint32_t>();
+    gp.tiles = (const GroupTile*)(w + ga.tiles);
+    gp.perm = w + ga.perm;
+    gp.query_row = w + ga.query_row;
+    gp.row_count = w + ga.row_count;
+    gp.row_words = (uint32_t)((ix->capacity + 31) / 32);
+    gp.live_words = (uint32_t)((live + 31) / 32);
+  } else if (filter) {  // the label bitmap -> this handle's node bitmap -> the list of allowed node ids
     const uint64_t words = (ix->capacity + 31) / 32;
     uint32_t* const ids = ix->d_scanids.as<uint32_t>();
     hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
@@ -1222,11 +1307,19 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   }
   ix->sample_kernel = -1;  // ev0 / ev1 no longer bracket a graph-search launch: a pending sample of the adaptive choice is dropped
   HIP_TRY(hipEventRecord(ix->ev0, stream));
-  HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
-  hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, p);
-  HIP_TRY(hipGetLastError());
   const uint32_t merge_lds = 3u * (uint32_t)K * 8u;
-  hipLaunchKernelGGL(exhaustive_merge_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, p);
+  if (grouped) {
+    gp.s = p;
+    HIP_TRY(raise_lds_limit((const void*)kern_g, ix->device, shape.lds));
+    hipLaunchKernelGGL(kern_g, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(exhaustive_merge_grouped_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, gp);
+  } else {
+    HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
+    hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(exhaustive_merge_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, p);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ix->ev1, stream));
   ix->last_stream = stream;
@@ -1237,6 +1330,11 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   ix->geom[2] = shape.lds;
   for (int i = 3; i < 8; i++) ix->geom[i] = 0;
   ix->geom[6] = 3;  // (fnv_last_launch_geometry: the exhaustive scan)
+  if (grouped) {    // ... its grouped form: queries per tile, entries of the id queue, row segments
+    ix->geom[3] = shape.tile;
+    ix->geom[4] = SCAN_QUEUE_IDS;
+    ix->geom[5] = shape.segments;
+  }
   return FNV_OK;
 }
 
@@ -1287,7 +1385,9 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   const bool small_launch = shape.small_launch, shadow = shape.shadow;
   const uint32_t nslots = shape.nslots, tail_shadows = shape.tail_shadows;
 
-  rc = grow_workspace(ix, shape.max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr);
+  const bool grouped = filter && filter->grouped;
+  rc = grow_workspace(ix, shape.max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr && !grouped);
+  if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
   if (rc) return rc;
 
   SearchParams p = sorted ? plan.sorted : plan.heaps;
@@ -1319,7 +1419,14 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   p.tail_exact = shape.tail_exact;
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));
-  if (filter) {  // the label bitmap -> this handle's node bitmap (labels as they are now: after reorder(), device builds ...)
+  if (grouped) {  // the filter table -> this handle's node bitmaps; every query reads its own row
+    rc = launch_filter_rows(ix, *filter, live, stream, nullptr);
+    if (rc) return rc;
+    p.node_bits = ix->ws.rows.as<uint32_t>();
+    p.query_filter = filter->query_filter;
+    p.filter_words = (uint32_t)((ix->capacity + 31) / 32);
+    p.n_filters = (uint32_t)filter->n_filters;
+  } else if (filter) {  // the label bitmap -> this handle's node bitmap (labels as they are now: after reorder(), device builds ...)
     const uint64_t words = (ix->capacity + 31) / 32;
     hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
                        live, words, filter->bits, filter->n_bits, ix->d_nodebits.as<uint32_t>());
@@ -1412,7 +1519,24 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   SearchFilter dev_filter{nullptr, 0};
   SearchOptions opt;
   opt.exhaustive = exhaustive;
-  if (host_filter) {
+  const bool grouped = host_filter && host_filter->grouped;
+  if (grouped) {  // the filter table (its rows `stride` apart, as the caller has them), then query_filter, through d_allowed
+    const size_t row_bytes = (size_t)((host_filter->n_bits + 7) / 8);
+    const size_t tbytes = host_filter->n_filters && row_bytes ? (size_t)(host_filter->n_filters - 1) * host_filter->stride + row_bytes : 0;
+    const size_t qf_off = (tbytes + 15) & ~(size_t)15;
+    {
+      std::lock_guard<std::mutex> lock(ix->mu);
+      int rc = ix->d_allowed.grow(qf_off + (size_t)nq * 4);
+      if (rc) return rc;
+    }
+    uint8_t* const base = ix->d_allowed.as<uint8_t>();
+    if (tbytes) HIP_TRY(hipMemcpyAsync(base, host_filter->bits, tbytes, hipMemcpyHostToDevice, ix->stream));
+    HIP_TRY(hipMemcpyAsync(base + qf_off, host_filter->query_filter, (size_t)nq * 4, hipMemcpyHostToDevice, ix->stream));
+    dev_filter = *host_filter;
+    dev_filter.bits = tbytes ? base : nullptr;
+    dev_filter.query_filter = (const int32_t*)(base + qf_off);
+    opt.filter = &dev_filter;
+  } else if (host_filter) {
     const size_t fbytes = (size_t)((host_filter->n_bits + 7) / 8);
     if (fbytes) {
       {
@@ -1458,7 +1582,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   // size (round 6): the kernel reads the queries from and writes the results into the caller's own memory -- each query
   // crosses PCIe once while the launch runs, nothing is copied before or after it.  (Batches that fit the staging buffer take
   // the path below whatever their memory is: one attribute query per array costs more than their copies.)
-  if (!pinned && ix->host_zero_copy != 0) {
+  if (!pinned && ix->host_zero_copy != 0 && !grouped) {  // (grouped calls: always the staged copies)
     auto device_view = [](const void* host) -> void* {
       if (!host) return nullptr;
       hipPointerAttribute_t a;
@@ -1489,7 +1613,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   // time +0-3 %, wall time of a call -13 ... -40 us at every batch size from 1 to 1024 queries (one query: 0.157 -> 0.143 ms
   // at ef=50; 64: 0.24-0.26 -> 0.215 ms; 1024: 0.446 -> 0.405 ms).
   uint8_t* h = (uint8_t*)ix->h_pin;  // (small batches)
-  if (pinned && nq <= (uint64_t)ix->host_zero_copy) {
+  if (pinned && nq <= (uint64_t)ix->host_zero_copy && !grouped) {
     memcpy(h + qoff, queries, qbytes);
     *(int32_t*)(h + soff) = ST_OK;
     const SearchOutputs pin_slab = lay_out_slab(h + ooff, nq, K);
@@ -1595,7 +1719,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
     // Admission, reservation and creation happen under lane_mu: two concurrent callers cannot both pass the budget
     // test, and a batch that fits no lane (large index, FLATNAV_LANE_BUDGET_MB=0) creates none.  Lock order: lane_mu, then a
     // lane's host_mu by try_lock only (fnv_tune takes lane_mu, then every lane's host_mu, blocking).
-    const size_t need = launch_workspace_bytes(ix, nq);
+    const size_t need = launch_workspace_bytes(ix, nq) + (host_filter && host_filter->grouped ? filter_rows_bytes(ix, *host_filter) : 0);
     if (need <= ix->lane_budget_bytes) {
       std::lock_guard<std::mutex> admission(ix->lane_mu);
       for (int which = 1; which < fnv_index_s::kMaxLanes; which++) {
@@ -1720,6 +1844,86 @@ int fnv_search_batch_exhaustive_device(fnv_index_t ix, const void* d_queries, ui
   const SearchFilter f{n_bits ? (const uint8_t*)d_allowed_bits : nullptr, n_bits};
   SearchOptions opt;
   opt.filter = use_filter ? &f : nullptr;
+  opt.exhaustive = true;
+  return search_device_impl(ix, d_queries, nq, K, 1, 1, SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, nullptr},
+                            hip_stream, opt);
+}
+
+// ---- grouped filters: a table of allowed sets and, per query, which of them it uses ----------------------------------
+static int check_grouped_args(const void* filters, uint64_t n_filters, uint64_t stride, uint64_t n_bits, const int32_t* query_filter,
+                              uint64_t nq, SearchFilter* out) {
+  if (n_bits > (1ull << 31)) return fail(FNV_ERR_INVALID, "n_bits must be at most 2^31 (labels are int32)");
+  if (n_filters > 0x7FFFFFFFull) return fail(FNV_ERR_INVALID, "n_filters must be at most 2^31 - 1 (query_filter is int32)");
+  if (n_filters > 0 && stride < (n_bits + 7) / 8) return fail(FNV_ERR_INVALID, "filter_stride_bytes is smaller than ceil(n_bits / 8)");
+  if (n_filters > 0 && n_bits > 0 && !filters) return fail(FNV_ERR_INVALID, "filters is null but n_filters > 0 and n_bits > 0");
+  if (nq > 0 && !query_filter) return fail(FNV_ERR_INVALID, "query_filter is null");
+  *out = SearchFilter{n_filters && n_bits ? (const uint8_t*)filters : nullptr, n_bits};
+  out->grouped = true;
+  out->n_filters = n_filters;
+  out->stride = stride;
+  out->query_filter = query_filter;
+  return FNV_OK;
+}
+// (host entry points: the array is theirs to read before anything is launched)
+static int check_query_filter_values(const int32_t* query_filter, uint64_t nq, uint64_t n_filters) {
+  for (uint64_t q = 0; q < nq; q++)
+    if (query_filter[q] < -1 || (int64_t)query_filter[q] >= (int64_t)n_filters)
+      return fail(FNV_ERR_INVALID, "query_filter[" + std::to_string(q) + "] = " + std::to_string(query_filter[q]) +
+                                       " is neither -1 nor a filter of the table (n_filters = " + std::to_string(n_filters) + ")");
+  return FNV_OK;
+}
+
+int fnv_search_batch_filtered_grouped(fnv_index_t ix, const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                                      const void* filters, uint64_t n_filters, uint64_t filter_stride_bytes, uint64_t n_bits,
+                                      const int32_t* query_filter, float* out_dist, int32_t* out_labels, int32_t* out_count,
+                                      uint64_t* out_ndist, uint64_t* out_nhops) {
+  SearchFilter f{nullptr, 0};
+  int rc = check_grouped_args(filters, n_filters, filter_stride_bytes, n_bits, query_filter, nq, &f);
+  if (!rc) rc = check_search_args(ix, queries, nq, K, ef_search, num_initializations, out_dist, out_labels);
+  if (!rc) rc = check_query_filter_values(query_filter, nq, n_filters);
+  if (rc) return rc;
+  return search_batch_host(ix, queries, nq, K, ef_search, num_initializations,
+                           SearchOutputs{out_dist, out_labels, out_count, out_ndist, out_nhops}, &f);
+}
+
+int fnv_search_batch_filtered_grouped_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search,
+                                             int num_initializations, const void* d_filters, uint64_t n_filters,
+                                             uint64_t filter_stride_bytes, uint64_t n_bits, const int32_t* d_query_filter,
+                                             float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count, uint64_t* d_out_ndist,
+                                             uint64_t* d_out_nhops, void* hip_stream) {
+  if (!ix) return fail(FNV_ERR_INVALID, "index is null");
+  SearchFilter f{nullptr, 0};
+  int rc = check_grouped_args(d_filters, n_filters, filter_stride_bytes, n_bits, d_query_filter, nq, &f);
+  if (rc) return rc;
+  SearchOptions opt;
+  opt.filter = &f;
+  return search_device_impl(ix, d_queries, nq, K, ef_search, num_initializations,
+                            SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, d_out_nhops}, hip_stream, opt);
+}
+
+int fnv_search_batch_exhaustive_grouped(fnv_index_t ix, const void* queries, uint64_t nq, int K, const void* filters, uint64_t n_filters,
+                                        uint64_t filter_stride_bytes, uint64_t n_bits, const int32_t* query_filter, float* out_dist,
+                                        int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist) {
+  SearchFilter f{nullptr, 0};
+  int rc = check_exhaustive_args(ix, K, 0, nullptr, 0);
+  if (!rc) rc = check_grouped_args(filters, n_filters, filter_stride_bytes, n_bits, query_filter, nq, &f);
+  if (!rc && nq && (!queries || !out_dist || !out_labels)) rc = fail(FNV_ERR_INVALID, "null buffer");
+  if (!rc) rc = check_query_filter_values(query_filter, nq, n_filters);
+  if (rc) return rc;
+  return search_batch_host(ix, queries, nq, K, /*ef_search=*/1, /*num_initializations=*/1,
+                           SearchOutputs{out_dist, out_labels, out_count, out_ndist, nullptr}, &f, true);
+}
+
+int fnv_search_batch_exhaustive_grouped_device(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, const void* d_filters,
+                                               uint64_t n_filters, uint64_t filter_stride_bytes, uint64_t n_bits,
+                                               const int32_t* d_query_filter, float* d_out_dist, int32_t* d_out_labels,
+                                               int32_t* d_out_count, uint64_t* d_out_ndist, void* hip_stream) {
+  SearchFilter f{nullptr, 0};
+  int rc = check_exhaustive_args(ix, K, 0, nullptr, 0);
+  if (!rc) rc = check_grouped_args(d_filters, n_filters, filter_stride_bytes, n_bits, d_query_filter, nq, &f);
+  if (rc) return rc;
+  SearchOptions opt;
+  opt.filter = &f;
   opt.exhaustive = true;
   return search_device_impl(ix, d_queries, nq, K, 1, 1, SearchOutputs{d_out_dist, d_out_labels, d_out_count, d_out_ndist, nullptr},
                             hip_stream, opt);

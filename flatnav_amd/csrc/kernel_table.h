@@ -12,6 +12,7 @@ namespace fnv_dev {
 typedef void (*kernel_fn)(const SearchParams);
 typedef void (*wire_fn)(const WireParams);
 typedef void (*scan_fn)(const ScanParams);
+typedef void (*scan_grouped_fn)(const GroupedScanParams);
 
 // All kernels for one (element type, metric): [row configuration][FULL rows].
 struct KernelTable {
@@ -22,6 +23,7 @@ struct KernelTable {
   wire_fn select[kNumCfgs][2];         // wire_select_kernel
   wire_fn connect[kNumCfgs][2];        // wire_connect_kernel
   scan_fn flat[kNumCfgs][2];           // exhaustive_scan_kernel (scan.hpp: the exhaustive search)
+  scan_grouped_fn flat_g[kNumCfgs][2]; // exhaustive_scan_grouped_kernel (... with one filter per query)
 };
 
 // X(element type, type tag, metric ordinal, metric tag)
@@ -32,11 +34,12 @@ struct KernelTable {
 // The kernel families, X(ordinal, name): one compilation of kernel_inst.hip (-DFNV_INST_FAMILY=ordinal -DFNV_INST_FNAME=name)
 // per family and (type, metric) defines the filler fill_<name>_<type tag>_<metric tag>.  0 the exact two-heap kernel + entry
 // scan, 12 its filtered form, 3 the wiring kernels, 4-7 the merged beam in MB_R / 1 / 0 (LDS) / 2 register chunks, 8-11 the
-// DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS), 13 the exhaustive search's scan.
+// DIRECT forms of 4-7 (small launches on small indexes: the visited set is a bitmap in LDS), 13 the exhaustive search's scan, 14 its grouped form.
 #define FNV_FOR_EACH_FAMILY(X, ...)                                                                              \
   X(0, exact, __VA_ARGS__) X(12, exact_f, __VA_ARGS__) X(3, wire, __VA_ARGS__) X(4, merged, __VA_ARGS__)         \
   X(5, merged1, __VA_ARGS__) X(6, merged0, __VA_ARGS__) X(7, merged2, __VA_ARGS__) X(8, merged_d, __VA_ARGS__)   \
-  X(9, merged1_d, __VA_ARGS__) X(10, merged0_d, __VA_ARGS__) X(11, merged2_d, __VA_ARGS__) X(13, scan, __VA_ARGS__)
+  X(9, merged1_d, __VA_ARGS__) X(10, merged0_d, __VA_ARGS__) X(11, merged2_d, __VA_ARGS__) X(13, scan, __VA_ARGS__)   \
+  X(14, scan_g, __VA_ARGS__)
 
 // The row format f32h (float32 queries on the half-width mirror of a float32 table, half_rows.hpp) has the exact family (without
 // the entry scan) and the merged-beam families with their DIRECT forms only, for the FULL rows with an even CU; its tables'

@@ -3,6 +3,7 @@
 #pragma once
 #include "distance.hpp"
 #include "heaps.hpp"
+#include "scan_select.hpp"
 #include "visited.hpp"
 namespace fnv_dev {
 
@@ -384,9 +385,12 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
   uint32_t vis_count = 1;
   bool ovf = false;       // 32-bit table: switched to the bitmap; tagged: some id went to the bitmap
   uint32_t n_dist = 0, n_hops = 0;
-  const uint32_t* const node_bits = FILTER ? cold_args()->node_bits : nullptr;
+  const uint32_t* node_bits = FILTER ? cold_args()->node_bits : nullptr;
   bool entry_allowed = true;
   if (FILTER) {  // the entry navigates either way; it is a result only if allowed (max_dist starts at its distance regardless)
+    // (grouped launches: this query's own row of the bitmap table; qi is a real query index -- filtered launches have no shadows)
+    if (const int32_t* const qf = cold_args()->query_filter)
+      node_bits += (uint64_t)filter_row(rfl((int)qf[qi]), cold_args()->n_filters) * cold_args()->filter_words;
     entry_allowed = (rfl((int)node_bits[entry >> 5]) >> (entry & 31)) & 1;
     if (!entry_allowed) s.nbr_n = 0;
   }

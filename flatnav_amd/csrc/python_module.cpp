@@ -226,6 +226,92 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     return py::make_tuple(dist, labels);
   }
 
+  // `filters` (a sequence of what packAllowed takes, or a 2-D bool mask [F, labels]) -> the C ABI's filter table: F rows of
+  // `stride` bytes, n_bits = the largest of the filters' own
+  static void packFilters(const py::object& filters_obj, std::vector<uint8_t>& table, uint64_t& n_filters, uint64_t& stride,
+                          uint64_t& n_bits) {
+    std::vector<std::vector<uint8_t>> rows;
+    n_bits = 0;
+    auto add = [&](const py::handle& one) {
+      py::array a = py::array::ensure(one);
+      if (!a) throw std::invalid_argument("a filter must be a bool mask or an integer array of labels.");
+      rows.emplace_back();
+      uint64_t nb = 0;
+      packAllowed(a, rows.back(), nb);
+      n_bits = std::max(n_bits, nb);
+    };
+    if (py::isinstance<py::array>(filters_obj) && py::reinterpret_borrow<py::array>(filters_obj).ndim() == 2) {
+      py::array mask = py::reinterpret_borrow<py::array>(filters_obj);
+      if (mask.dtype().kind() != 'b') throw std::invalid_argument("a 2-D filter table must be a bool mask [filters, labels].");
+    }
+    for (py::handle one : filters_obj) add(one);
+    n_filters = rows.size();
+    stride = (n_bits + 7) / 8;
+    table.assign(static_cast<size_t>(n_filters * stride), 0);
+    for (size_t f = 0; f < rows.size(); ++f) std::copy(rows[f].begin(), rows[f].end(), table.begin() + static_cast<py::ssize_t>(f * stride));
+  }
+  static std::vector<int32_t> queryFilter(const py::array& qf_any, py::ssize_t nq, uint64_t n_filters) {
+    if (qf_any.ndim() != 1 || qf_any.shape(0) != nq) throw std::invalid_argument("query_filter must hold one entry per query.");
+    if (qf_any.size() && qf_any.dtype().kind() != 'i' && qf_any.dtype().kind() != 'u')
+      throw std::invalid_argument("query_filter must be an integer array.");
+    auto v = qf_any.cast<dense_array<int64_t>>();
+    std::vector<int32_t> out(static_cast<size_t>(nq));
+    for (py::ssize_t q = 0; q < nq; ++q) {
+      if (v.data()[q] < -1 || v.data()[q] >= static_cast<int64_t>(n_filters))
+        throw std::invalid_argument("query_filter[" + std::to_string(q) + "] is neither -1 nor a filter of the table.");
+      out[static_cast<size_t>(q)] = static_cast<int32_t>(v.data()[q]);
+    }
+    return out;
+  }
+
+  // search_filtered_grouped(queries, K, ef_search, filters, query_filter, num_initializations=100): search_filtered with one
+  // allowed set per query (query_filter[q] = its filter's row in `filters`, -1 = none), in one launch.
+  py::tuple searchFilteredGrouped(const py::array& queries_any, int K, int ef_search, const py::object& filters_obj,
+                                  const py::array& query_filter_any, int num_initializations) {
+    py::array queries = elements(queries_any);
+    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
+    if (K <= 0) throw std::invalid_argument("K must be positive.");
+    std::vector<uint8_t> table;
+    uint64_t n_filters = 0, stride = 0, n_bits = 0;
+    packFilters(filters_obj, table, n_filters, stride, n_bits);
+    const py::ssize_t nq = queries.shape(0);
+    const std::vector<int32_t> qf = queryFilter(query_filter_any, nq, n_filters);
+    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
+    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
+    {
+      const void* qptr = queries.data();
+      float* dptr = dist.mutable_data();
+      int* lptr = labels.mutable_data();
+      py::gil_scoped_release release;
+      _index->searchBatchFilteredGrouped(qptr, static_cast<uint64_t>(nq), K, ef_search, num_initializations,
+                                         table.empty() ? nullptr : table.data(), n_filters, stride, n_bits, qf.data(), dptr, lptr, nullptr);
+    }
+    return py::make_tuple(dist, labels);
+  }
+
+  // search_exhaustive_grouped(queries, K, filters, query_filter): search_exhaustive with one allowed set per query.
+  py::tuple searchExhaustiveGrouped(const py::array& queries_any, int K, const py::object& filters_obj, const py::array& query_filter_any) {
+    py::array queries = elements(queries_any);
+    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
+    if (K <= 0 || K > 1024) throw std::invalid_argument("K of an exhaustive search must be between 1 and 1024.");
+    std::vector<uint8_t> table;
+    uint64_t n_filters = 0, stride = 0, n_bits = 0;
+    packFilters(filters_obj, table, n_filters, stride, n_bits);
+    const py::ssize_t nq = queries.shape(0);
+    const std::vector<int32_t> qf = queryFilter(query_filter_any, nq, n_filters);
+    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
+    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
+    {
+      const void* qptr = queries.data();
+      float* dptr = dist.mutable_data();
+      int* lptr = labels.mutable_data();
+      py::gil_scoped_release release;
+      _index->searchBatchExhaustiveGrouped(qptr, static_cast<uint64_t>(nq), K, table.empty() ? nullptr : table.data(), n_filters, stride,
+                                           n_bits, qf.data(), dptr, lptr, nullptr);
+    }
+    return py::make_tuple(dist, labels);
+  }
+
   // search_single(query, K, ef_search, num_initializations=100) -> (float32[K], int32[K])
   py::tuple searchSingle(const py::array& query_any, int K, int ef_search, int num_initializations) {
     py::array query = elements(query_any);
@@ -311,6 +397,14 @@ void bindIndex(py::module_& m, const char* name) {
            "Exact k-NN by one device scan over all nodes, or over the nodes whose label is allowed (`allowed` as for "
            "search_filtered) -> (distances[Q,K] float32, labels[Q,K] int32) sorted by (distance, node id), rows padded with "
            "(+inf, -1) when there are fewer than K candidates.  1 <= K <= 1024.")
+      .def("search_filtered_grouped", &T::searchFilteredGrouped, py::arg("queries"), py::arg("K"), py::arg("ef_search"),
+           py::arg("filters"), py::arg("query_filter"), py::arg("num_initializations") = 100,
+           "search_filtered with one allowed set per query, in one launch: `filters` = a sequence of filters (each as `allowed` of "
+           "search_filtered) or a 2-D bool mask [F, labels]; query_filter[q] = the filter query q uses, -1 = none.")
+      .def("search_exhaustive_grouped", &T::searchExhaustiveGrouped, py::arg("queries"), py::arg("K"), py::arg("filters"),
+           py::arg("query_filter"),
+           "search_exhaustive with one allowed set per query, in one launch (`filters` / `query_filter` as for "
+           "search_filtered_grouped; -1 = every node).  1 <= K <= 1024.")
       .def("get_query_distance_computations", &T::getQueryDistanceComputations,
            "Distance evaluations since the last call (needs collect_stats=True); resets the counter.")
       .def("save", &T::save, py::arg("filename"), "Write the index in flatnav's binary format.")

@@ -225,4 +225,36 @@ __global__ __launch_bounds__(256) void node_filter_kernel(const int32_t* labels,
   if ((lane & 31) == 0 && w < n_words) node_bits[w] = (uint32_t)(lane ? m >> 32 : m);
 }
 
+// Grouped filtered search: the same rule for a TABLE of n_filters label bitmaps (filter f at allowed_bits + f * stride_bytes,
+// one n_bits for all) in one launch, the filter on the grid's second dimension: node_bits[r][n_words].  Two fixed rows follow
+// the filters' (scan_select.hpp, filter_row): row n_filters holds every live node, row n_filters + 1 none.
+// row_count (null: not wanted) [n_filters + 2], zero at launch: the nodes set in each row -- the block's four wavefronts add up in
+// LDS first, so a row takes one global atomic per 256 nodes that has any bit set.
+__global__ __launch_bounds__(256) void node_filter_table_kernel(const int32_t* labels, uint64_t n_live, uint64_t n_words,
+                                                                const uint8_t* allowed_bits, uint64_t stride_bytes, uint64_t n_bits,
+                                                                uint32_t n_filters, uint32_t* node_bits, uint32_t* row_count) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & (WAVE - 1));
+  const uint64_t w = i >> 5;
+  const bool live = i < n_live;
+  const int32_t L = live ? labels[i] : -1;
+  const bool in_range = L >= 0 && (uint64_t)L < n_bits;
+  __shared__ uint32_t wave_pop[4];
+  for (uint32_t r = blockIdx.y; r < n_filters + 2u; r += gridDim.y) {  // (the grid's second dimension ends at 65535)
+    bool ok = live && r == n_filters;
+    if (r < n_filters && in_range) ok = (allowed_bits[(uint64_t)r * stride_bytes + ((uint32_t)L >> 3)] >> (L & 7)) & 1u;
+    const unsigned long long m = __ballot(ok);
+    if ((lane & 31) == 0 && w < n_words) node_bits[(uint64_t)r * n_words + w] = (uint32_t)(lane ? m >> 32 : m);
+    if (row_count) {  // (uniform over the block)
+      if (lane == 0) wave_pop[threadIdx.x / WAVE] = (uint32_t)__popcll(m);
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const uint32_t total = wave_pop[0] + wave_pop[1] + wave_pop[2] + wave_pop[3];
+        if (total) atomicAdd(row_count + r, total);
+      }
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace fnv_dev

@@ -155,7 +155,186 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
   }
 }
 
-#ifndef FNV_INST_FAMILY  // (the two kernels below are not templates: beam_search.hip alone emits them, not kernel_inst.hip's units)
+// ---- grouped filters: one allowed set per query (fnv_search_batch_exhaustive_grouped) --------------------------------------
+// One batch of VPW * PU queued node ids against the tile's nqb staged queries: exhaustive_scan_kernel's loop body -- the same
+// loads, the same per-lane chunk order, group_sum, scan_key and scan_insert, so a distance has the same bits -- with the ids
+// taken from ids[0, nvalid) (LDS) instead of a compacted list; slots from nvalid on repeat the last valid id with val = false.
+// (A copy, not a shared body: the plain scan's instantiations stay instruction for instruction what they were.  Only the GPU
+// tests hold the two bodies to the same bits: ANY change to the scoring of either must be made in both.)
+template <typename T, int METRIC, int G, int CU, bool FULL>
+__device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint4* qlds, uint64_t* lists, uint32_t nqb,
+                                                 const uint32_t* ids, uint32_t nvalid, int lane) {
+  constexpr int PU = passes<G, CU>();
+  constexpr int VPW = WAVE / G;
+  constexpr int SPAN = G * CU;
+  constexpr bool TAIL = row_has_tail<G, CU, FULL>();
+  typedef Dist<T, METRIC> D;
+  typedef typename D::acc_t acc_t;
+  const int g = lane % G, v = lane / G;
+  const int K = (int)p.K;
+  const uint32_t q_chunks = p.q_chunks;
+  const int nchunks = (int)p.nchunks;
+  const bool one_span = nchunks <= SPAN;
+  const uint32_t tc = p.tail_chunks;
+  uint32_t id[PU];
+  bool val[PU];
+  const uint8_t* rowp[PU];
+#pragma unroll
+  for (int pu = 0; pu < PU; pu++) {
+    const uint32_t slot = (uint32_t)(pu * VPW + v);
+    val[pu] = slot < nvalid;
+    id[pu] = ids[val[pu] ? slot : nvalid - 1u];
+    rowp[pu] = p.vectors + (uint64_t)id[pu] * p.row_bytes;
+  }
+  uint4 y[PU][CU], yt[PU];
+  auto load_span = [&](int c0) {
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++) {
+#pragma unroll
+      for (int cu = 0; cu < CU; cu++) {
+        const int c = c0 + cu * G + g;
+        y[pu][cu] = make_uint4(0u, 0u, 0u, 0u);
+        if (FULL || TAIL || c < nchunks) y[pu][cu] = *reinterpret_cast<const uint4*>(rowp[pu] + (uint32_t)c * 16u);
+      }
+    }
+  };
+  if (one_span) load_span(0);
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++) {
+      yt[pu] = make_uint4(0u, 0u, 0u, 0u);
+      if ((uint32_t)g < tc) yt[pu] = *reinterpret_cast<const uint4*>(p.tails + ((uint64_t)id[pu] * tc + (uint32_t)g) * 16u);
+    }
+  }
+  for (uint32_t qq = 0; qq < nqb; qq++) {
+    const uint4* qv = qlds + (size_t)qq * q_chunks;
+    acc_t acc[PU];
+    typename D::qacc_t qacc = D::qzero();
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++) acc[pu] = D::zero();
+    for (int c0 = 0; c0 < nchunks; c0 += SPAN) {
+      if (!one_span) load_span(c0);
+#pragma unroll
+      for (int cu = 0; cu < CU; cu++) {
+        const uint4 x = qv[c0 + cu * G + g];
+        qacc = D::qchunk(qacc, x);
+#pragma unroll
+        for (int pu = 0; pu < PU; pu++) acc[pu] = D::chunk(acc[pu], x, y[pu][cu]);
+      }
+    }
+    if constexpr (TAIL) {
+      const uint4 xt = qv[SPAN + g];
+      qacc = D::qchunk(qacc, xt);
+#pragma unroll
+      for (int pu = 0; pu < PU; pu++) acc[pu] = D::chunk(acc[pu], xt, yt[pu]);
+    }
+    uint64_t* const list = lists + (size_t)qq * K;
+    uint64_t kth = list[K - 1];
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++) {
+      const float d = D::finish(group_sum<G>(D::lane_sum(acc[pu], qacc)));
+      const uint64_t key = scan_key(__float_as_uint(d), id[pu]);
+      unsigned long long pm = __ballot(g == 0 && val[pu] && scan_key_less(key, kth));
+      while (pm) {
+        const int i = __ffsll((long long)pm) - 1;
+        pm &= pm - 1;
+        const uint64_t k = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), i) << 32) |
+                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, i);
+        if (scan_key_less(k, kth)) {
+          scan_insert(list, K, k, lane);
+          kth = list[K - 1];
+        }
+      }
+    }
+  }
+}
+
+// One wavefront per (tile descriptor, row segment).  The tile's queries all use one filter row; the block walks that row's
+// words over its segment of [0, live_words), 64 words a step, and turns set bits into node ids in an LDS queue: a wave prefix
+// over the words' popcounts gives every lane the place of its word's ids, the words that fit the queue's free room (a prefix of
+// the lanes) are appended, full batches are scored, what is left moves to the queue's front, until the step's words are used
+// up.  The last short batch is scored after the last word.  Which batch a node falls into never shows: the order is total.
+// LDS: the plain scan's [tile][q_chunks] queries and [tile][K] lists, then SCAN_QUEUE_IDS ids.
+template <typename T, int METRIC, int G, int CU, bool FULL>
+__global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const GroupedScanParams gp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr uint32_t BATCH = (uint32_t)(passes<G, CU>() * (WAVE / G));
+  static_assert(BATCH - 1u + 32u <= SCAN_QUEUE_IDS && BATCH <= (uint32_t)WAVE, "a word always fits behind the leftovers");
+  const ScanParams& p = gp.s;
+  const int lane = threadIdx.x;
+  const uint32_t seg = blockIdx.x / p.tiles;
+  const GroupTile t = gp.tiles[blockIdx.x % p.tiles];
+  const uint32_t nqb = t.count;
+  if (nqb == 0u) return;  // (past the real tiles: the launch is an upper bound)
+  const int K = (int)p.K;
+  const uint32_t q_chunks = p.q_chunks;
+  uint4* const qlds = reinterpret_cast<uint4*>(smem);
+  uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * q_chunks * 16u);
+  uint32_t* const queue = reinterpret_cast<uint32_t*>(lists + (size_t)p.tile_queries * K);
+  const uint32_t* const perm = gp.perm + t.first;
+
+  {  // the tile's queries, zero padded to q_chunks; every list empty
+    const int padded = (int)(q_chunks * 16u / sizeof(T));
+    const int dim = (int)p.dim;
+    for (uint32_t qq = 0; qq < nqb; qq++) {
+      const T* qsrc = reinterpret_cast<const T*>(p.queries) + (uint64_t)perm[qq] * p.dim;
+      T* qdst = reinterpret_cast<T*>(qlds + (size_t)qq * q_chunks);
+      for (int i = lane; i < padded; i += WAVE) qdst[i] = i < dim ? qsrc[i] : T(0);
+    }
+    for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) lists[i] = SCAN_PAD;
+  }
+  wave_sync();
+
+  const uint32_t* const bits = gp.node_bits + (uint64_t)t.row * gp.row_words;
+  const uint32_t wlo = (uint32_t)((uint64_t)gp.live_words * seg / p.segments);
+  const uint32_t whi = (uint32_t)((uint64_t)gp.live_words * (seg + 1) / p.segments);
+  uint32_t count = 0;  // ids in the queue (wave-uniform)
+  for (uint32_t w0 = wlo; w0 < whi; w0 += WAVE) {
+    const uint32_t w = w0 + (uint32_t)lane;
+    uint32_t word = w < whi ? bits[w] : 0u;
+    while (__ballot(word != 0u)) {
+      const uint32_t pc = (uint32_t)__popc(word);
+      uint32_t incl = pc;  // ids of lanes [0, lane]
+#pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, off, WAVE);
+        if (lane >= off) incl += up;
+      }
+      const bool fits = count + incl <= SCAN_QUEUE_IDS;  // (incl never decreases along the lanes: a prefix of them)
+      const int nfit = __popcll(__ballot(fits));          // >= 1 word with ids: count < BATCH here
+      if (fits) {
+        uint32_t at = count + incl - pc;
+        while (word) {
+          queue[at++] = w * 32u + (uint32_t)(__ffs((int)word) - 1);
+          word &= word - 1u;
+        }
+      }
+      count += (uint32_t)__shfl((int)incl, nfit - 1, WAVE);
+      wave_sync();
+      uint32_t head = 0;
+      for (; count - head >= BATCH; head += BATCH)
+        scan_score_batch<T, METRIC, G, CU, FULL>(p, qlds, lists, nqb, queue + head, BATCH, lane);
+      if (head) {  // the leftovers (fewer than a batch) to the front
+        const uint32_t rem = count - head;
+        uint32_t keep = 0;
+        if ((uint32_t)lane < rem) keep = queue[head + lane];
+        wave_sync();
+        if ((uint32_t)lane < rem) queue[lane] = keep;
+        wave_sync();
+        count = rem;
+      }
+    }
+  }
+  if (count) scan_score_batch<T, METRIC, G, CU, FULL>(p, qlds, lists, nqb, queue, count, lane);
+
+  wave_sync();
+  for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) {
+    const uint32_t qq = i / (uint32_t)K, k = i % (uint32_t)K;
+    p.partial[((uint64_t)perm[qq] * p.segments + seg) * (uint64_t)K + k] = lists[i];
+  }
+}
+
+#ifndef FNV_INST_FAMILY  // (the kernels below are not templates: beam_search.hip alone emits them, not kernel_inst.hip's units)
 // The allowed node ids of a node bitmap (bit i & 31 of word i >> 5), compacted wave by wave: the order is whatever the
 // atomics make it, which the selection does not see.  *count must be zero at launch; ids holds n_live entries.
 static __global__ __launch_bounds__(256) void exhaustive_compact_kernel(const uint32_t* node_bits, uint64_t n_live, uint32_t* ids,
@@ -172,9 +351,9 @@ static __global__ __launch_bounds__(256) void exhaustive_compact_kernel(const ui
 }
 
 // One wavefront per query: its `segments` sorted lists -> the K first of their union -> the caller's arrays.
-// LDS: three lists of K keys.
-static __global__ __launch_bounds__(WAVE) void exhaustive_merge_kernel(const ScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// LDS: three lists of K keys.  `candidates()`: how many the query had (out_count / out_ndist), read once the lists are merged.
+template <typename F>
+__device__ __forceinline__ void scan_merge_query(const ScanParams& p, unsigned char* smem, F candidates) {
   const int lane = threadIdx.x;
   const uint32_t q = blockIdx.x, K = p.K;
   uint64_t* a = reinterpret_cast<uint64_t*>(smem);
@@ -199,7 +378,7 @@ static __global__ __launch_bounds__(WAVE) void exhaustive_merge_kernel(const Sca
     a = b;
     b = t;
   }
-  const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
+  const uint64_t ncand = candidates();
   for (uint32_t k = lane; k < K; k += WAVE) {
     const uint64_t key = a[k];
     float od = std::numeric_limits<float>::infinity();
@@ -216,6 +395,73 @@ static __global__ __launch_bounds__(WAVE) void exhaustive_merge_kernel(const Sca
     if (p.out_count) p.out_count[q] = (int32_t)(ncand < (uint64_t)K ? ncand : (uint64_t)K);
     if (p.out_ndist) p.out_ndist[q] = ncand;
   }
+}
+static __global__ __launch_bounds__(WAVE) void exhaustive_merge_kernel(const ScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  scan_merge_query(p, smem, [&] { return p.cand_ids ? (uint64_t)*p.cand_count : p.n_live; });
+}
+// ... of a grouped launch: the candidates of a query are the nodes set in its filter row.
+static __global__ __launch_bounds__(WAVE) void exhaustive_merge_grouped_kernel(const GroupedScanParams gp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  scan_merge_query(gp.s, smem, [&] { return (uint64_t)gp.row_count[gp.query_row[blockIdx.x]]; });
+}
+
+// Grouping of a grouped launch's queries by filter row, in four small steps (rows = n_filters + 2; every array uint32):
+//   group_rows_kernel     query_row[q] = filter_row(query_filter[q]), counts[row]++          (counts zero at launch)
+//   group_prefix_kernel   slot_start / tile_start [rows + 1]: exclusive prefixes of the counts and of ceil(count / tile)
+//   group_scatter_kernel  perm: the query indices, contiguous per row, in whatever order the atomics leave inside a row
+//                         (results go out at the original query index)                          (cursor zero at launch)
+//   group_tiles_kernel    the `bound` tile descriptors (scan_select.hpp, group_tile_at)
+static __global__ __launch_bounds__(256) void group_rows_kernel(const int32_t* query_filter, uint32_t nq, uint32_t n_filters,
+                                                                uint32_t* query_row, uint32_t* counts) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const uint32_t r = filter_row(query_filter[q], n_filters);
+  query_row[q] = r;
+  atomicAdd(counts + r, 1u);
+}
+static __global__ __launch_bounds__(256) void group_prefix_kernel(const uint32_t* counts, uint32_t rows, uint32_t tile,
+                                                                  uint32_t* slot_start, uint32_t* tile_start) {
+  __shared__ uint32_t sc[256], st[256];
+  const uint32_t tid = threadIdx.x;
+  uint32_t carry_c = 0, carry_t = 0;
+  for (uint32_t base = 0; base < rows; base += 256u) {  // one block: 256 rows a step, Hillis-Steele inside it
+    const uint32_t g = base + tid;
+    const uint32_t c = g < rows ? counts[g] : 0u, t = (c + tile - 1u) / tile;
+    sc[tid] = c;
+    st[tid] = t;
+    __syncthreads();
+    for (uint32_t off = 1; off < 256u; off <<= 1) {
+      const uint32_t ac = tid >= off ? sc[tid - off] : 0u, at = tid >= off ? st[tid - off] : 0u;
+      __syncthreads();
+      sc[tid] += ac;
+      st[tid] += at;
+      __syncthreads();
+    }
+    if (g < rows) {
+      slot_start[g] = carry_c + sc[tid] - c;
+      tile_start[g] = carry_t + st[tid] - t;
+    }
+    carry_c += sc[255];
+    carry_t += st[255];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    slot_start[rows] = carry_c;
+    tile_start[rows] = carry_t;
+  }
+}
+static __global__ __launch_bounds__(256) void group_scatter_kernel(const uint32_t* query_row, uint32_t nq, const uint32_t* slot_start,
+                                                                   uint32_t* cursor, uint32_t* perm) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const uint32_t r = query_row[q];
+  perm[slot_start[r] + atomicAdd(cursor + r, 1u)] = q;
+}
+static __global__ __launch_bounds__(256) void group_tiles_kernel(const uint32_t* slot_start, const uint32_t* tile_start, uint32_t rows,
+                                                                 uint32_t tile, uint32_t bound, GroupTile* tiles) {
+  const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d < bound) tiles[d] = group_tile_at(d, slot_start, tile_start, rows, tile);
 }
 
 #endif  // FNV_INST_FAMILY

@@ -102,4 +102,75 @@ struct ScanParams {
   uint32_t tiles;              // ceil(nq / tile_queries)
 };
 
+// ---- grouped filters (fnv_search_batch_*_grouped): one allowed set per query ---------------------------------------------
+// A grouped launch keeps n_filters + 2 node bitmaps ("filter rows"): row f < n_filters is filter f, row n_filters holds every
+// live node (query_filter == -1: no filter), row n_filters + 1 is empty (any other value, which only the _device entry points
+// can meet: the host entry points refuse it).  So no value of query_filter[q] leads outside the table.
+FNV_SCAN_HD inline uint32_t filter_row(int32_t query_filter, uint32_t n_filters) {
+  if (query_filter == -1) return n_filters;
+  return (uint32_t)query_filter < n_filters ? (uint32_t)query_filter : n_filters + 1u;
+}
+
+// The grouped scan's tiles.  Queries are permuted so that every filter row's queries are contiguous, and a tile holds at most
+// `tile` queries of ONE row: a block then walks one bitmap for all its queries.  How many tiles that takes depends on the data,
+//   sum_g ceil(c_g / tile)  <=  ceil(nq / tile) + min(rows, nq)   and never more than nq,
+// so the host launches this bound and the descriptors past the real ones have count 0.
+struct GroupTile {
+  uint32_t first;  // first slot of the permutation
+  uint32_t count;  // queries of the tile, at most `tile`; 0: not a tile, its blocks return at once
+  uint32_t row;    // the filter row they all use
+};
+FNV_SCAN_HD inline uint64_t group_tile_bound(uint64_t nq, uint64_t rows, uint32_t tile) {
+  const uint64_t b = (nq + tile - 1) / tile + (rows < nq ? rows : nq);
+  return b < nq ? b : nq;
+}
+// Descriptor d from the rows' exclusive prefixes: slot_start[g] = queries of the rows before g, tile_start[g] = tiles of the
+// rows before g (both with a last entry [rows] = the total).  One independent binary search per descriptor.
+FNV_SCAN_HD inline GroupTile group_tile_at(uint32_t d, const uint32_t* slot_start, const uint32_t* tile_start, uint32_t rows,
+                                           uint32_t tile) {
+  if (d >= tile_start[rows]) return GroupTile{0u, 0u, 0u};
+  uint32_t lo = 0, hi = rows;  // the last g with tile_start[g] <= d (rows without queries share their successor's start)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (tile_start[mid] <= d) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t j = d - tile_start[lo], c = slot_start[lo + 1] - slot_start[lo];
+  const uint32_t left = c - j * tile;
+  return GroupTile{slot_start[lo] + j * tile, left < tile ? left : tile, lo};
+}
+// The same layout stated sequentially (the CPU test holds group_tile_at against it): out[0, bound) from the rows' query counts.
+// Returns the number of real tiles.
+inline uint32_t group_tiles_layout(const uint32_t* counts, uint32_t rows, uint32_t tile, GroupTile* out, uint32_t bound) {
+  uint32_t n = 0, slot = 0;
+  for (uint32_t g = 0; g < rows; g++) {
+    for (uint32_t j = 0; j < counts[g]; j += tile) {
+      if (n < bound) out[n] = GroupTile{slot + j, counts[g] - j < tile ? counts[g] - j : tile, g};
+      n++;
+    }
+    slot += counts[g];
+  }
+  for (uint32_t d = n; d < bound; d++) out[d] = GroupTile{0u, 0u, 0u};
+  return n;
+}
+
+// The grouped scan reads its candidates from the tile's bitmap row: set bits become node ids in an LDS queue of this many
+// entries, scored in batches as they fill (scan.hpp).  256 ids = 1 KB: with a tile budget of 19 KB a block still takes sixteen
+// 1280-byte LDS granules, eight blocks per CU as the plain scan; and a queue that holds less than a batch (at most 24 rows)
+// plus one 32-node word could not make progress.
+constexpr uint32_t SCAN_QUEUE_IDS = 256;
+
+// Parameter block of the grouped scan and its merge: the plain block (cand_ids / cand_count null, tiles = the launched bound)
+// and what grouping adds.
+struct GroupedScanParams {
+  ScanParams s;
+  const uint32_t* node_bits;   // [n_filters + 2][row_words]
+  const GroupTile* tiles;      // [s.tiles]
+  const uint32_t* perm;        // [nq] query indices, contiguous per filter row
+  const uint32_t* query_row;   // [nq] filter row of each query
+  const uint32_t* row_count;   // [n_filters + 2] nodes set in each row = the candidates of its queries
+  uint32_t row_words;          // words per bitmap row: ceil(capacity / 32)
+  uint32_t live_words;         // ceil(n_live / 32): the segments cut [0, live_words) in whole words
+};
+
 }  // namespace fnv_dev

@@ -90,8 +90,13 @@ struct SearchParams {
   unsigned long long* tie_log;  // [nslots][log_entries]
   uint32_t log_entries;
   // Filtered search (beam_search_filtered_kernel only): bit (i & 31) of word i >> 5 set = node i may be a result; null elsewhere.
-  // (The last field: the other kernels' parameter offsets stay as they were.)
+  // (Behind every other kernel's fields: their parameter offsets stay as they were.)
   const uint32_t* node_bits;
+  // Grouped filtered search (one filter per query): node_bits holds n_filters + 2 rows of filter_words words each (scan_select.hpp,
+  // filter_row) and query q reads row filter_row(query_filter[q], n_filters).  query_filter null = a single-filter launch: row 0.
+  const int32_t* query_filter;  // [nq]
+  uint32_t filter_words;
+  uint32_t n_filters;
 };
 
 // The fields of the visited-table geometry that the per-hop probe needs (kept in scalar registers).

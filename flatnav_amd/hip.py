@@ -29,6 +29,8 @@ C_ABI_SYMBOLS = [
     "fnv_index_adopt", "fnv_lane_info", "fnv_last_handover_stats", "fnv_row_layout",
     "fnv_search_batch_filtered", "fnv_search_batch_filtered_device", "fnv_index_build_half_rows", "fnv_index_half_rows",
     "fnv_search_batch_exhaustive", "fnv_search_batch_exhaustive_device",
+    "fnv_search_batch_filtered_grouped", "fnv_search_batch_filtered_grouped_device",
+    "fnv_search_batch_exhaustive_grouped", "fnv_search_batch_exhaustive_grouped_device",
 ]
 
 _lib = None
@@ -82,6 +84,15 @@ def lib() -> C.CDLL:
                                                   C.c_uint64] + [C.c_void_p] * 4
         L.fnv_search_batch_exhaustive_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
                                                          C.c_uint64] + [C.c_void_p] * 5
+    if hasattr(L, "fnv_search_batch_filtered_grouped"):  # (older builds under the A/B tools lack the grouped filters)
+        table = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]  # filters, n_filters, stride, n_bits, query_filter
+        L.fnv_search_batch_filtered_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int] + table + [
+            C.c_void_p] * 5
+        L.fnv_search_batch_filtered_grouped_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
+                                                               C.c_int] + table + [C.c_void_p] * 6
+        L.fnv_search_batch_exhaustive_grouped.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int] + table + [C.c_void_p] * 4
+        L.fnv_search_batch_exhaustive_grouped_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int] + table + [
+            C.c_void_p] * 5
     L.fnv_search_status.argtypes = [C.c_void_p]
     L.fnv_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.fnv_last_replayed_queries.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
@@ -165,6 +176,38 @@ def pack_allowed(allowed):
     mask = np.zeros(n_bits, dtype=np.bool_)
     mask[a] = True
     return np.ascontiguousarray(np.packbits(mask, bitorder="little")), n_bits
+
+
+def pack_filters(filters):
+    """The C ABI's filter TABLE of a grouped search -> (uint8 array [F, stride], n_bits).  `filters`: a sequence of anything
+    pack_allowed takes (they may differ in kind and length), or a 2-D bool mask [F, labels].  n_bits is the largest of the
+    filters' own; a shorter filter's row is zero beyond its own bits (those labels are not allowed).  Row f is filter f."""
+    if isinstance(filters, np.ndarray) and filters.ndim == 2:
+        if filters.dtype != np.bool_:
+            raise ValueError("a 2-D filter table must be a bool mask [filters, labels]")
+        packed = [pack_allowed(row) for row in filters]
+    else:
+        packed = [pack_allowed(f) for f in filters]
+    n_bits = max([n for _, n in packed], default=0)
+    table = np.zeros((len(packed), (n_bits + 7) // 8), dtype=np.uint8)
+    for f, (bits, _) in enumerate(packed):
+        table[f, :bits.size] = bits
+    return table, n_bits
+
+
+def _query_filter(query_filter, nq: int, n_filters: int) -> np.ndarray:
+    """query_filter of a grouped search as the C ABI takes it: int32 [nq], every value -1 (no filter) or a row of the table."""
+    a = np.asarray(query_filter)
+    if a.ndim != 1 or a.size != nq:
+        raise ValueError("query_filter must hold one entry per query")
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("query_filter must be an integer array, not %s" % a.dtype)
+    a = a.astype(np.int64, copy=False)
+    bad = np.flatnonzero((a < -1) | (a >= n_filters))
+    if bad.size:
+        raise ValueError("query_filter[%d] = %d is neither -1 nor a filter of the table (n_filters = %d)"
+                         % (int(bad[0]), int(a[bad[0]]), n_filters))
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def search_multi(indexes, queries, K: int, ef_search: int, num_initializations: int = 100, stats: bool = False):
@@ -390,6 +433,55 @@ class DeviceIndex:
             return d, l, {"count": cnt, "n_dist": nd}
         return d, l
 
+    def search_filtered_grouped(self, queries, K: int, ef_search: int, filters, query_filter, num_initializations: int = 100,
+                                stats: bool = False):
+        """search_filtered with one allowed set PER QUERY, in one launch (fnv_search_batch_filtered_grouped) ->
+        (dist float32[Q,K], labels int32[Q,K][, stats]).  `filters`: see pack_filters; query_filter[q] = the filter query q
+        uses, or -1 for none.  Row q is what search_filtered returns for that query with that filter (search for -1)."""
+        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("Queries have incorrect dimensions.")
+        nq = q.shape[0]
+        if K <= 0:
+            raise ValueError("K must be positive")
+        table, n_bits = pack_filters(filters)
+        qf = _query_filter(query_filter, nq, table.shape[0])
+        d = np.empty((nq, K), dtype=np.float32)
+        l = np.empty((nq, K), dtype=np.int32)
+        cnt = np.empty(nq, dtype=np.int32)
+        nd = np.zeros(nq, dtype=np.uint64)
+        nh = np.zeros(nq, dtype=np.uint64)
+        check(lib().fnv_search_batch_filtered_grouped(self._h, q.ctypes.data, nq, K, ef_search, num_initializations,
+                                                      table.ctypes.data if table.size else None, table.shape[0],
+                                                      table.shape[1], n_bits, qf.ctypes.data, d.ctypes.data, l.ctypes.data,
+                                                      cnt.ctypes.data, nd.ctypes.data, nh.ctypes.data))
+        if stats:
+            return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
+        return d, l
+
+    def search_exhaustive_grouped(self, queries, K: int, filters, query_filter, stats: bool = False):
+        """search_exhaustive with one allowed set PER QUERY, in one launch (fnv_search_batch_exhaustive_grouped) ->
+        (dist float32[Q,K], labels int32[Q,K][, stats]).  `filters`: see pack_filters; query_filter[q] = the filter query q
+        uses, or -1 for every live node.  Row q is what search_exhaustive returns for that query with that filter."""
+        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError("Queries have incorrect dimensions.")
+        nq = q.shape[0]
+        if K <= 0 or K > 1024:
+            raise ValueError("K of an exhaustive search must be between 1 and 1024")
+        table, n_bits = pack_filters(filters)
+        qf = _query_filter(query_filter, nq, table.shape[0])
+        d = np.empty((nq, K), dtype=np.float32)
+        l = np.empty((nq, K), dtype=np.int32)
+        cnt = np.empty(nq, dtype=np.int32)
+        nd = np.zeros(nq, dtype=np.uint64)
+        check(lib().fnv_search_batch_exhaustive_grouped(self._h, q.ctypes.data, nq, K, table.ctypes.data if table.size else None,
+                                                        table.shape[0], table.shape[1], n_bits, qf.ctypes.data, d.ctypes.data,
+                                                        l.ctypes.data, cnt.ctypes.data, nd.ctypes.data))
+        if stats:
+            return d, l, {"count": cnt, "n_dist": nd}
+        return d, l
+
     def search_into(self, queries: np.ndarray, K: int, ef_search: int, dist: np.ndarray, labels: np.ndarray,
                     num_initializations: int = 100) -> None:
         """Host-buffer batched search into arrays the CALLER owns (no allocation, no conversion): queries [Q, dim] of the index's
@@ -431,6 +523,28 @@ class DeviceIndex:
         check(lib().fnv_search_batch_exhaustive_device(self._h, q_ptr, nq, K, 1 if use_filter else 0, bits_ptr or None,
                                                        int(n_bits), dist_ptr, label_ptr, count_ptr or None, ndist_ptr or None,
                                                        stream or None))
+
+    def search_device_filtered_grouped(self, q_ptr: int, nq: int, K: int, ef_search: int, num_initializations: int,
+                                       filters_ptr: int, n_filters: int, stride_bytes: int, n_bits: int, query_filter_ptr: int,
+                                       dist_ptr: int, label_ptr: int, count_ptr: int = 0, ndist_ptr: int = 0, nhops_ptr: int = 0,
+                                       stream=None) -> None:
+        """Device-buffer grouped filtered search (fnv_search_batch_filtered_grouped_device): every pointer -- the filter table
+        (`n_filters` bitmaps of `n_bits` bits, `stride_bytes` apart) and the int32 `query_filter_ptr` [nq] included -- is device
+        memory; enqueued on `stream` without synchronising.  A query_filter value that is neither -1 nor a filter of the table
+        gives that query the empty filter."""
+        check(lib().fnv_search_batch_filtered_grouped_device(self._h, q_ptr, nq, K, ef_search, num_initializations,
+                                                             filters_ptr or None, int(n_filters), int(stride_bytes), int(n_bits),
+                                                             query_filter_ptr or None, dist_ptr, label_ptr, count_ptr or None,
+                                                             ndist_ptr or None, nhops_ptr or None, stream or None))
+
+    def search_device_exhaustive_grouped(self, q_ptr: int, nq: int, K: int, filters_ptr: int, n_filters: int, stride_bytes: int,
+                                         n_bits: int, query_filter_ptr: int, dist_ptr: int, label_ptr: int, count_ptr: int = 0,
+                                         ndist_ptr: int = 0, stream=None) -> None:
+        """Device-buffer grouped exhaustive search (fnv_search_batch_exhaustive_grouped_device); arguments as
+        search_device_filtered_grouped."""
+        check(lib().fnv_search_batch_exhaustive_grouped_device(self._h, q_ptr, nq, K, filters_ptr or None, int(n_filters),
+                                                               int(stride_bytes), int(n_bits), query_filter_ptr or None, dist_ptr,
+                                                               label_ptr, count_ptr or None, ndist_ptr or None, stream or None))
 
     def tune(self, queries, K: int, ef_search: int, num_initializations: int = 100, nq: int = 0) -> None:
         """Settle the adaptive kernel choice for (K, ef_search, this batch size) in one call (fnv_tune): afterwards no
@@ -490,6 +604,8 @@ class DeviceIndex:
         out = {k: int(g[i]) for i, k in enumerate(keys)}
         out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds", "exhaustive_scan"][int(g[6])]
         out["tail_exact"] = int(g[7])
+        if int(g[6]) == 3 and int(g[4]):  # the grouped scan reports its tiling in the slots the graph search's layout uses
+            out["tile_queries"], out["queue_ids"], out["segments"] = int(g[3]), int(g[4]), int(g[5])
         return out
 
 

@@ -920,6 +920,45 @@ class Index {
     return results;
   }
 
+  // Grouped filters (flatnav_hip.h, fnv_search_batch_*_grouped): searchBatchFiltered / searchBatchExhaustive with one allowed set
+  // PER QUERY in one launch.  filters: n_filters bitmaps of n_bits bits, stride_bytes apart, each read as allowed_bits above;
+  // query_filter[q] = the filter query q uses, -1 = none (anything else: std::invalid_argument).  Row q is what the
+  // single-filter call returns for that query with that filter.  Always on this index's primary GPU.
+  void searchBatchFilteredGrouped(const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
+                                  const uint8_t* filters, uint64_t n_filters, uint64_t stride_bytes, uint64_t n_bits,
+                                  const int32_t* query_filter, float* out_dist, label_t* out_labels, int32_t* out_count = nullptr) {
+    if (num_initializations <= 0) throw std::invalid_argument("num_initializations must be greater than 0.");
+    std::lock_guard<std::mutex> g(_device_guard);
+    ensureDevice();
+    std::vector<uint64_t> ndist;
+    if (_collect_stats) ndist.resize(nq);
+    detail::throwOnDeviceError(fnv_search_batch_filtered_grouped(_device_index, queries, nq, K, ef_search, num_initializations, filters,
+                                                                 n_filters, stride_bytes, n_bits, query_filter, out_dist,
+                                                                 reinterpret_cast<int32_t*>(out_labels), out_count,
+                                                                 _collect_stats ? ndist.data() : nullptr, nullptr));
+    if (_collect_stats) {  // same accounting as searchBatchFiltered
+      uint64_t total = static_cast<uint64_t>(num_initializations) * nq;
+      for (uint64_t v : ndist) total += v;
+      _distance_computations.fetch_add(total);
+    }
+  }
+  void searchBatchExhaustiveGrouped(const void* queries, uint64_t nq, int K, const uint8_t* filters, uint64_t n_filters,
+                                    uint64_t stride_bytes, uint64_t n_bits, const int32_t* query_filter, float* out_dist,
+                                    label_t* out_labels, int32_t* out_count = nullptr) {
+    std::lock_guard<std::mutex> g(_device_guard);
+    ensureDevice();
+    std::vector<uint64_t> ndist;
+    if (_collect_stats) ndist.resize(nq);
+    detail::throwOnDeviceError(fnv_search_batch_exhaustive_grouped(_device_index, queries, nq, K, filters, n_filters, stride_bytes, n_bits,
+                                                                   query_filter, out_dist, reinterpret_cast<int32_t*>(out_labels),
+                                                                   out_count, _collect_stats ? ndist.data() : nullptr));
+    if (_collect_stats) {  // same accounting as searchBatchExhaustive
+      uint64_t total = 0;
+      for (uint64_t v : ndist) total += v;
+      _distance_computations.fetch_add(total);
+    }
+  }
+
   // ---- reordering (reference Index.h:412-440, 872-926) ---------------------------------------
   void doGraphReordering(const std::vector<std::string>& reordering_methods) {
     for (const auto& method : reordering_methods) {

@@ -365,6 +365,56 @@ int fnv_search_batch_exhaustive_device(fnv_index_t index, const void* d_queries,
                                        const void* d_allowed_bits, uint64_t n_bits, float* d_out_dist, int32_t* d_out_labels,
                                        int32_t* d_out_count, uint64_t* d_out_ndist, void* hip_stream);
 
+/* Grouped filters: the two filtered searches above with ONE ALLOWED SET PER QUERY -- a table of n_filters bitmaps and, per query,
+ * which of them it uses -- in one launch: the multi-tenant / per-user batch that would otherwise be one call per predicate.
+ *   Filter table: filter f is the bitmap at filters + f * filter_stride_bytes, read exactly as allowed_bits of
+ *     fnv_search_batch_filtered (over label values, little-endian bit order, negative labels and labels >= n_bits not allowed);
+ *     one n_bits for all filters, n_bits <= 2^31; filter_stride_bytes >= ceil(n_bits / 8); n_filters <= 2^31 - 1; filters may
+ *     be NULL only when n_filters == 0 or n_bits == 0.
+ *   query_filter[q] (int32, one per query): 0 .. n_filters - 1 = that filter; -1 = no filter for this query (every live node is a
+ *     candidate whatever its label, negative labels included).  Any other value: the host entry points return FNV_ERR_INVALID --
+ *     they read the array before launching, the message names the first offending query, nothing is launched; the _device
+ *     entry points cannot look without synchronising and give that query the EMPTY filter (a row of (+inf, -1), count 0).  No
+ *     kernel reads outside the bitmaps for any value.
+ *   Results: row q holds exactly the bytes the single-filter call writes for that query with filter query_filter[q] -- graph
+ *     search: labels, distance bits, out_count, out_ndist, out_nhops; exhaustive search: labels, distance bits, out_count,
+ *     out_ndist, in the (distance, node id) order with NaN last.  A -1 row equals the row of fnv_search_batch / of the
+ *     unfiltered fnv_search_batch_exhaustive.  Padding, "fewer than K is not an error", FNV_ERR_CAPACITY (graph form only),
+ *     1 <= K <= 1024 (exhaustive form) and nq == 0 being a no-op are as in the single-filter calls.
+ *   Launches: the graph form runs the filtered two-heap kernel, every query reading its own node bitmap; it takes no samples for
+ *     the adaptive kernel choice and leaves its measurements alone.  The exhaustive form groups the queries by filter into
+ *     tiles of one filter each (at most ceil(nq / tile) + min(n_filters + 2, nq) tiles, never more than nq: the grid is that
+ *     bound) and scans, per tile, the set bits of its filter's node bitmap -- no per-filter id lists; row segments cut the node
+ *     range, so filters that select contiguous node ranges load them unevenly.  fnv_last_launch_geometry reports
+ *     {grid_blocks = the launched bound x segments, 64, lds_bytes, queries per tile, entries of the LDS id queue, segments,
+ *     kernel = 3, 0} for it.
+ *   Memory: temporary HBM in the workspace of whichever handle or lane runs the call: (n_filters + 2) x ceil(capacity / 32) x 4
+ *     bytes of node bitmaps (the filters, "every live node" for -1, "none"), O(nq + n_filters) grouping arrays, and for the
+ *     exhaustive form the partial lists as above; all of it counts towards that lane's share of the lane budget (fnv_lane_info).  Nothing else limits n_filters; an allocation that fails is FNV_ERR_RUNTIME
+ *     with a message that says how many bytes the filter rows needed.
+ * The host entry points (filters and query_filter in host memory) are as thread-safe as fnv_search_batch and use the lanes the
+ *   same way; they always take the staged-copy path (the filter table and query_filter go through the handle's staging, never
+ *   zero-copy).  The _device entry points (every buffer in the index's device memory) enqueue on `hip_stream` without
+ *   synchronising; one launch in flight per handle.
+ * Not covered: fnv_search_batch_multi / replicas, routing between the graph and the scan form, a K or ef_search per query. */
+int fnv_search_batch_filtered_grouped(fnv_index_t index, const void* queries, uint64_t nq, int K, int ef_search,
+                                      int num_initializations, const void* filters, uint64_t n_filters,
+                                      uint64_t filter_stride_bytes, uint64_t n_bits, const int32_t* query_filter, float* out_dist,
+                                      int32_t* out_labels, int32_t* out_count, uint64_t* out_ndist, uint64_t* out_nhops);
+int fnv_search_batch_filtered_grouped_device(fnv_index_t index, const void* d_queries, uint64_t nq, int K, int ef_search,
+                                             int num_initializations, const void* d_filters, uint64_t n_filters,
+                                             uint64_t filter_stride_bytes, uint64_t n_bits, const int32_t* d_query_filter,
+                                             float* d_out_dist, int32_t* d_out_labels, int32_t* d_out_count,
+                                             uint64_t* d_out_ndist, uint64_t* d_out_nhops, void* hip_stream);
+int fnv_search_batch_exhaustive_grouped(fnv_index_t index, const void* queries, uint64_t nq, int K, const void* filters,
+                                        uint64_t n_filters, uint64_t filter_stride_bytes, uint64_t n_bits,
+                                        const int32_t* query_filter, float* out_dist, int32_t* out_labels, int32_t* out_count,
+                                        uint64_t* out_ndist);
+int fnv_search_batch_exhaustive_grouped_device(fnv_index_t index, const void* d_queries, uint64_t nq, int K, const void* d_filters,
+                                               uint64_t n_filters, uint64_t filter_stride_bytes, uint64_t n_bits,
+                                               const int32_t* d_query_filter, float* d_out_dist, int32_t* d_out_labels,
+                                               int32_t* d_out_count, uint64_t* d_out_ndist, void* hip_stream);
+
 /* ---- several GPUs of one node: index replicated, query rows sharded, no per-query collective -------
  * The reference parallelises a batch over host threads that share one index in memory (executeInParallel over rows,
  * python-bindings/src/flatnav/bindings.cpp:198-211, include/flatnav/util/Multithreading.h:19-48); here every GPU
