@@ -89,7 +89,7 @@ struct Blob {
   }
   float dist(const void* q, uint32_t i) const {
     if (dtype == 9) {
-      float a[4096], b[4096];  // (unaligned-safe copies; dim <= 4096 is checked by the caller)
+      static thread_local float a[9216], b[9216];  // (unaligned-safe copies, off the stack; dim <= 9216 is checked by the caller)
       std::memcpy(a, q, dim * 4);
       std::memcpy(b, data(i), dim * 4);
       return dist_f32(a, b, dim, ip);
@@ -106,7 +106,7 @@ extern "C" int fsr_search(const uint8_t* blob, uint64_t node_size, uint64_t data
                           const uint8_t* bits, uint64_t n_bits, float* out_d, int32_t* out_l, int32_t* out_cnt,
                           uint64_t* out_ndist, uint64_t* out_nhops) {
   if (dtype != 9 && dtype != 0 && dtype != 4) return 1;
-  if (dim == 0 || dim > 4096 || n_nodes == 0 || K <= 0 || ef <= 0 || n_init <= 0) return 1;
+  if (dim == 0 || dim > 9216 || n_nodes == 0 || K <= 0 || ef <= 0 || n_init <= 0) return 1;
   const Blob b{blob, node_size, data_size, n_nodes, M, dim, dtype, metric != 0};
   const size_t esize = dtype == 9 ? 4 : 1;
   const size_t B = (size_t)std::max(ef, K);

@@ -143,6 +143,13 @@ int lph_variant_allowed(int v, int multi_round, int try_tail, int shadows_on, in
   return variant_allowed(v, multi_round != 0, try_tail != 0, shadows_on != 0, pinned_only != 0);
 }
 
+// Row configuration `cfg` of kCfgs: its lanes per row (G) and chunks per lane and span (CU).  Returns the number of
+// configurations, so that tests/row_classes.py never repeats the table.
+int lph_row_cfg(int cfg, int* G, int* CU) {
+  if (cfg >= 0 && cfg < kNumCfgs) *G = kCfgs[cfg].G, *CU = kCfgs[cfg].CU;
+  return kNumCfgs;
+}
+
 // Query slots of `lds` bytes that the LDS of one CU holds (whole granules).
 int lph_slots_per_cu(uint32_t lds) { return (int)(kLdsPerCu / lds_allocated(lds)); }
 

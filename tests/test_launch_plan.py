@@ -24,7 +24,7 @@ from test_visited_model import ModelVisited
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "launch_plan_harness.cpp")
-F32, U8, F16 = 9, 0, 2  # FNV_DTYPE_* (include/flatnav_hip.h)
+F32, U8, F16 = 9, 0, 8  # FNV_DTYPE_* (include/flatnav_hip.h)
 FNV_ERR_INVALID = 1
 WAVE, OVF_LIST, STASH = 64, 30, 64
 MODE_HEAPS, MODE_MERGED_REGS, MODE_MERGED_LDS = 0, 1, 2
