@@ -1167,6 +1167,31 @@ static int launch_filter_rows(fnv_index_s* ix, const SearchFilter& f, uint64_t l
   HIP_TRY(hipGetLastError());
   return FNV_OK;
 }
+// One filter for the launch: the label bitmap -> d_nodebits, by the labels as they are now (after reorder(), device builds ...)
+static int launch_node_filter(fnv_index_s* ix, const SearchFilter& f, uint64_t live, hipStream_t stream) {
+  const uint64_t words = (ix->capacity + 31) / 32;
+  hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
+                     live, words, f.bits, f.n_bits, ix->d_nodebits.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  return FNV_OK;
+}
+// What every launch checks after its own arguments; false: the call is over with *rc (an empty batch is FNV_OK).
+static bool batch_to_launch(const void* d_queries, uint64_t nq, const SearchOutputs& out, int* rc) {
+  *rc = FNV_OK;
+  if (nq == 0) return false;
+  if (!d_queries || !out.dist || !out.labels) *rc = fail(FNV_ERR_INVALID, "null buffer");
+  else if (nq > 0x7FFFFFFFull) *rc = fail(FNV_ERR_INVALID, "too many queries in one batch");
+  return *rc == FNV_OK;
+}
+// What the launch was, for the fnv_last_* calls: grid, block, LDS bytes, then five values of the kernel's own (geom[6]: its mode).
+static void record_launch(fnv_index_s* ix, hipStream_t stream, uint64_t grid, uint64_t block, uint64_t lds, uint64_t g3, uint64_t g4,
+                          uint64_t g5, uint64_t mode, uint64_t g7) {
+  ix->last_stream = stream;
+  ix->launched = true;
+  if (!ix->is_lane) ix->last_served = nullptr;  // the handle's own launch is its most recent one
+  const uint64_t geom[8] = {grid, block, lds, g3, g4, g5, mode, g7};
+  for (int i = 0; i < 8; i++) ix->geom[i] = geom[i];
+}
 // The grouping arrays of a grouped scan (scan.hpp's group_* kernels), as uint32 offsets into one buffer.
 struct GroupArrays {
   size_t query_row, perm, counts, cursor, row_count, slot_start, tile_start, tiles, bytes;
@@ -1219,10 +1244,9 @@ static ScanShape scan_shape(const fnv_index_s* ix, const RowGeometry& g, uint64_
 
 static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, const SearchOutputs& out, void* hip_stream,
                             const SearchOptions& opt) {
+  int rc;
   if (K < 1 || K > SCAN_MAX_K) return fail(FNV_ERR_INVALID, "K of an exhaustive search must be between 1 and 1024");
-  if (nq == 0) return FNV_OK;
-  if (!d_queries || !out.dist || !out.labels) return fail(FNV_ERR_INVALID, "null buffer");
-  if (nq > 0x7FFFFFFFull) return fail(FNV_ERR_INVALID, "too many queries in one batch");
+  if (!batch_to_launch(d_queries, nq, out, &rc)) return rc;
   std::lock_guard<std::mutex> lock(ix->mu);
   ON_DEVICE(ix->device);
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -1236,7 +1260,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const scan_grouped_fn kern_g = kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full];
   const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
-  int rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
+  rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
   if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
   if (!rc && grouped) rc = ix->ws.group.grow(ga.bytes);
   if (!rc && filter && !grouped) rc = ix->d_nodebits.grow((size_t)(ix->capacity + 31) / 32 * 4);
@@ -1293,11 +1317,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
     gp.row_words = (uint32_t)((ix->capacity + 31) / 32);
     gp.live_words = (uint32_t)((live + 31) / 32);
   } else if (filter) {  // the label bitmap -> this handle's node bitmap -> the list of allowed node ids
-    const uint64_t words = (ix->capacity + 31) / 32;
     uint32_t* const ids = ix->d_scanids.as<uint32_t>();
-    hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
-                       live, words, filter->bits, filter->n_bits, ix->d_nodebits.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
+    rc = launch_node_filter(ix, *filter, live, stream);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ids, 0, 16, stream));
     hipLaunchKernelGGL(exhaustive_compact_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, stream,
                        (const uint32_t*)ix->d_nodebits.as<uint32_t>(), live, ids + 4, ids);
@@ -1322,19 +1344,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ix->ev1, stream));
-  ix->last_stream = stream;
-  ix->launched = true;
-  if (!ix->is_lane) ix->last_served = nullptr;
-  ix->geom[0] = (uint64_t)shape.tiles * shape.segments;
-  ix->geom[1] = WAVE;
-  ix->geom[2] = shape.lds;
-  for (int i = 3; i < 8; i++) ix->geom[i] = 0;
-  ix->geom[6] = 3;  // (fnv_last_launch_geometry: the exhaustive scan)
-  if (grouped) {    // ... its grouped form: queries per tile, entries of the id queue, row segments
-    ix->geom[3] = shape.tile;
-    ix->geom[4] = SCAN_QUEUE_IDS;
-    ix->geom[5] = shape.segments;
-  }
+  // (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id queue, row segments)
+  record_launch(ix, stream, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped ? shape.tile : 0, grouped ? SCAN_QUEUE_IDS : 0,
+                grouped ? shape.segments : 0, 3, 0);
   return FNV_OK;
 }
 
@@ -1345,9 +1357,8 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   // Index.h:847-849
   if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
   if (K <= 0 || ef_search <= 0) return fail(FNV_ERR_INVALID, "K and ef_search must be positive");
-  if (nq == 0) return FNV_OK;
-  if (!d_queries || !out.dist || !out.labels) return fail(FNV_ERR_INVALID, "null buffer");
-  if (nq > 0x7FFFFFFFull) return fail(FNV_ERR_INVALID, "too many queries in one batch");
+  int rc;
+  if (!batch_to_launch(d_queries, nq, out, &rc)) return rc;
   std::lock_guard<std::mutex> lock(ix->mu);
   ON_DEVICE(ix->device);
   hipStream_t stream = (hipStream_t)hip_stream;
@@ -1366,7 +1377,7 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     ix->plan.valid = false;
   }
   ix->measured_half = (int)half_rows;
-  int rc = ensure_plan(ix, B, K, half_rows);
+  rc = ensure_plan(ix, B, K, half_rows);
   if (rc) return rc;
   PlannedLaunch& plan = ix->plan;
   if (filter && !plan.fkern.fn) {
@@ -1426,11 +1437,9 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
     p.query_filter = filter->query_filter;
     p.filter_words = (uint32_t)((ix->capacity + 31) / 32);
     p.n_filters = (uint32_t)filter->n_filters;
-  } else if (filter) {  // the label bitmap -> this handle's node bitmap (labels as they are now: after reorder(), device builds ...)
-    const uint64_t words = (ix->capacity + 31) / 32;
-    hipLaunchKernelGGL(node_filter_kernel, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, stream, (const int32_t*)ix->d_labels,
-                       live, words, filter->bits, filter->n_bits, ix->d_nodebits.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
+  } else if (filter) {
+    rc = launch_node_filter(ix, *filter, live, stream);
+    if (rc) return rc;
     p.node_bits = ix->d_nodebits.as<uint32_t>();
   }
   HIP_TRY(hipEventRecord(ix->ev0, stream));
@@ -1482,17 +1491,8 @@ static int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq
   if (c.exploratory) ix->explored_launches++;
   ix->last_shadow = shadow;
   ix->last_half = kern.half_rows;
-  ix->last_stream = stream;
-  ix->launched = true;
-  if (!ix->is_lane) ix->last_served = nullptr;  // the handle's own launch is its most recent one
-  ix->geom[0] = nslots;
-  ix->geom[1] = WAVE;
-  ix->geom[2] = lds_bytes;
-  ix->geom[3] = (uint64_t)bpc;
-  ix->geom[4] = p.vis_slots;
-  ix->geom[5] = p.cand_slots;
-  ix->geom[6] = (uint64_t)(sorted ? plan.mode : MODE_HEAPS);
-  ix->geom[7] = p.tail_exact;
+  record_launch(ix, stream, nslots, WAVE, lds_bytes, (uint64_t)bpc, p.vis_slots, p.cand_slots, (uint64_t)(sorted ? plan.mode : MODE_HEAPS),
+                p.tail_exact);
   return FNV_OK;
 }
 

@@ -123,27 +123,42 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     return this->shared_from_this();
   }
 
-  // search(queries, K, ef_search, num_initializations=100) -> (float32[Q,K], int32[Q,K])
-  py::tuple search(const py::array& queries_any, int K, int ef_search, int num_initializations) {
+  // The frame of every batched search: the queries as elements, the shape and K checks (`exhaustive`: K has an upper bound),
+  // prepare(nq) -- the form's own arguments, still under the GIL --, the output arrays, run(qptr, nq, dptr, lptr) with the GIL
+  // released (the GPU works; other Python threads may run), and the (float32[Q,K], int32[Q,K]) tuple.
+  template <typename Prepare, typename Run>
+  py::tuple searchBatched(const py::array& queries_any, int K, bool exhaustive, Prepare prepare, Run run) {
     py::array queries = elements(queries_any);
     if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
+    if (exhaustive && (K <= 0 || K > 1024)) throw std::invalid_argument("K of an exhaustive search must be between 1 and 1024.");
     if (K <= 0) throw std::invalid_argument("K must be positive.");
     const py::ssize_t nq = queries.shape(0);
+    prepare(nq);
     py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
     py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
-    std::vector<int32_t> counts(static_cast<size_t>(nq));
     {
       const void* qptr = queries.data();
       float* dptr = dist.mutable_data();
       int* lptr = labels.mutable_data();
-      py::gil_scoped_release release;  // the GPU works; other Python threads may run
-      _index->searchBatch(qptr, static_cast<uint64_t>(nq), K, ef_search, num_initializations, dptr, lptr, counts.data());
+      py::gil_scoped_release release;
+      run(qptr, static_cast<uint64_t>(nq), dptr, lptr);
     }
-    for (py::ssize_t q = 0; q < nq; ++q)  // bindings.cpp:184-189
-      if (counts[static_cast<size_t>(q)] != K)
-        throw std::runtime_error("Search did not return the expected number of results. Expected " + std::to_string(K) +
-                                 " but got " + std::to_string(counts[static_cast<size_t>(q)]) + ".");
     return py::make_tuple(dist, labels);
+  }
+
+  // search(queries, K, ef_search, num_initializations=100) -> (float32[Q,K], int32[Q,K])
+  py::tuple search(const py::array& queries_any, int K, int ef_search, int num_initializations) {
+    std::vector<int32_t> counts;
+    py::tuple out = searchBatched(
+        queries_any, K, false, [&](py::ssize_t nq) { counts.resize(static_cast<size_t>(nq)); },
+        [&](const void* qptr, uint64_t nq, float* dptr, int* lptr) {
+          _index->searchBatch(qptr, nq, K, ef_search, num_initializations, dptr, lptr, counts.data());
+        });
+    for (int32_t count : counts)  // bindings.cpp:184-189
+      if (count != K)
+        throw std::runtime_error("Search did not return the expected number of results. Expected " + std::to_string(K) +
+                                 " but got " + std::to_string(count) + ".");
+    return out;
   }
 
   // `allowed` (1-D bool mask indexed by label, or 1-D integer array of labels) -> the C ABI's bitmap over label values
@@ -177,53 +192,34 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
   // nodes whose label is allowed; `allowed` = 1-D bool mask indexed by label, or 1-D integer array of labels (order and
   // duplicates ignored, a negative label raises ValueError).  Short rows are padded with (+inf, -1), never raised on.
   py::tuple searchFiltered(const py::array& queries_any, int K, int ef_search, const py::array& allowed_any, int num_initializations) {
-    py::array queries = elements(queries_any);
-    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
-    if (K <= 0) throw std::invalid_argument("K must be positive.");
     std::vector<uint8_t> bits;
     uint64_t n_bits = 0;
-    packAllowed(allowed_any, bits, n_bits);
-    const py::ssize_t nq = queries.shape(0);
-    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
-    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
-    {
-      const void* qptr = queries.data();
-      float* dptr = dist.mutable_data();
-      int* lptr = labels.mutable_data();
-      py::gil_scoped_release release;
-      _index->searchBatchFiltered(qptr, static_cast<uint64_t>(nq), K, ef_search, num_initializations, bits.empty() ? nullptr : bits.data(),
-                                  n_bits, dptr, lptr, nullptr);
-    }
-    return py::make_tuple(dist, labels);
+    return searchBatched(
+        queries_any, K, false, [&](py::ssize_t) { packAllowed(allowed_any, bits, n_bits); },
+        [&](const void* qptr, uint64_t nq, float* dptr, int* lptr) {
+          _index->searchBatchFiltered(qptr, nq, K, ef_search, num_initializations, bits.empty() ? nullptr : bits.data(), n_bits, dptr, lptr,
+                                      nullptr);
+        });
   }
 
   // search_exhaustive(queries, K, allowed=None) -> (float32[Q,K], int32[Q,K]): the exact K nearest among all nodes, or among
   // those whose label is allowed (`allowed` as for search_filtered), by one device scan; sorted by (distance, node id).
   // Short rows are padded with (+inf, -1), never raised on.
   py::tuple searchExhaustive(const py::array& queries_any, int K, const py::object& allowed_obj) {
-    py::array queries = elements(queries_any);
-    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
-    if (K <= 0 || K > 1024) throw std::invalid_argument("K of an exhaustive search must be between 1 and 1024.");
     std::vector<uint8_t> bits;
     uint64_t n_bits = 0;
     const bool use_filter = !allowed_obj.is_none();
-    if (use_filter) {
-      py::array allowed_any = py::array::ensure(allowed_obj);
-      if (!allowed_any) throw std::invalid_argument("allowed must be a bool mask or an integer array of labels.");
-      packAllowed(allowed_any, bits, n_bits);
-    }
-    const py::ssize_t nq = queries.shape(0);
-    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
-    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
-    {
-      const void* qptr = queries.data();
-      float* dptr = dist.mutable_data();
-      int* lptr = labels.mutable_data();
-      py::gil_scoped_release release;
-      _index->searchBatchExhaustive(qptr, static_cast<uint64_t>(nq), K, bits.empty() ? nullptr : bits.data(), n_bits, use_filter, dptr,
-                                    lptr, nullptr);
-    }
-    return py::make_tuple(dist, labels);
+    return searchBatched(
+        queries_any, K, true,
+        [&](py::ssize_t) {
+          if (!use_filter) return;
+          py::array allowed_any = py::array::ensure(allowed_obj);
+          if (!allowed_any) throw std::invalid_argument("allowed must be a bool mask or an integer array of labels.");
+          packAllowed(allowed_any, bits, n_bits);
+        },
+        [&](const void* qptr, uint64_t nq, float* dptr, int* lptr) {
+          _index->searchBatchExhaustive(qptr, nq, K, bits.empty() ? nullptr : bits.data(), n_bits, use_filter, dptr, lptr, nullptr);
+        });
   }
 
   // `filters` (a sequence of what packAllowed takes, or a 2-D bool mask [F, labels]) -> the C ABI's filter table: F rows of
@@ -264,52 +260,39 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
     return out;
   }
 
+  struct FilterTable {  // the grouped forms' own arguments as the C ABI takes them
+    std::vector<uint8_t> table;
+    uint64_t n_filters = 0, stride = 0, n_bits = 0;
+    std::vector<int32_t> query_filter;
+    void pack(const py::object& filters_obj, const py::array& query_filter_any, py::ssize_t nq) {
+      packFilters(filters_obj, table, n_filters, stride, n_bits);
+      query_filter = queryFilter(query_filter_any, nq, n_filters);
+    }
+    const uint8_t* data() const { return table.empty() ? nullptr : table.data(); }
+  };
+
   // search_filtered_grouped(queries, K, ef_search, filters, query_filter, num_initializations=100): search_filtered with one
   // allowed set per query (query_filter[q] = its filter's row in `filters`, -1 = none), in one launch.
   py::tuple searchFilteredGrouped(const py::array& queries_any, int K, int ef_search, const py::object& filters_obj,
                                   const py::array& query_filter_any, int num_initializations) {
-    py::array queries = elements(queries_any);
-    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
-    if (K <= 0) throw std::invalid_argument("K must be positive.");
-    std::vector<uint8_t> table;
-    uint64_t n_filters = 0, stride = 0, n_bits = 0;
-    packFilters(filters_obj, table, n_filters, stride, n_bits);
-    const py::ssize_t nq = queries.shape(0);
-    const std::vector<int32_t> qf = queryFilter(query_filter_any, nq, n_filters);
-    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
-    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
-    {
-      const void* qptr = queries.data();
-      float* dptr = dist.mutable_data();
-      int* lptr = labels.mutable_data();
-      py::gil_scoped_release release;
-      _index->searchBatchFilteredGrouped(qptr, static_cast<uint64_t>(nq), K, ef_search, num_initializations,
-                                         table.empty() ? nullptr : table.data(), n_filters, stride, n_bits, qf.data(), dptr, lptr, nullptr);
-    }
-    return py::make_tuple(dist, labels);
+    FilterTable f;
+    return searchBatched(
+        queries_any, K, false, [&](py::ssize_t nq) { f.pack(filters_obj, query_filter_any, nq); },
+        [&](const void* qptr, uint64_t nq, float* dptr, int* lptr) {
+          _index->searchBatchFilteredGrouped(qptr, nq, K, ef_search, num_initializations, f.data(), f.n_filters, f.stride, f.n_bits,
+                                             f.query_filter.data(), dptr, lptr, nullptr);
+        });
   }
 
   // search_exhaustive_grouped(queries, K, filters, query_filter): search_exhaustive with one allowed set per query.
   py::tuple searchExhaustiveGrouped(const py::array& queries_any, int K, const py::object& filters_obj, const py::array& query_filter_any) {
-    py::array queries = elements(queries_any);
-    if (queries.ndim() != 2 || queries.shape(1) != _dim) throw std::invalid_argument("Queries have incorrect dimensions.");
-    if (K <= 0 || K > 1024) throw std::invalid_argument("K of an exhaustive search must be between 1 and 1024.");
-    std::vector<uint8_t> table;
-    uint64_t n_filters = 0, stride = 0, n_bits = 0;
-    packFilters(filters_obj, table, n_filters, stride, n_bits);
-    const py::ssize_t nq = queries.shape(0);
-    const std::vector<int32_t> qf = queryFilter(query_filter_any, nq, n_filters);
-    py::array_t<float> dist({nq, static_cast<py::ssize_t>(K)});
-    py::array_t<int> labels({nq, static_cast<py::ssize_t>(K)});
-    {
-      const void* qptr = queries.data();
-      float* dptr = dist.mutable_data();
-      int* lptr = labels.mutable_data();
-      py::gil_scoped_release release;
-      _index->searchBatchExhaustiveGrouped(qptr, static_cast<uint64_t>(nq), K, table.empty() ? nullptr : table.data(), n_filters, stride,
-                                           n_bits, qf.data(), dptr, lptr, nullptr);
-    }
-    return py::make_tuple(dist, labels);
+    FilterTable f;
+    return searchBatched(
+        queries_any, K, true, [&](py::ssize_t nq) { f.pack(filters_obj, query_filter_any, nq); },
+        [&](const void* qptr, uint64_t nq, float* dptr, int* lptr) {
+          _index->searchBatchExhaustiveGrouped(qptr, nq, K, f.data(), f.n_filters, f.stride, f.n_bits, f.query_filter.data(), dptr, lptr,
+                                               nullptr);
+        });
   }
 
   // search_single(query, K, ef_search, num_initializations=100) -> (float32[K], int32[K])

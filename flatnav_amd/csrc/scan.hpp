@@ -3,15 +3,18 @@
 //
 //   1. filtered calls: node_filter_kernel (relayout.hpp) turns the label bitmap into a node bitmap, exhaustive_compact_kernel
 //      turns that into the list of allowed node ids (any order: the selection's order is total, scan_select.hpp).
-//   2. exhaustive_scan_kernel, one wavefront per (query tile, row segment): the tile's queries are staged in LDS, a lane group
-//      loads the chunks of PU rows into registers ONCE and scores them against every query of the tile -- the row traffic of a
-//      launch is  ceil(nq / tile) * candidates * row_bytes  instead of nq * candidates * row_bytes.  Per (query, row) the
-//      arithmetic is batch_dists' (distance.hpp): lane g of the row's group accumulates chunks g, g + G, ... in that order with
-//      Dist<T, METRIC>, group_sum adds the lanes -- so a distance has the bits the graph search reports for the same pair.
-//      Every query keeps a sorted list of its K best keys in LDS; a row that does not beat the K-th is dropped by one compare,
-//      one that does (about K ln(n / K) per query) is inserted by the whole wave.
+//   2. exhaustive_scan_kernel, one wavefront per (query tile, row segment): the tile's queries are staged in LDS
+//      (scan_stage_tile), a lane group loads the chunks of PU rows into registers ONCE and scores them against every query of
+//      the tile -- the row traffic of a launch is  ceil(nq / tile) * candidates * row_bytes  instead of
+//      nq * candidates * row_bytes.  Per (query, row) the arithmetic is batch_dists' (distance.hpp): lane g of the row's group
+//      accumulates chunks g, g + G, ... in that order with Dist<T, METRIC>, group_sum adds the lanes -- so a distance has the
+//      bits the graph search reports for the same pair.  Every query keeps a sorted list of its K best keys in LDS; a row that
+//      does not beat the K-th is dropped by one compare, one that does (about K ln(n / K) per query) is inserted by the whole
+//      wave.  The lists go out per segment (scan_flush_tile).
 //   3. exhaustive_merge_kernel, one wavefront per query: the segments' lists merged by rank (scan_select.hpp), keys back to
 //      (distance, label), padding, counters.
+// With one filter per query (fnv_search_batch_exhaustive_grouped) step 2 is exhaustive_scan_grouped_kernel: the same staging
+// and flushing around a walk of the tile's filter row; its batches are scored by scan_score_batch, a copy of step 2's loop.
 #pragma once
 #include "distance.hpp"
 #include "heaps.hpp"
@@ -34,6 +37,31 @@ __device__ __forceinline__ void scan_insert(uint64_t* list, int K, uint64_t key,
   wave_sync();
 }
 
+// The tile's queries into LDS, zero padded to q_chunks, and every list empty.  query_of(qq): the global query of tile slot qq.
+template <typename T, typename F>
+__device__ __forceinline__ void scan_stage_tile(const ScanParams& p, uint4* qlds, uint64_t* lists, uint32_t nqb, int lane, F query_of) {
+  const int padded = (int)(p.q_chunks * 16u / sizeof(T));
+  const int dim = (int)p.dim;
+  for (uint32_t qq = 0; qq < nqb; qq++) {
+    const T* qsrc = reinterpret_cast<const T*>(p.queries) + (uint64_t)query_of(qq) * p.dim;
+    T* qdst = reinterpret_cast<T*>(qlds + (size_t)qq * p.q_chunks);
+    for (int i = lane; i < padded; i += WAVE) qdst[i] = i < dim ? qsrc[i] : T(0);
+  }
+  for (uint32_t i = lane; i < nqb * p.K; i += WAVE) lists[i] = SCAN_PAD;
+  wave_sync();
+}
+// ... and the tile's lists out to the partial lists of segment `seg`
+template <typename F>
+__device__ __forceinline__ void scan_flush_tile(const ScanParams& p, const uint64_t* lists, uint32_t nqb, uint32_t seg, int lane, F query_of) {
+  wave_sync();
+  for (uint32_t i = lane; i < nqb * p.K; i += WAVE) {
+    const uint32_t qq = i / p.K, k = i % p.K;
+    p.partial[((uint64_t)query_of(qq) * p.segments + seg) * (uint64_t)p.K + k] = lists[i];
+  }
+}
+
+// One wavefront per (query tile, row segment): the tile's queries staged, the segment's candidates -- the live nodes, or the
+// compacted ids of the allowed ones -- scored VPW * PU at a time, by the kernel's own loop (see scan_score_batch below).
 template <typename T, int METRIC, int G, int CU, bool FULL>
 __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -47,23 +75,13 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
   const uint32_t tile = blockIdx.x % p.tiles, seg = blockIdx.x / p.tiles;
   const uint32_t q0 = tile * p.tile_queries;
   const uint32_t nqb = min(p.tile_queries, p.nq - q0);
+  uint4* const qlds = reinterpret_cast<uint4*>(smem);                                                     // [tile][q_chunks]
+  uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * p.q_chunks * 16u);  // [tile][K]
   const int K = (int)p.K;
   const uint32_t q_chunks = p.q_chunks;
   const int nchunks = (int)p.nchunks;
-  uint4* const qlds = reinterpret_cast<uint4*>(smem);                                               // [tile][q_chunks]
-  uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * q_chunks * 16u);  // [tile][K]
-
-  {  // the tile's queries, zero padded to q_chunks; every list empty
-    const int padded = (int)(q_chunks * 16u / sizeof(T));
-    const int dim = (int)p.dim;
-    for (uint32_t qq = 0; qq < nqb; qq++) {
-      const T* qsrc = reinterpret_cast<const T*>(p.queries) + (uint64_t)(q0 + qq) * p.dim;
-      T* qdst = reinterpret_cast<T*>(qlds + (size_t)qq * q_chunks);
-      for (int i = lane; i < padded; i += WAVE) qdst[i] = i < dim ? qsrc[i] : T(0);
-    }
-    for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) lists[i] = SCAN_PAD;
-  }
-  wave_sync();
+  const auto query_of = [&](uint32_t qq) { return q0 + qq; };
+  scan_stage_tile<T>(p, qlds, lists, nqb, lane, query_of);
 
   // this block's share of the candidates
   const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
@@ -147,20 +165,16 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
       }
     }
   }
-
-  wave_sync();
-  for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) {
-    const uint32_t qq = i / (uint32_t)K, k = i % (uint32_t)K;
-    p.partial[((uint64_t)(q0 + qq) * p.segments + seg) * (uint64_t)K + k] = lists[i];
-  }
+  scan_flush_tile(p, lists, nqb, seg, lane, query_of);
 }
 
 // ---- grouped filters: one allowed set per query (fnv_search_batch_exhaustive_grouped) --------------------------------------
 // One batch of VPW * PU queued node ids against the tile's nqb staged queries: exhaustive_scan_kernel's loop body -- the same
 // loads, the same per-lane chunk order, group_sum, scan_key and scan_insert, so a distance has the same bits -- with the ids
 // taken from ids[0, nvalid) (LDS) instead of a compacted list; slots from nvalid on repeat the last valid id with val = false.
-// (A copy, not a shared body: the plain scan's instantiations stay instruction for instruction what they were.  Only the GPU
-// tests hold the two bodies to the same bits: ANY change to the scoring of either must be made in both.)
+// (A copy, not a shared body: with the body shared, the plain scan's small launches -- a hundred queries on 1 % of the rows --
+// measured 0.7 % slower, profiles/exhaustive.md.  Only the GPU tests hold the two bodies to the same bits: ANY change to the
+// scoring of either must be made in both.)
 template <typename T, int METRIC, int G, int CU, bool FULL>
 __device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint4* qlds, uint64_t* lists, uint32_t nqb,
                                                  const uint32_t* ids, uint32_t nvalid, int lane) {
@@ -266,25 +280,12 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const Gro
   const GroupTile t = gp.tiles[blockIdx.x % p.tiles];
   const uint32_t nqb = t.count;
   if (nqb == 0u) return;  // (past the real tiles: the launch is an upper bound)
-  const int K = (int)p.K;
-  const uint32_t q_chunks = p.q_chunks;
   uint4* const qlds = reinterpret_cast<uint4*>(smem);
-  uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * q_chunks * 16u);
-  uint32_t* const queue = reinterpret_cast<uint32_t*>(lists + (size_t)p.tile_queries * K);
+  uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * p.q_chunks * 16u);
+  uint32_t* const queue = reinterpret_cast<uint32_t*>(lists + (size_t)p.tile_queries * p.K);
   const uint32_t* const perm = gp.perm + t.first;
-
-  {  // the tile's queries, zero padded to q_chunks; every list empty
-    const int padded = (int)(q_chunks * 16u / sizeof(T));
-    const int dim = (int)p.dim;
-    for (uint32_t qq = 0; qq < nqb; qq++) {
-      const T* qsrc = reinterpret_cast<const T*>(p.queries) + (uint64_t)perm[qq] * p.dim;
-      T* qdst = reinterpret_cast<T*>(qlds + (size_t)qq * q_chunks);
-      for (int i = lane; i < padded; i += WAVE) qdst[i] = i < dim ? qsrc[i] : T(0);
-    }
-    for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) lists[i] = SCAN_PAD;
-  }
-  wave_sync();
-
+  const auto query_of = [&](uint32_t qq) { return perm[qq]; };
+  scan_stage_tile<T>(p, qlds, lists, nqb, lane, query_of);
   const uint32_t* const bits = gp.node_bits + (uint64_t)t.row * gp.row_words;
   const uint32_t wlo = (uint32_t)((uint64_t)gp.live_words * seg / p.segments);
   const uint32_t whi = (uint32_t)((uint64_t)gp.live_words * (seg + 1) / p.segments);
@@ -326,12 +327,7 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const Gro
     }
   }
   if (count) scan_score_batch<T, METRIC, G, CU, FULL>(p, qlds, lists, nqb, queue, count, lane);
-
-  wave_sync();
-  for (uint32_t i = lane; i < nqb * (uint32_t)K; i += WAVE) {
-    const uint32_t qq = i / (uint32_t)K, k = i % (uint32_t)K;
-    p.partial[((uint64_t)perm[qq] * p.segments + seg) * (uint64_t)K + k] = lists[i];
-  }
+  scan_flush_tile(p, lists, nqb, seg, lane, query_of);
 }
 
 #ifndef FNV_INST_FAMILY  // (the kernels below are not templates: beam_search.hip alone emits them, not kernel_inst.hip's units)

@@ -231,6 +231,22 @@ def search_multi(indexes, queries, K: int, ef_search: int, num_initializations: 
     return d, l
 
 
+class _Outputs:
+    """The arrays a host-buffer search fills, in the order the C ABI takes them: dist float32[Q,K], labels int32[Q,K], then the
+    per-query stats count, n_dist and -- for the graph searches -- n_hops."""
+
+    def __init__(self, nq: int, K: int, hops: bool):
+        self.dist = np.empty((nq, K), dtype=np.float32)
+        self.labels = np.empty((nq, K), dtype=np.int32)
+        self.stats = {"count": np.empty(nq, dtype=np.int32), "n_dist": np.zeros(nq, dtype=np.uint64)}
+        if hops:
+            self.stats["n_hops"] = np.zeros(nq, dtype=np.uint64)
+        self.ptrs = [a.ctypes.data for a in (self.dist, self.labels, *self.stats.values())]
+
+    def result(self, stats: bool):
+        return (self.dist, self.labels, self.stats) if stats else (self.dist, self.labels)
+
+
 class DeviceIndex:
     """An index resident in one GPU's HBM (vectors / links / labels in SoA form)."""
 
@@ -368,119 +384,68 @@ class DeviceIndex:
     def set_option(self, name: str, value: int) -> None:
         check(lib().fnv_set_option(self._h, name.encode(), int(value)))
 
-    def search(self, queries, K: int, ef_search: int, num_initializations: int = 100, stats: bool = False):
-        """Host-buffer batched search -> (dist float32[Q,K], labels int32[Q,K][, stats])."""
+    def _batch(self, queries, K: int, k_max, hops: bool):
+        """What the host-buffer searches share: the queries as a C-contiguous array of the element type, checked, nq, and the
+        output arrays (_Outputs).  k_max: the upper bound of K (None: there is none); hops: the search counts hops."""
         q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError("Queries have incorrect dimensions.")
-        nq = q.shape[0]
+        if k_max is not None and not 1 <= K <= k_max:
+            raise ValueError("K of an exhaustive search must be between 1 and %d" % k_max)
         if K <= 0:
             raise ValueError("K must be positive")
-        d = np.empty((nq, K), dtype=np.float32)
-        l = np.empty((nq, K), dtype=np.int32)
-        cnt = np.empty(nq, dtype=np.int32)
-        nd = np.zeros(nq, dtype=np.uint64)
-        nh = np.zeros(nq, dtype=np.uint64)
-        check(lib().fnv_search_batch(self._h, q.ctypes.data, nq, K, ef_search, num_initializations, d.ctypes.data,
-                                     l.ctypes.data, cnt.ctypes.data, nd.ctypes.data, nh.ctypes.data))
-        if stats:
-            return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
-        return d, l
+        return q, q.shape[0], _Outputs(q.shape[0], K, hops)
+
+    def search(self, queries, K: int, ef_search: int, num_initializations: int = 100, stats: bool = False):
+        """Host-buffer batched search -> (dist float32[Q,K], labels int32[Q,K][, stats])."""
+        q, nq, out = self._batch(queries, K, None, True)
+        check(lib().fnv_search_batch(self._h, q.ctypes.data, nq, K, ef_search, num_initializations, *out.ptrs))
+        return out.result(stats)
 
     def search_filtered(self, queries, K: int, ef_search: int, allowed, num_initializations: int = 100, stats: bool = False):
         """Host-buffer batched search restricted to the nodes whose label is allowed (fnv_search_batch_filtered) ->
         (dist float32[Q,K], labels int32[Q,K][, stats]).  `allowed`: see pack_allowed.  Rows with fewer than K allowed
         results are padded with (+inf, -1) (stats["count"] says how many are real); that is not an error."""
-        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError("Queries have incorrect dimensions.")
-        nq = q.shape[0]
-        if K <= 0:
-            raise ValueError("K must be positive")
+        q, nq, out = self._batch(queries, K, None, True)
         bits, n_bits = pack_allowed(allowed)
-        d = np.empty((nq, K), dtype=np.float32)
-        l = np.empty((nq, K), dtype=np.int32)
-        cnt = np.empty(nq, dtype=np.int32)
-        nd = np.zeros(nq, dtype=np.uint64)
-        nh = np.zeros(nq, dtype=np.uint64)
         check(lib().fnv_search_batch_filtered(self._h, q.ctypes.data, nq, K, ef_search, num_initializations,
-                                              bits.ctypes.data if n_bits else None, n_bits, d.ctypes.data, l.ctypes.data,
-                                              cnt.ctypes.data, nd.ctypes.data, nh.ctypes.data))
-        if stats:
-            return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
-        return d, l
+                                              bits.ctypes.data if n_bits else None, n_bits, *out.ptrs))
+        return out.result(stats)
 
     def search_exhaustive(self, queries, K: int, allowed=None, stats: bool = False):
         """Exhaustive search (fnv_search_batch_exhaustive): the exact K nearest among the live nodes, or -- `allowed` given, see
         pack_allowed -- among those whose label is allowed -> (dist float32[Q,K], labels int32[Q,K][, stats]).  Sorted by
         (distance, node id), NaN distances last.  Rows with fewer than K candidates are padded with (+inf, -1);
         stats = {"count": real entries per row, "n_dist": rows evaluated per query = the number of candidates}."""
-        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError("Queries have incorrect dimensions.")
-        nq = q.shape[0]
-        if K <= 0 or K > 1024:
-            raise ValueError("K of an exhaustive search must be between 1 and 1024")
+        q, nq, out = self._batch(queries, K, 1024, False)
         bits, n_bits = pack_allowed(allowed) if allowed is not None else (None, 0)
-        d = np.empty((nq, K), dtype=np.float32)
-        l = np.empty((nq, K), dtype=np.int32)
-        cnt = np.empty(nq, dtype=np.int32)
-        nd = np.zeros(nq, dtype=np.uint64)
         check(lib().fnv_search_batch_exhaustive(self._h, q.ctypes.data, nq, K, 0 if allowed is None else 1,
-                                                bits.ctypes.data if n_bits else None, n_bits, d.ctypes.data, l.ctypes.data,
-                                                cnt.ctypes.data, nd.ctypes.data))
-        if stats:
-            return d, l, {"count": cnt, "n_dist": nd}
-        return d, l
+                                                bits.ctypes.data if n_bits else None, n_bits, *out.ptrs))
+        return out.result(stats)
 
     def search_filtered_grouped(self, queries, K: int, ef_search: int, filters, query_filter, num_initializations: int = 100,
                                 stats: bool = False):
         """search_filtered with one allowed set PER QUERY, in one launch (fnv_search_batch_filtered_grouped) ->
         (dist float32[Q,K], labels int32[Q,K][, stats]).  `filters`: see pack_filters; query_filter[q] = the filter query q
         uses, or -1 for none.  Row q is what search_filtered returns for that query with that filter (search for -1)."""
-        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError("Queries have incorrect dimensions.")
-        nq = q.shape[0]
-        if K <= 0:
-            raise ValueError("K must be positive")
+        q, nq, out = self._batch(queries, K, None, True)
         table, n_bits = pack_filters(filters)
         qf = _query_filter(query_filter, nq, table.shape[0])
-        d = np.empty((nq, K), dtype=np.float32)
-        l = np.empty((nq, K), dtype=np.int32)
-        cnt = np.empty(nq, dtype=np.int32)
-        nd = np.zeros(nq, dtype=np.uint64)
-        nh = np.zeros(nq, dtype=np.uint64)
         check(lib().fnv_search_batch_filtered_grouped(self._h, q.ctypes.data, nq, K, ef_search, num_initializations,
                                                       table.ctypes.data if table.size else None, table.shape[0],
-                                                      table.shape[1], n_bits, qf.ctypes.data, d.ctypes.data, l.ctypes.data,
-                                                      cnt.ctypes.data, nd.ctypes.data, nh.ctypes.data))
-        if stats:
-            return d, l, {"count": cnt, "n_dist": nd, "n_hops": nh}
-        return d, l
+                                                      table.shape[1], n_bits, qf.ctypes.data, *out.ptrs))
+        return out.result(stats)
 
     def search_exhaustive_grouped(self, queries, K: int, filters, query_filter, stats: bool = False):
         """search_exhaustive with one allowed set PER QUERY, in one launch (fnv_search_batch_exhaustive_grouped) ->
         (dist float32[Q,K], labels int32[Q,K][, stats]).  `filters`: see pack_filters; query_filter[q] = the filter query q
         uses, or -1 for every live node.  Row q is what search_exhaustive returns for that query with that filter."""
-        q = np.ascontiguousarray(queries, dtype=_np_dtype(self.dtype))
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError("Queries have incorrect dimensions.")
-        nq = q.shape[0]
-        if K <= 0 or K > 1024:
-            raise ValueError("K of an exhaustive search must be between 1 and 1024")
+        q, nq, out = self._batch(queries, K, 1024, False)
         table, n_bits = pack_filters(filters)
         qf = _query_filter(query_filter, nq, table.shape[0])
-        d = np.empty((nq, K), dtype=np.float32)
-        l = np.empty((nq, K), dtype=np.int32)
-        cnt = np.empty(nq, dtype=np.int32)
-        nd = np.zeros(nq, dtype=np.uint64)
         check(lib().fnv_search_batch_exhaustive_grouped(self._h, q.ctypes.data, nq, K, table.ctypes.data if table.size else None,
-                                                        table.shape[0], table.shape[1], n_bits, qf.ctypes.data, d.ctypes.data,
-                                                        l.ctypes.data, cnt.ctypes.data, nd.ctypes.data))
-        if stats:
-            return d, l, {"count": cnt, "n_dist": nd}
-        return d, l
+                                                        table.shape[0], table.shape[1], n_bits, qf.ctypes.data, *out.ptrs))
+        return out.result(stats)
 
     def search_into(self, queries: np.ndarray, K: int, ef_search: int, dist: np.ndarray, labels: np.ndarray,
                     num_initializations: int = 100) -> None:
