@@ -3,8 +3,8 @@
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container as well as on the MI355X box.
 The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 104
 objects (kernel_inst.hip: 13 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
-half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), plus beam_search.hip (host code, C ABI, re-layout kernels), and
-linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
+half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
+C ABI, the non-template kernels), one object each in the same pool, and linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
 from __future__ import annotations
 
@@ -19,10 +19,16 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
-                                           "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "relayout.hpp",
+                                           "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "runtime.hpp",
                                            "launch_plan.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
-MAIN = os.path.join(CSRC, "beam_search.hip")
+# The host units behind runtime.hpp, which brings launch_plan.hpp (kernel units include neither) and, through kernel_table.h,
+# the device headers that say what a launch passes.  Each unit with the kernel headers it includes on top of those (launch.hip:
+# scan.hpp for its non-template kernels; the others in developer builds, where it instantiates the search kernels itself).
+HOST_HEADERS = ("runtime.hpp", "launch_plan.hpp")
+KERNEL_HEADERS = ("scan.hpp", "kernels.hpp", "merged_beam.hpp", "visited.hpp")
+HOST_UNITS = {"index.hip": (), "launch.hip": KERNEL_HEADERS, "host_search.hip": (), "multi.hip": (), "tune.hip": (),
+              "device_build.hip": ()}
 INST = os.path.join(CSRC, "kernel_inst.hip")
 TYPES = [("float", "f32"), ("uint8_t", "u8"), ("int8_t", "i8"), ("_Float16", "f16")]
 METRICS = [(0, "l2"), (1, "ip")]
@@ -46,7 +52,9 @@ def hipcc() -> str:
 
 def _units(defines):
     """(object path, source, extra -D flags) for every translation unit."""
-    units = [(os.path.join(OBJ, "beam_search.o"), MAIN, [])]
+    units = [(os.path.join(OBJ, name[:-4] + ".o"), os.path.join(CSRC, name), []) for name in HOST_UNITS]
+    if "FNV_DEV_FAST_BUILD" in defines:  # developer build: the host units only, one instantiation per kernel (launch.hip)
+        return [(o, s, f + ["-D" + d for d in defines]) for o, s, f in units]
     for (ctype, tag), families, extra in [(t, FAMILIES, []) for t in TYPES] + [(HALF_ROWS_TYPE, HALF_ROWS_FAMILIES,
                                                                                  ["-DFNV_INST_HALF_ROWS"])]:
         for metric, mtag in METRICS:
@@ -61,8 +69,11 @@ def _stale(obj, src):
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    # relayout.hpp (upload / measurement kernels) and launch_plan.hpp (the launch planner) are included by beam_search.hip only
-    deps = HEADERS if src == MAIN else [h for h in HEADERS if not h.endswith(("relayout.hpp", "launch_plan.hpp"))]
+    name = os.path.basename(src)
+    if name in HOST_UNITS:
+        deps = [h for h in HEADERS if os.path.basename(h) not in KERNEL_HEADERS or os.path.basename(h) in HOST_UNITS[name]]
+    else:  # runtime.hpp and launch_plan.hpp (the launch planner) are included by the host units only
+        deps = [h for h in HEADERS if os.path.basename(h) not in HOST_HEADERS]
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 
 
@@ -70,7 +81,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(d) > t for d in [MAIN, INST] + HEADERS)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(CSRC, name) for name in HOST_UNITS] + [INST] + HEADERS)
 
 
 def build(force: bool = False, verbose: bool = False, defines=(), out: str | None = None, jobs: int | None = None) -> str:
@@ -91,8 +102,6 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str | Non
     if verbose:
         base.insert(1, "-Rpass-analysis=kernel-resource-usage")
     units = [(os.path.join(objdir, os.path.basename(o)), s, f) for o, s, f in _units(defines)]
-    if "FNV_DEV_FAST_BUILD" in defines:  # developer build: one translation unit, one instantiation per kernel
-        units = units[:1]
     todo = [(o, s, f) for o, s, f in units if force or custom or _stale(o, s)]
 
     def compile_one(unit):

@@ -1,4 +1,4 @@
-// distance.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
+// distance.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by the host units).
 // Cross-lane reductions, per-chunk distance arithmetic and the batched gather/distance primitive.
 #pragma once
 #include "half_rows.hpp"
@@ -236,7 +236,7 @@ constexpr bool query_in_regs() {
 // multiplied with chunk c of the query by the same lane as before (lane g of the vector's group: chunks g, g + 8, g + 16 from
 // the main table, then chunk 24 + g from the side table), so every distance keeps its bits.  One row configuration has the
 // form: G = 8, CU = 3 with FULL = false  (FULL = true is the plain 384-byte row: d = 96 float32 / 384 one-byte elements).
-// The host picks it for rows of 3 lines + at most 32 bytes whose side table stays small (beam_search.hip row_layout).
+// The host picks it for rows of 3 lines + at most 32 bytes whose side table stays small (launch_plan.hpp, row_layout).
 // ---------------------------------------------------------------------------------------------
 template <int G, int CU, bool FULL>
 constexpr bool row_has_tail() {

@@ -1,5 +1,5 @@
 // half_rows.hpp -- part of the gfx950 search engine, free of HIP (device code includes it through distance.hpp, the host code
-// through beam_search.hip, tests/half_rows_harness.cpp as it is).  The HALF-WIDTH MIRROR of a float32 vector table: every rule
+// through runtime.hpp, tests/half_rows_harness.cpp as it is).  The HALF-WIDTH MIRROR of a float32 vector table: every rule
 // of it is stated here once -- which rows can have one, where a 16-byte chunk of a float32 row lives in its mirror row, when a
 // float32 value survives binary16, and how one row is converted.
 //

@@ -1,4 +1,4 @@
-// heaps.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
+// heaps.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by the host units).
 // Heap entry packing, phase timers, and the wave-cooperative libstdc++-exact heap operations.
 #pragma once
 #include "search_params.h"

@@ -1,7 +1,7 @@
 // kernel_inst.hip -- one compilation = the instantiations of ONE kernel family for ONE (element type, metric):
 //   hipcc -c -DFNV_INST_T=float -DFNV_INST_TAG=f32 -DFNV_INST_METRIC=0 -DFNV_INST_MTAG=l2 -DFNV_INST_FAMILY=4 -DFNV_INST_FNAME=merged ...
 // The families (ordinal, name) are listed in kernel_table.h (FNV_FOR_EACH_FAMILY).
-// flatnav_amd/build.py compiles the 104 combinations in parallel and links them with beam_search.hip -- and eighteen more for the
+// flatnav_amd/build.py compiles the 104 combinations in parallel and links them with the host units -- and eighteen more for the
 // row format f32h (float32 queries on the half-width mirror, half_rows.hpp; -DFNV_INST_T=fnv_dev::f32h -DFNV_INST_HALF_ROWS):
 // the exact family (without the entry scan) and the merged-beam families with their DIRECT forms, for the row configurations
 // a mirror exists for.

@@ -1,4 +1,4 @@
-// kernels.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
+// kernels.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by the host units).
 // Entry-point scan, the K0 batch kernel, the exact (two-heap) search of one query and its kernel.
 #pragma once
 #include "distance.hpp"

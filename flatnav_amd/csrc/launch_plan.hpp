@@ -1,7 +1,7 @@
 // launch_plan.hpp -- part of the gfx950 search engine: the launch planner, in plain C++ (no HIP header; compiles with g++).
 // Everything the host decides about a search launch by arithmetic alone: the row layout, the visited-table geometry and the
 // LDS layout of a query slot, the table-size ladder and its occupancy trade, the choice of kernel family and variant, the
-// shape of one launch, the layouts fnv_tune tries.  beam_search.hip owns the HIP runtime (kernel pointers, occupancy
+// shape of one launch, the layouts fnv_tune tries.  The host units (runtime.hpp) own the HIP runtime (kernel pointers, occupancy
 // queries, LDS limits, events, buffers) and hands the planner what it needs of it as a `Runtime` object:
 //   int occupancy(int mode, uint32_t lds)                workgroups of MODE_*'s kernel one CU holds with `lds` bytes each (0: error)
 //   const char* raise_lds_limit(int mode, uint32_t lds)  that kernel may be launched with `lds` bytes: null, or the runtime's error
@@ -341,7 +341,7 @@ inline RowGeometry row_geometry(const PlanInputs* ix) {
 // The adaptive choice keeps its measurements per (beam width, batch class: more than one round of queries or not).
 inline int tuner_key(int B, bool multi_round) { return 2 * B + (multi_round ? 1 : 0); }
 
-// What a search launch looks like for one (beam width, K) on one index: cached (beam_search.hip, which adds the kernels),
+// What a search launch looks like for one (beam width, K) on one index: cached (launch.hip, which adds the kernels),
 // because working it out costs several occupancy queries and a single-query search should not pay for them every time.
 struct LaunchPlan {
   bool valid = false;
@@ -468,7 +468,7 @@ inline KernelChoice default_choice(const PlanInputs* ix, const LaunchPlan& plan,
   return c;
 }
 // The adaptive choice ("sorted_beam" = 2) keeps, per tuner_key, the best time of each variant (Tuner); choose_kernel
-// (beam_search.hip) harvests the timings and asks the four rules below.
+// (launch.hip) harvests the timings and asks the four rules below.
 // A pinned variant (fnv_tune's launches / "sorted_variant"): as asked when this launch can run it, else the merged-beam kernel.
 inline int pinned_variant(int pinned, bool multi_round, bool shadows_on) {
   return variant_allowed(pinned, multi_round, true, shadows_on, true) ? pinned : 1;

@@ -1,4 +1,4 @@
-// merged_beam.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units; by beam_search.hip in developer builds).
+// merged_beam.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units; by launch.hip in developer builds).
 //
 // beam_search_merged_kernel -- the default search kernel: the same traversal as beam_search_kernel (the libstdc++-exact
 // two-heap kernel) with the beam held as ONE SORTED ARRAY of at most B entries -- closest first, an "expanded" flag

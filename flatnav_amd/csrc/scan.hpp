@@ -1,7 +1,7 @@
-// scan.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's `scan` units and by beam_search.hip).
+// scan.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's `scan` units and by launch.hip).
 // The EXHAUSTIVE search (fnv_search_batch_exhaustive): the exact K nearest among the live nodes, or among the allowed ones.
 //
-//   1. filtered calls: node_filter_kernel (relayout.hpp) turns the label bitmap into a node bitmap, exhaustive_compact_kernel
+//   1. filtered calls: node_filter_kernel (launch.hip) turns the label bitmap into a node bitmap, exhaustive_compact_kernel
 //      turns that into the list of allowed node ids (any order: the selection's order is total, scan_select.hpp).
 //   2. exhaustive_scan_kernel, one wavefront per (query tile, row segment): the tile's queries are staged in LDS
 //      (scan_stage_tile), a lane group loads the chunks of PU rows into registers ONCE and scores them against every query of
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const Gro
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
 }
 
-#ifndef FNV_INST_FAMILY  // (the kernels below are not templates: beam_search.hip alone emits them, not kernel_inst.hip's units)
+#ifndef FNV_INST_FAMILY  // (the kernels below are not templates: launch.hip alone emits them, not kernel_inst.hip's units)
 // The allowed node ids of a node bitmap (bit i & 31 of word i >> 5), compacted wave by wave: the order is whatever the
 // atomics make it, which the selection does not see.  *count must be zero at launch; ids holds n_live entries.
 static __global__ __launch_bounds__(256) void exhaustive_compact_kernel(const uint32_t* node_bits, uint64_t n_live, uint32_t* ids,

@@ -1,5 +1,5 @@
 // search_params.h -- part of the gfx950 search engine (device code: included by every kernel translation unit and, through
-// kernel_table.h, by beam_search.hip).  What the kernels need on top of search_types.h: the load-pipelining knobs and the
+// kernel_table.h, by the host units).  What the kernels need on top of search_types.h: the load-pipelining knobs and the
 // scalar-register helpers.
 #pragma once
 #include <hip/hip_runtime.h>

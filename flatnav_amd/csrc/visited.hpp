@@ -1,4 +1,4 @@
-// visited.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
+// visited.hpp -- part of the gfx950 search engine (device code; included by kernel_inst.hip's units and by the host units).
 // Exact visited sets in LDS (32-bit open addressing and the 16-bit-tag bucketed table).
 #pragma once
 #include "search_params.h"

@@ -1,4 +1,4 @@
-// wire.hpp -- part of the gfx950 engine (device code; included by kernel_inst.hip's units and by beam_search.hip).
+// wire.hpp -- part of the gfx950 engine (device code; included by kernel_inst.hip's units and by the host units).
 // Device-side graph wiring for batched insertion: the reference's selectNeighbors
 // (include/flatnav/index/Index.h:714-763) and connectNeighbors (:765-834) for a batch of new nodes whose
 // beams (ef_construction nearest wired nodes) the search kernel has just produced.

@@ -81,7 +81,7 @@ def replicate_index(dev, device: int, src: int = 0, group=None, piece_bytes: int
             raise RuntimeError("device buffer smaller than its live rows")
         views.append(torch.as_tensor(_DevView(ptr, want), device="cuda:%d" % device))
     tail = getattr(dev, "tail_bytes", 0)
-    if tail:  # split rows: the side table follows the main table of THIS rank's capacity (csrc/beam_search.hip row_layout)
+    if tail:  # split rows: the side table follows the main table of THIS rank's capacity (csrc/launch_plan.hpp row_layout)
         ptr, nbytes = bufs[0]
         capacity = nbytes // (dev.row_bytes + tail)
         views.append(torch.as_tensor(_DevView(ptr + capacity * dev.row_bytes, dev.n_nodes * tail), device="cuda:%d" % device))

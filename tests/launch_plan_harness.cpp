@@ -86,7 +86,7 @@ void lph_free(void* plan) { delete (Plan*)plan; }
 
 // One unfiltered launch of `nq` queries over `live` nodes on that plan, the way search_device_impl shapes it: the plan's
 // default kernel choice, or `pinned` (>= 0: a variant, as "sorted_variant" pins it).  Fills `out` (lph_shape_columns).
-// The lines between the planner's calls are a TWIN of glue that stays in flatnav_amd/csrc/beam_search.hip -- choose_kernel's
+// The lines between the planner's calls are a TWIN of glue that stays in flatnav_amd/csrc/launch.hip -- choose_kernel's
 // pinned branch with its follow-up (sorted, tail_pct), and search_device_impl's choice of bpc / LDS bytes and its DIRECT
 // condition: what this returns is the planner under this copy, and an edit of either side belongs in the other.
 void lph_launch(const void* plan, uint64_t nq, int num_initializations, uint64_t live, int pinned, int64_t* out) {

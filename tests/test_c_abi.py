@@ -29,8 +29,8 @@ def test_header_and_binding_agree():
 
 
 def test_every_option_the_library_accepts_is_documented_in_the_header():
-    # fnv_set_option's names (csrc/beam_search.hip) against the option list of include/flatnav_hip.h
-    src = open(os.path.join(ROOT, "flatnav_amd", "csrc", "beam_search.hip")).read()
+    # fnv_set_option's names (csrc/index.hip) against the option list of include/flatnav_hip.h
+    src = open(os.path.join(ROOT, "flatnav_amd", "csrc", "index.hip")).read()
     body = src[src.index("int fnv_set_option("):]
     body = body[:body.index("\nint ", 10)]
     names = sorted(set(re.findall(r'n == "([a-z_0-9]+)"', body)))
@@ -77,7 +77,7 @@ def test_argument_validation_needs_no_device(libpath):
 
 
 def test_row_layout_rules_need_no_device(libpath, monkeypatch):
-    # fnv_row_layout: the stride / split-row rule of the vector table (csrc/beam_search.hip row_layout), a pure function of
+    # fnv_row_layout: the stride / split-row rule of the vector table (csrc/launch_plan.hpp row_layout), a pure function of
     # (dim, element type, capacity) and three environment variables
     from flatnav_amd import hip
 

@@ -50,7 +50,7 @@ LAYOUT = {7: (16, 0), 64: (128, 0), 100: (256, 0), 128: (256, 0), 192: (384, 0),
 
 @pytest.mark.parametrize("d", sorted(LAYOUT))
 def test_row_layout(d, monkeypatch):
-    # 2-byte rows follow the byte rule of csrc/beam_search.hip row_layout: 193 ... 208-d float16 = three lines + <= 32 bytes is
+    # 2-byte rows follow the byte rule of csrc/launch_plan.hpp row_layout: 193 ... 208-d float16 = three lines + <= 32 bytes is
     # split; a float16 row of d elements is laid out exactly like a float32 row of d / 2
     from flatnav_amd import build, hip
 

@@ -65,7 +65,7 @@ def test_rows_on_whole_lines_keep_every_bit(oracle_mod, hipmod, dt, dim, metric,
     monkeypatch.delenv("FLATNAV_SPLIT_ROWS")
     layouts = [plain, padded, always]
     rem = rb16 % 128
-    splits = rb16 - rem == 384 and 0 < rem <= 32  # csrc/beam_search.hip row_layout (the side table of 6000 rows is tiny)
+    splits = rb16 - rem == 384 and 0 < rem <= 32  # csrc/launch_plan.hpp row_layout (the side table of 6000 rows is tiny)
     default = _upload(hipmod, ix)  # what a caller gets
     if splits:
         assert default.row_bytes == 384 and default.tail_bytes == rem

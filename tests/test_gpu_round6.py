@@ -83,7 +83,7 @@ def test_replicas_inherit_the_sources_measurements(oracle_mod):
     assert np.array_equal(got[1], want100[1]) and all(np.array_equal(got[2][k], want100[2][k]) for k in ("n_dist", "n_hops"))
 
 
-# ---- SPLIT ROWS (csrc/distance.hpp, beam_search.hip row_layout): three whole lines in the table + the last 16 / 32 bytes of every
+# ---- SPLIT ROWS (csrc/distance.hpp, launch_plan.hpp row_layout): three whole lines in the table + the last 16 / 32 bytes of every
 #      row in a dense side table.  Search parity over the dims that split: tests/test_gpu_round3.py::test_rows_on_whole_lines_keep_every_bit.
 SPLIT_CASES = [("l2", "float32", 100), ("angular", "float32", 104), ("l2", "uint8", 400), ("angular", "int8", 410), ("l2", "float32", 97)]
 

@@ -6,7 +6,7 @@ from flatnav_amd import build as hb
 import io, contextlib, os
 defs = sys.argv[1:]
 cmd = [hb.hipcc(), "-Rpass-analysis=kernel-resource-usage", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function", "-Wno-inline-asm",
-       "-fvisibility=hidden", "-I" + os.path.join(hb.ROOT, "include")] + ["-D" + d for d in defs] + ["-c", hb.MAIN, "-o", "/tmp/resusage.o"]
+       "-fvisibility=hidden", "-I" + os.path.join(hb.ROOT, "include")] + ["-D" + d for d in defs] + ["-c", os.path.join(hb.CSRC, "launch.hip"), "-o", "/tmp/resusage.o"]
 p = subprocess.run(cmd, capture_output=True, text=True)
 cur = None
 rows = {}
