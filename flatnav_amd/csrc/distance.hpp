@@ -243,6 +243,17 @@ constexpr bool row_has_tail() {
   return G == 8 && CU == 3 && !FULL;
 }
 
+// GATHER DEPTH of a row format: the passes the search kernels keep in flight per batch.  passes<G, CU>() was chosen for 12
+// global_load_dwordx4 per lane outstanding on rows of the element type itself (search_params.h).  A mirror row is
+// CU / 2 loads per lane, so the same passes leave half of that in flight -- and, at G = 8, end a batch after 24 vectors: a link
+// row of M = 32 with more than 24 unvisited neighbours (27 % of the hops of c2 at ef = 52) then pays a second dependent gather
+// round trip in the same hop.  Mirror rows at G = 8 take four passes: 32 vectors per batch, 8 (CU = 4) / 4 (CU = 2) loads in
+// flight.  The wider mirror configurations keep their passes (a batch of theirs never held a whole link row).
+template <typename T, int G, int CU>
+constexpr int gather_passes() {
+  return (RowFormat<T>::half_rows && G == 8 && passes<G, CU>() < 4) ? 4 : passes<G, CU>();
+}
+
 template <int G, int CU>
 struct Query {
   const uint4* lds;                           // staged query; not read when the query lives in registers
@@ -262,6 +273,29 @@ struct Query {
 };
 
 // ---------------------------------------------------------------------------------------------
+// One span (G * CU float32 chunks from c0 on) of mirror rows, in two halves: ISSUE requests a lane's CU / 2 units of one row
+// (`rowp`: the row's address + g * 16), FINISH meets them with the staged query.  batch_dists (below) runs the two back to back;
+// the entry scan of the search kernels (kernels.hpp, scan_rows) issues the next batch before it finishes the current one.
+// ---------------------------------------------------------------------------------------------
+template <int G, int CU>
+__device__ __forceinline__ void half_span_issue(const uint8_t* rowp, int c0, uint4 (&y)[CU / 2]) {
+#pragma unroll
+  for (int j = 0; j < CU / 2; j++) y[j] = *reinterpret_cast<const uint4*>(rowp + (c0 / 2 + j * G) * 16);
+}
+template <int METRIC, int G, int CU, int PU>
+__device__ __forceinline__ void half_span_finish(const Query<G, CU>& q, int c0, int g, int npass, const uint4 (&y)[PU][CU / 2],
+                                                 f32x2 (&acc)[PU]) {
+  typedef Dist<f32h, METRIC> D;
+#pragma unroll
+  for (int j = 0; j < CU / 2; j++) {
+    const uint4 xa = q.lds[c0 + (2 * j) * G + g], xb = q.lds[c0 + (2 * j + 1) * G + g];
+#pragma unroll
+    for (int pu = 0; pu < PU; pu++)
+      if (pu < npass) acc[pu] = D::half_chunk(D::half_chunk(acc[pu], xa, y[pu][j].x, y[pu][j].y), xb, y[pu][j].z, y[pu][j].w);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Distances from the query (in LDS, zero padded to q_chunks -- or in registers, above) to one BATCH of up to PU * (64/G) nodes.
 // Lane layout: g = lane % G walks the 16-byte chunks of a row (chunk g, g+G, ...), v = lane / G picks the
 // vector of a pass; pass pu holds batch slot pu*(64/G) + v.  id[pu] is per lane (equal within a G-lane group) and
@@ -273,10 +307,11 @@ struct Query {
 // ---------------------------------------------------------------------------------------------
 // Rows are addressed as rows + id * row_stride: the HBM vector table in the search kernel, an LDS tile in the
 // entry-scan kernel (same arithmetic and summation order in both, so their distances agree bit for bit).
-template <typename T, int METRIC, int G, int CU, bool FULL>
+// PU (deduced from the arrays) = the passes of a batch: passes<G, CU>() in the scan, wiring and K0 kernels, the row format's
+// gather_passes<T, G, CU>() in the search kernels.  Which vectors are in flight together never changes a distance.
+template <typename T, int METRIC, int G, int CU, bool FULL, int PU>
 __device__ __forceinline__ void batch_dists(const uint8_t* rows, uint32_t row_stride, int nchunks, const Query<G, CU>& q,
-                                            const uint32_t (&id)[passes<G, CU>()], int npass, float (&out)[passes<G, CU>()], int lane) {
-  constexpr int PU = passes<G, CU>();
+                                            const uint32_t (&id)[PU], int npass, float (&out)[PU], int lane) {
   typedef Dist<T, METRIC> D;
   typedef typename D::acc_t acc_t;
   const int g = lane % G;
@@ -327,19 +362,9 @@ __device__ __forceinline__ void batch_dists(const uint8_t* rows, uint32_t row_st
     for (int c0 = 0; c0 < nchunks; c0 += G * CU) {
       uint4 y[PU][HU];
 #pragma unroll
-      for (int pu = 0; pu < PU; pu++) {
-        if (pu < npass) {
-#pragma unroll
-          for (int j = 0; j < HU; j++) y[pu][j] = *reinterpret_cast<const uint4*>(rowp[pu] + (c0 / 2 + j * G) * 16);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < HU; j++) {
-        const uint4 xa = q.lds[c0 + (2 * j) * G + g], xb = q.lds[c0 + (2 * j + 1) * G + g];
-#pragma unroll
-        for (int pu = 0; pu < PU; pu++)
-          if (pu < npass) acc[pu] = D::half_chunk(D::half_chunk(acc[pu], xa, y[pu][j].x, y[pu][j].y), xb, y[pu][j].z, y[pu][j].w);
-      }
+      for (int pu = 0; pu < PU; pu++)
+        if (pu < npass) half_span_issue<G, CU>(rowp[pu], c0, y[pu]);
+      half_span_finish<METRIC, G, CU, PU>(q, c0, g, npass, y, acc);
     }
   } else if (FULL) {
     // rows are a whole number of G*CU-chunk spans (e.g. d=128 f32: 32 chunks = 8 lanes x 4): no clamping, no

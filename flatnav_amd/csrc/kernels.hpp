@@ -12,13 +12,76 @@ namespace fnv_dev {
 // wins.  Per lane the node index only grows, so '<' keeps the earliest; across lanes the tie goes to the
 // smaller index.  `rows`/`stride` address row j of the scan set (HBM: j*step-th vector; LDS tile: j-th row).
 // ---------------------------------------------------------------------------------------------
-template <typename T, int METRIC, int G, int CU, bool FULL>
+// PU: the passes of a batch (K0: passes<G, CU>(); the search kernels' own scan: the row format's gather depth).
+//
+// Mirror rows at G = 8, rows of one span, in the merged-beam kernel (entry_point below; what the registers allow without
+// scratch: two batches of PU * CU / 2 units next to the accumulators, 64 of a 128-register budget at CU = 4): the scan is
+// DOUBLE-BUFFERED.  Every query
+// scans the same rows, which sit in L2, and a batch whose loads are only requested after the batch before has been reduced makes
+// the scan a chain of dependent round trips; here batch k + 1 is requested before batch k is met with the query.  All PU passes
+// of a batch are requested whatever their number of real rows (the ids are clamped to the last row: legal, and the same lines
+// again), and one batch past the end likewise, so that no request is conditional -- the waits then count exactly the loads of
+// the batch that is due.  Same arithmetic per pass, same order of the comparisons: the same entry point and distance.
+template <typename T, int G, int CU>
+constexpr bool scan_double_buffered() {
+  return RowFormat<T>::half_rows && G == 8;
+}
+
+template <typename T, int METRIC, int G, int CU, bool FULL, int PU = passes<G, CU>(), bool DOUBLE_BUFFERED = false>
 __device__ __forceinline__ void scan_rows(const uint8_t* rows, uint32_t stride_rows, uint32_t id_mul, int nchunks,
                                           const Query<G, CU>& q, uint32_t count, uint32_t j_base, int lane, float& best_d,
                                           uint32_t& best_j) {
-  constexpr int PU = passes<G, CU>();
   constexpr int VPW = WAVE / G;
   const int v = lane / G;
+  if constexpr (DOUBLE_BUFFERED && scan_double_buffered<T, G, CU>()) {
+    if (nchunks == G * CU && count != 0u) {  // (wave-uniform)
+      typedef Dist<T, METRIC> D;
+      constexpr uint32_t BATCH = VPW * PU;
+      const int g = lane % G;
+      const uint8_t* const lane_rows = rows + g * 16;
+      auto issue = [&](const uint32_t j0, uint4 (&y)[PU][CU / 2]) {
+#pragma unroll
+        for (int pu = 0; pu < PU; pu++)
+          half_span_issue<G, CU>(lane_rows + (uint64_t)(min(j0 + pu * VPW + v, count - 1) * id_mul) * stride_rows, 0, y[pu]);
+      };
+      auto finish = [&](const uint32_t j0, const uint4 (&y)[PU][CU / 2]) {
+        typename D::acc_t acc[PU];
+#pragma unroll
+        for (int pu = 0; pu < PU; pu++) acc[pu] = D::zero();
+        half_span_finish<METRIC, G, CU, PU>(q, 0, g, PU, y, acc);
+#pragma unroll
+        for (int pu = 0; pu < PU; pu++) {
+          const uint32_t j = j0 + pu * VPW + v;
+          const float sd = D::finish(group_sum<G>(D::lane_sum(acc[pu], D::qzero())));
+          if (j < count && sd < best_d) {  // strict '<': first minimum wins (Index.h:864)
+            best_d = sd;
+            best_j = j_base + j;
+          }
+        }
+      };
+      // (the scheduling barriers: left alone the compiler sinks each batch's loads to their first use -- one batch in flight
+      // again; the requests of the next batch stay ABOVE the arithmetic of the current one)
+      uint4 ya[PU][CU / 2], yb[PU][CU / 2];
+      auto two_batches = [&](const uint32_t j0) -> bool {  // ya is under way; returns whether rows are left (ya under way again)
+        issue(j0 + BATCH, yb);
+        __builtin_amdgcn_sched_barrier(0);
+        finish(j0, ya);
+        if (j0 + BATCH >= count) return false;
+        issue(j0 + 2 * BATCH, ya);
+        __builtin_amdgcn_sched_barrier(0);
+        finish(j0 + BATCH, yb);
+        return j0 + 2 * BATCH < count;
+      };
+      // The first four batches (the default scan of 100 rows is four of 32) are straight-line code: around a loop's back edge
+      // the compiler's wait-count bookkeeping gives up and waits for everything in flight at the loop's head.
+      issue(0u, ya);
+      uint32_t j0 = 0;
+      bool more = two_batches(j0);
+      if (more) more = two_batches(j0 += 2 * BATCH);
+      while (more) more = two_batches(j0 += 2 * BATCH);
+      return;
+    }
+  }
   for (uint32_t j0 = 0; j0 < count; j0 += VPW * PU) {
     uint32_t sid[PU];
     bool sval[PU];
@@ -171,18 +234,25 @@ __device__ __forceinline__ void clear_spill_bitmap(uint32_t* bitmap, const uint3
   __threadfence();
 }
 
-// Next query of this slot (-1: none left) from the launch's atomic dispenser.
-__device__ __forceinline__ int next_query(int lane) {
+// Next work item of this slot (-1: none left).  A slot's FIRST item is its block index: no round trip before the first query,
+// and a launch does not open with every slot's atomic on one word.  The launch's atomic dispenser (zero at launch) hands out the
+// items from gridDim.x on, so every item below nq is still taken exactly once, in ascending order per slot.
+__device__ __forceinline__ int next_query(int lane, bool first) {
   ColdArgs c = cold_args();
-  int qi = 0;
-  if (lane == 0) qi = (int)atomicAdd(c->dispenser, 1u);
-  qi = rfl(qi);
+  int qi = (int)blockIdx.x;
+  if (!first) {
+    if (lane == 0) qi = (int)(atomicAdd(c->dispenser, 1u) + gridDim.x);
+    qi = rfl(qi);
+  }
   if ((uint32_t)qi >= c->nq) return -1;
   return qi;
 }
 
 // Entry point of query qi and its distance: from the batch kernel K0 if it ran, else the in-kernel scan.
-template <typename T, int METRIC, int G, int CU, bool FULL>
+// DOUBLE_BUFFERED: the merged-beam kernel's scan on the row formats of scan_double_buffered().  The two-heap kernels keep the
+// batch-by-batch scan: with two batches of units next to the four-pass gather their {8,4} inner-product unit no longer fits its
+// 128 registers (8 bytes of scratch per lane).
+template <typename T, int METRIC, int G, int CU, bool FULL, bool DOUBLE_BUFFERED = false>
 __device__ __forceinline__ uint32_t entry_point(const uint8_t* vectors, uint32_t row_bytes, int nchunks, const Query<G, CU>& q,
                                                 int qi, int lane, float& best_d) {
   ColdArgs c = cold_args();
@@ -194,7 +264,7 @@ __device__ __forceinline__ uint32_t entry_point(const uint8_t* vectors, uint32_t
   best_d = std::numeric_limits<float>::max();
   uint32_t best_j = 0;
   const uint32_t step = c->scan_step;
-  scan_rows<T, METRIC, G, CU, FULL>(vectors, row_bytes, step, nchunks, q, c->n_scan, 0u, lane, best_d, best_j);
+  scan_rows<T, METRIC, G, CU, FULL, gather_passes<T, G, CU>(), DOUBLE_BUFFERED>(vectors, row_bytes, step, nchunks, q, c->n_scan, 0u, lane, best_d, best_j);
   wave_argmin(best_d, best_j);
   return best_j * step;
 }
@@ -365,7 +435,7 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
   // is then computed per call instead of being hoisted to the kernel entry, where the merged-beam kernel, which inlines
   // this function for its rare re-runs, would have to keep it alive across its own hop loop and spill it to scratch)
   asm volatile("" : "+v"(lane));
-  constexpr int PU = passes<G, CU>();
+  constexpr int PU = gather_passes<T, G, CU>();
   const uint8_t* const vectors = x.vectors;
   const uint32_t* const links = x.links;
   const uint32_t row_bytes = x.row_bytes;
@@ -728,8 +798,8 @@ __global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) vo
   x.stage_ids = reinterpret_cast<uint32_t*>(smem + p.off_stage_ids);
   x.ovf_list = reinterpret_cast<uint32_t*>(smem + p.off_ovf);
 
-  while (true) {
-    const int qi = next_query(lane);
+  for (bool first = true;; first = false) {
+    const int qi = next_query(lane, first);
     if (qi < 0) break;
     PH_DECL
     Query<G, CU> q;
@@ -770,8 +840,8 @@ __global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) vo
   x.stage_ids = reinterpret_cast<uint32_t*>(smem + p.off_stage_ids);
   x.ovf_list = reinterpret_cast<uint32_t*>(smem + p.off_ovf);
 
-  while (true) {
-    const int qi = next_query(lane);
+  for (bool first = true;; first = false) {
+    const int qi = next_query(lane, first);
     if (qi < 0) break;
     PH_DECL
     Query<G, CU> q;

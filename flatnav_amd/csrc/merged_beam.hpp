@@ -116,17 +116,17 @@ __global__ __launch_bounds__(WAVE, CU == 1 ? 5 : R == MB_R ? 3 : waves_per_simd<
   //  The four-chunk form -- beams of 129-256 entries -- is compiled for THREE waves per SIMD (168 registers, round 4): its
   //  LDS footprint, a 6144-slot table next to the beam, keeps at most 9-11 queries per CU resident anyway, and at four
   //  waves it kept 4-8 registers of the merge in scratch memory)
-  constexpr int PU = passes<G, CU>();
+  constexpr int PU = gather_passes<T, G, CU>();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane_of_kernel = threadIdx.x;
   const float INF = std::numeric_limits<float>::infinity();
 
-  while (true) {
+  for (bool first = true;; first = false) {
     // (opaque per query, like the tail's below: lane-derived constants of the prologue are computed per query, not kept
     // alive -- in scratch, in the four-chunk form -- from the kernel's entry on)
     int lane = lane_of_kernel;
     asm volatile("" : "+v"(lane));
-    const int item = next_query(lane);
+    const int item = next_query(lane, first);
     if (item < 0) break;
 #ifdef FNV_TIMELINE  // developer build (tools/dev/launch_timeline.py): the per-query counters carry start / end clock readings instead
     const unsigned long long tl_start = wall_clock64();
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(WAVE, CU == 1 ? 5 : R == MB_R ? 3 : waves_per_simd<
     PH_MARK(0);
 
     float best_d;
-    uint32_t entry = entry_point<T, METRIC, G, CU, FULL>(vectors, row_bytes, nchunks, q, qi, lane, best_d);
+    uint32_t entry = entry_point<T, METRIC, G, CU, FULL, true>(vectors, row_bytes, nchunks, q, qi, lane, best_d);
     PH_MARK(1);
     best_d = rfl(best_d);
     entry = (uint32_t)rfl((int)entry);

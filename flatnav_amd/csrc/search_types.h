@@ -36,7 +36,7 @@ struct SearchParams {
   int32_t* out_count;       // [nq] or null
   uint64_t* out_ndist;      // [nq] or null
   uint64_t* out_nhops;      // [nq] or null
-  uint32_t* dispenser;      // next query id
+  uint32_t* dispenser;      // zero at launch; next work item = gridDim.x + its value (a slot's first item is its block index)
   uint32_t* redo_count;     // merged-beam kernel: [0] queries it handed to the exact search (equal keys at a decision),
                             // [1..4] by reason, [5] of them resumed from their log, [6] hops taken from the logs,
                             // [7] hops the merged-beam passes of the resumed queries had made

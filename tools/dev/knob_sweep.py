@@ -87,6 +87,8 @@ for item in [x for x in args.libs.split(",") if x]:
     m = load_hip(path, name)
     if hasattr(m.lib(), "fnv_index_adopt"):  # the same buffers, no copy
         d2 = m.DeviceIndex.adopt(dev.device_buffers(), M, N, DT, cfg["metric"], DIM, device=0, keep_alive=index)
+        if dev.half_rows()["state"] == "live" and hasattr(m.lib(), "fnv_index_build_half_rows"):
+            d2.build_half_rows()  # (an adopted handle has no mirror until asked: like against like)
     else:  # an older build: its own copy
         d2 = m.DeviceIndex.alloc(M, N, DT, cfg["metric"], DIM, device=0)
         for (sp, sb), (dp, db) in zip(dev.device_buffers(), d2.device_buffers()):
