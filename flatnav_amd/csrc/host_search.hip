@@ -72,6 +72,8 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   SearchOptions opt;
   opt.exhaustive = exhaustive;
   const bool grouped = host_filter && host_filter->grouped;
+  // (filter routing: a routed call's scan stage writes whole rows a second time -- it takes the staged copies, as grouped calls do)
+  const bool staged_only = grouped || (host_filter && !exhaustive && (ix->filter_scan_max > 0 || ix->filter_scan_on_overflow != 0));
   if (grouped) {  // the filter table (its rows `stride` apart, as the caller has them), then query_filter, through d_allowed
     const size_t row_bytes = (size_t)((host_filter->n_bits + 7) / 8);
     const size_t tbytes = host_filter->n_filters && row_bytes ? (size_t)(host_filter->n_filters - 1) * host_filter->stride + row_bytes : 0;
@@ -134,7 +136,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   // size (round 6): the kernel reads the queries from and writes the results into the caller's own memory -- each query
   // crosses PCIe once while the launch runs, nothing is copied before or after it.  (Batches that fit the staging buffer take
   // the path below whatever their memory is: one attribute query per array costs more than their copies.)
-  if (!pinned && ix->host_zero_copy != 0 && !grouped) {  // (grouped calls: always the staged copies)
+  if (!pinned && ix->host_zero_copy != 0 && !staged_only) {  // (grouped and routed calls: always the staged copies)
     auto device_view = [](const void* host) -> void* {
       if (!host) return nullptr;
       hipPointerAttribute_t a;
@@ -165,7 +167,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   // time +0-3 %, wall time of a call -13 ... -40 us at every batch size from 1 to 1024 queries (one query: 0.157 -> 0.143 ms
   // at ef=50; 64: 0.24-0.26 -> 0.215 ms; 1024: 0.446 -> 0.405 ms).
   uint8_t* h = (uint8_t*)ix->h_pin;  // (small batches)
-  if (pinned && nq <= (uint64_t)ix->host_zero_copy && !grouped) {
+  if (pinned && nq <= (uint64_t)ix->host_zero_copy && !staged_only) {
     memcpy(h + qoff, queries, qbytes);
     *(int32_t*)(h + soff) = ST_OK;
     const SearchOutputs pin_slab = lay_out_slab(h + ooff, nq, K);
@@ -269,7 +271,10 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
     // from 1 / 2 / 3 / 4 caller threads on four lanes; at 50M nodes one full-grid lane is 19 GB and the second does not fit.
     // Admission, reservation and creation happen under lane_mu: two concurrent callers cannot both pass the budget
     // test, and a batch that fits no lane (large index, FLATNAV_LANE_BUDGET_MB=0) creates none.  (The lock order: fnv_index_s.)
-    const size_t need = launch_workspace_bytes(ix, nq) + (host_filter && host_filter->grouped ? filter_rows_bytes(ix, *host_filter) : 0);
+    // (a routed filtered search: its node bitmaps -- the grouped call's own among them --, grouping arrays, route words and partial lists)
+    const size_t routed_need = host_filter && !exhaustive ? routed_workspace_bytes(ix, *host_filter, nq, K) : 0;
+    const size_t need = launch_workspace_bytes(ix, nq) +
+                        (routed_need ? routed_need : host_filter && host_filter->grouped ? filter_rows_bytes(ix, *host_filter) : 0);
     if (need <= ix->lane_budget_bytes) {
       std::lock_guard<std::mutex> admission(ix->lane_mu);
       for (int which = 1; which < fnv_index_s::kMaxLanes; which++) {

@@ -606,12 +606,15 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   else if (n == "visited_direct") ix->visited_direct = value;  // (read per launch)
   else if (n == "host_zero_copy") ix->host_zero_copy = value;  // (read per host-buffer call)
   else if (n == "scan_segment_rows") ix->scan_segment_rows = value;  // (read per exhaustive launch)
+  else if (n == "filter_scan_max") ix->filter_scan_max = value;  // (read per filtered launch, like the next)
+  else if (n == "filter_scan_on_overflow") ix->filter_scan_on_overflow = value != 0;
   else if (n == "half_rows") ix->half_rows = value;  // (read per launch; the mirror's launches are another kernel's: measurements go)
   else return fail(FNV_ERR_INVALID, "unknown option: " + n);
   // What fnv_tune measured (kernel variant, LDS layout) stays valid across options that change neither the launch plan
   // nor the kernel choice: Index.h::addBatchDevice flips output_node_ids around every device build, and a tune costs
   // dozens of launches.  (output_node_ids is read per launch; shadow_exact per launch; tune_layout by fnv_tune itself.)
-  const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows";
+  const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows" ||
+                            n == "filter_scan_max" || n == "filter_scan_on_overflow";  // (filtered launches never touch the tuner)
   if (!keeps_tuning) {
     ix->options_version++;
     ix->tuner.clear();

@@ -670,7 +670,19 @@ __device__ __forceinline__ void exact_query(const ExactCtx& x, const Query<G, CU
       if (c->out_count) c->out_count[qi] = err ? 0 : cnt;
       if (c->out_ndist) c->out_ndist[qi] = n_dist;
       if (c->out_nhops) c->out_nhops[qi] = n_hops;
-      if (err) {
+      if constexpr (FILTER) {
+        // Overflow routing (scan_select.hpp): the scan stage answers this query and overwrites the row above; no status is raised.
+        // (A branch of its own, the unfiltered kernels' statement below left word for word: they compile as they did.)
+        if (err) {
+          uint32_t* const route = c->query_route;
+          if (route && route[c->nq] != 0u) {
+            route[qi] = ROUTE_OVERFLOW;
+          } else {
+            atomicMax(c->status, err);
+            if (c->host_status) __hip_atomic_store(c->host_status, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          }
+        }
+      } else if (err) {
         atomicMax(c->status, err);
         if (c->host_status) __hip_atomic_store(c->host_status, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // (every writer stores the same code)
       }
@@ -843,6 +855,9 @@ __global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) vo
   for (bool first = true;; first = false) {
     const int qi = next_query(lane, first);
     if (qi < 0) break;
+    // filter routing (scan_select.hpp): a query that was handed to the scan before the launch costs one dispenser step
+    if (const uint32_t* const route = cold_args()->query_route)
+      if (rfl((int)route[qi]) != (int)ROUTE_GRAPH) continue;
     PH_DECL
     Query<G, CU> q;
     stage_query<T>(q, qlds, x.vis, x.ovf_list, qi, x.tagged, lane);

@@ -371,9 +371,10 @@ static void record_launch(fnv_index_s* ix, hipStream_t stream, uint64_t grid, ui
   for (int i = 0; i < 8; i++) ix->geom[i] = geom[i];
 }
 // The grouping arrays of a grouped scan (scan.hpp's group_* kernels), as uint32 offsets into one buffer.
+// `routed` (the scan stage of a routed filtered graph search): nq route words and the overflow flag behind them as well.
 struct GroupArrays {
-  size_t query_row, perm, counts, cursor, row_count, slot_start, tile_start, tiles, bytes;
-  GroupArrays(uint64_t nq, uint64_t rows, uint64_t tile_bound) {
+  size_t query_row, perm, counts, cursor, row_count, slot_start, tile_start, tiles, route, bytes;
+  GroupArrays(uint64_t nq, uint64_t rows, uint64_t tile_bound, bool routed = false) {
     query_row = 0;
     perm = query_row + nq;
     counts = perm + nq;  // counts | cursor | row_count: cleared by one memset
@@ -382,7 +383,8 @@ struct GroupArrays {
     slot_start = row_count + rows;
     tile_start = slot_start + rows + 1;
     tiles = tile_start + rows + 1;
-    bytes = (tiles + 3 * tile_bound) * 4;
+    route = tiles + 3 * tile_bound;
+    bytes = (route + (routed ? nq + 1 : 0)) * 4;
   }
 };
 
@@ -393,6 +395,7 @@ struct GroupArrays {
 constexpr uint32_t kScanLdsBudget = 20u << 10;  // per block: eight blocks per CU = two wavefronts per SIMD
 constexpr uint32_t kScanMaxTile = 32, kScanMaxSegments = 64, kScanForcedSegments = 1024;
 constexpr uint64_t kScanPartialBudget = 256ull << 20;
+constexpr uint32_t kScanMaxLds = 160u << 10;  // one query and its list must fit a block's LDS
 struct ScanShape {
   uint32_t tile, tiles, segments, lds;
 };
@@ -420,32 +423,44 @@ static ScanShape scan_shape(const fnv_index_s* ix, const RowGeometry& g, uint64_
   return s;
 }
 
-static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, const SearchOutputs& out, void* hip_stream,
-                            const SearchOptions& opt) {
-  int rc;
-  if (K < 1 || K > SCAN_MAX_K) return fail(FNV_ERR_INVALID, "K of an exhaustive search must be between 1 and 1024");
-  if (!batch_to_launch(d_queries, nq, out, &rc)) return rc;
+// Filter routing of a filtered graph search ("filter_scan_max" / "filter_scan_on_overflow", scan_select.hpp): whether this launch
+// routes, its filter as a TABLE -- the grouped call's own, or, the single-filter call, a table of that one filter with a null
+// query_filter (every query reads row 0) -- and the shape of the scan stage.  Routing is not applied where the scan cannot take
+// the call (K beyond its lists, rows too long for its LDS): an option never makes a valid call invalid.
+struct RoutedLaunch {
+  bool on = false;
+  SearchFilter table{nullptr, 0};
+  ScanShape shape{};
+};
+static RoutedLaunch plan_routing(const fnv_index_s* ix, const SearchFilter* filter, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
+  RoutedLaunch r;
+  if (!filter || (ix->filter_scan_max <= 0 && ix->filter_scan_on_overflow == 0) || K > SCAN_MAX_K) return r;
+  r.table = *filter;
+  if (!filter->grouped) {
+    r.table.grouped = true;
+    r.table.n_filters = 1;
+    r.table.stride = (filter->n_bits + 7) / 8;
+    r.table.query_filter = nullptr;
+  }
+  r.shape = scan_shape(ix, g, nq, K, live, r.table.rows());
+  r.on = r.shape.lds <= kScanMaxLds;
+  return r;
+}
+// HBM a routed launch of `nq` queries takes on top of the search kernel's per-slot workspace (0: the launch does not route): the
+// node bitmaps, the grouping arrays with the route words, the partial lists.  What a host-buffer caller's lane is admitted with.
+size_t routed_workspace_bytes(fnv_index_s* ix, const SearchFilter& f, uint64_t nq, int K) {
   std::lock_guard<std::mutex> lock(ix->mu);
-  ON_DEVICE(ix->device);
-  hipStream_t stream = (hipStream_t)hip_stream;
-  const SearchFilter* filter = opt.filter;
   const uint64_t live = live_nodes(ix);
-  const RowGeometry g = row_geometry(ix);
-  const bool grouped = filter && filter->grouped;
-  const ScanShape shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
-  if (shape.lds > 160u * 1024u) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
-  const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
-  const scan_grouped_fn kern_g = kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full];
-  const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
+  if (nq == 0 || nq > 0x7FFFFFFFull || K < 1) return 0;
+  const RoutedLaunch r = plan_routing(ix, &f, row_geometry(ix), nq, K, live);
+  if (!r.on) return 0;
+  return filter_rows_bytes(ix, r.table) + GroupArrays(nq, r.table.rows(), r.shape.tiles, true).bytes +
+         (size_t)nq * r.shape.segments * (size_t)K * 8;
+}
 
-  rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
-  if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
-  if (!rc && grouped) rc = ix->ws.group.grow(ga.bytes);
-  if (!rc && filter && !grouped) rc = ix->d_nodebits.grow((size_t)node_words(ix) * 4);
-  if (!rc && filter && !grouped) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
-  ix->ws_bytes = ix->ws.bytes();
-  if (rc) return rc;
-
+// What the scan kernels are told about the index and the call (cand_ids / cand_count, the single-filter scan's own, stay null).
+static ScanParams scan_params(const fnv_index_s* ix, const RowGeometry& g, const void* d_queries, uint64_t nq, int K,
+                              const SearchOutputs& out, const SearchOptions& opt, const ScanShape& shape, uint64_t live) {
   ScanParams p;
   memset(&p, 0, sizeof(p));
   p.vectors = ix->d_vectors;
@@ -468,32 +483,87 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   p.segments = shape.segments;
   p.tile_queries = shape.tile;
   p.tiles = shape.tiles;
+  return p;
+}
+// The queries of a grouped scan grouped by filter row into tiles (scan.hpp's group_* kernels; counts and cursor are zero, the
+// filter rows and row_count under way on `stream`), and what the scan and its merge are told about it.  `route` (null: every
+// query): the route words of a routed filtered graph search, whose scan stage takes only the queries whose word is set.
+static int launch_grouping(fnv_index_s* ix, const SearchFilter& f, const GroupArrays& ga, const ScanShape& shape, uint64_t nq, uint64_t live,
+                           hipStream_t stream, const uint32_t* route, GroupedScanParams* gp) {
+  uint32_t* const w = ix->ws.group.as<uint32_t>();
+  const uint32_t rows = (uint32_t)f.rows(), n = (uint32_t)nq;
+  if (route)
+    hipLaunchKernelGGL(group_rows_routed_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, f.query_filter, route, n,
+                       (uint32_t)f.n_filters, w + ga.query_row, w + ga.counts);
+  else
+    hipLaunchKernelGGL(group_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, f.query_filter, n, (uint32_t)f.n_filters,
+                       w + ga.query_row, w + ga.counts);
+  hipLaunchKernelGGL(group_prefix_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t*)(w + ga.counts), rows, shape.tile,
+                     w + ga.slot_start, w + ga.tile_start);
+  hipLaunchKernelGGL(group_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t*)(w + ga.query_row), n,
+                     (const uint32_t*)(w + ga.slot_start), w + ga.cursor, w + ga.perm);
+  hipLaunchKernelGGL(group_tiles_kernel, dim3((shape.tiles + 255) / 256), dim3(256), 0, stream, (const uint32_t*)(w + ga.slot_start),
+                     (const uint32_t*)(w + ga.tile_start), rows, shape.tile, shape.tiles, (GroupTile*)(w + ga.tiles));
+  HIP_TRY(hipGetLastError());
+  gp->node_bits = ix->ws.rows.as<uint32_t>();
+  gp->tiles = (const GroupTile*)(w + ga.tiles);
+  gp->perm = w + ga.perm;
+  gp->query_row = w + ga.query_row;
+  gp->row_count = w + ga.row_count;
+  gp->row_words = (uint32_t)node_words(ix);
+  gp->live_words = (uint32_t)((live + 31) / 32);
+  return FNV_OK;
+}
+// The grouped scan and its merge.  `route` as above: the merge then answers the routed queries only and zeroes their out_nhops.
+static int launch_grouped_scan(fnv_index_s* ix, scan_grouped_fn kern_g, const GroupedScanParams& gp, const ScanShape& shape, uint64_t nq,
+                               hipStream_t stream, const uint32_t* route = nullptr, uint64_t* out_nhops = nullptr) {
+  const uint32_t merge_lds = 3u * gp.s.K * 8u;
+  HIP_TRY(raise_lds_limit((const void*)kern_g, ix->device, shape.lds));
+  hipLaunchKernelGGL(kern_g, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp);
+  HIP_TRY(hipGetLastError());
+  if (route) hipLaunchKernelGGL(exhaustive_merge_routed_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, gp, route, out_nhops);
+  else hipLaunchKernelGGL(exhaustive_merge_grouped_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, gp);
+  HIP_TRY(hipGetLastError());
+  return FNV_OK;
+}
+
+static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, const SearchOutputs& out, void* hip_stream,
+                            const SearchOptions& opt) {
+  int rc;
+  if (K < 1 || K > SCAN_MAX_K) return fail(FNV_ERR_INVALID, "K of an exhaustive search must be between 1 and 1024");
+  if (!batch_to_launch(d_queries, nq, out, &rc)) return rc;
+  std::lock_guard<std::mutex> lock(ix->mu);
+  ON_DEVICE(ix->device);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const SearchFilter* filter = opt.filter;
+  const uint64_t live = live_nodes(ix);
+  const RowGeometry g = row_geometry(ix);
+  const bool grouped = filter && filter->grouped;
+  const ScanShape shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
+  if (shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
+  const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
+  const scan_grouped_fn kern_g = kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full];
+  const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
+
+  rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
+  if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
+  if (!rc && grouped) rc = ix->ws.group.grow(ga.bytes);
+  if (!rc && filter && !grouped) rc = ix->d_nodebits.grow((size_t)node_words(ix) * 4);
+  if (!rc && filter && !grouped) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
+  ix->ws_bytes = ix->ws.bytes();
+  if (rc) return rc;
+
+  ScanParams p = scan_params(ix, g, d_queries, nq, K, out, opt, shape, live);
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));  // (the status word: this path never sets it)
   GroupedScanParams gp;
   memset(&gp, 0, sizeof(gp));
   if (grouped) {  // the filter table -> this handle's node bitmaps and their popcounts; the queries grouped by row into tiles
     uint32_t* const w = ix->ws.group.as<uint32_t>();
-    const uint32_t rows = (uint32_t)filter->rows(), n = (uint32_t)nq;
-    HIP_TRY(hipMemsetAsync(w + ga.counts, 0, (size_t)3 * rows * 4, stream));  // counts | cursor | row_count
+    HIP_TRY(hipMemsetAsync(w + ga.counts, 0, (size_t)3 * filter->rows() * 4, stream));  // counts | cursor | row_count
     rc = launch_filter_rows(ix, *filter, live, stream, w + ga.row_count);
+    if (!rc) rc = launch_grouping(ix, *filter, ga, shape, nq, live, stream, nullptr, &gp);
     if (rc) return rc;
-    hipLaunchKernelGGL(group_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, filter->query_filter, n,
-                       (uint32_t)filter->n_filters, w + ga.query_row, w + ga.counts);
-    hipLaunchKernelGGL(group_prefix_kernel, dim3(1), dim3(256), 0, stream, (const uint32_t*)(w + ga.counts), rows, shape.tile,
-                       w + ga.slot_start, w + ga.tile_start);
-    hipLaunchKernelGGL(group_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t*)(w + ga.query_row), n,
-                       (const uint32_t*)(w + ga.slot_start), w + ga.cursor, w + ga.perm);
-    hipLaunchKernelGGL(group_tiles_kernel, dim3((shape.tiles + 255) / 256), dim3(256), 0, stream, (const uint32_t*)(w + ga.slot_start),
-                       (const uint32_t*)(w + ga.tile_start), rows, shape.tile, shape.tiles, (GroupTile*)(w + ga.tiles));
-    HIP_TRY(hipGetLastError());
-    gp.node_bits = ix->ws.rows.as<uint32_t>();
-    gp.tiles = (const GroupTile*)(w + ga.tiles);
-    gp.perm = w + ga.perm;
-    gp.query_row = w + ga.query_row;
-    gp.row_count = w + ga.row_count;
-    gp.row_words = (uint32_t)node_words(ix);
-    gp.live_words = (uint32_t)((live + 31) / 32);
   } else if (filter) {  // the label bitmap -> this handle's node bitmap -> the list of allowed node ids
     uint32_t* const ids = ix->d_scanids.as<uint32_t>();
     rc = launch_node_filter(ix, *filter, live, stream);
@@ -510,10 +580,8 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const uint32_t merge_lds = 3u * (uint32_t)K * 8u;
   if (grouped) {
     gp.s = p;
-    HIP_TRY(raise_lds_limit((const void*)kern_g, ix->device, shape.lds));
-    hipLaunchKernelGGL(kern_g, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(exhaustive_merge_grouped_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, gp);
+    rc = launch_grouped_scan(ix, kern_g, gp, shape, nq, stream);
+    if (rc) return rc;
   } else {
     HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
     hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, p);
@@ -573,8 +641,21 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   const uint32_t nslots = shape.nslots, tail_shadows = shape.tail_shadows;
 
   const bool grouped = filter && filter->grouped;
-  rc = grow_workspace(ix, shape.max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr && !grouped);
-  if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
+  // Filter routing (scan_select.hpp): with an option on, and wherever the scan can take the call (else the graph form as ever),
+  // the launch keeps a route word per query and a scan stage follows the search kernel.  One routed implementation: the
+  // single-filter call becomes a grouped launch over a table of one filter (a null query_filter reads row 0).
+  const RowGeometry sg = row_geometry(ix);
+  const RoutedLaunch routing = plan_routing(ix, filter, sg, nq, K, live);
+  const bool routed = routing.on;
+  const SearchFilter& table = routing.table;
+  const ScanShape& sshape = routing.shape;
+  const SearchFilter* const rows_of = routed ? &table : grouped ? filter : nullptr;  // the launch reads a table of node bitmaps
+  const GroupArrays ga(nq, routed ? table.rows() : 0, sshape.tiles, true);
+  rc = grow_workspace(ix, shape.max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr && !rows_of);
+  if (!rc && rows_of) rc = grow_filter_rows(ix, *rows_of);
+  if (!rc && routed) rc = ix->ws.scan.grow((size_t)nq * sshape.segments * (size_t)K * 8);
+  if (!rc && routed) rc = ix->ws.group.grow(ga.bytes);
+  ix->ws_bytes = ix->ws.bytes();
   if (rc) return rc;
 
   SearchParams p = sorted ? plan.sorted : plan.heaps;
@@ -606,13 +687,22 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   p.tail_exact = shape.tail_exact;
 
   HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));
-  if (grouped) {  // the filter table -> this handle's node bitmaps; every query reads its own row
-    rc = launch_filter_rows(ix, *filter, live, stream, nullptr);
+  uint32_t* const gw = routed ? ix->ws.group.as<uint32_t>() : nullptr;
+  if (rows_of) {  // the filter table -> this handle's node bitmaps; every query reads its own row
+    if (routed) HIP_TRY(hipMemsetAsync(gw + ga.counts, 0, (size_t)3 * table.rows() * 4, stream));  // counts | cursor | row_count
+    rc = launch_filter_rows(ix, *rows_of, live, stream, routed ? gw + ga.row_count : nullptr);
     if (rc) return rc;
     p.node_bits = ix->ws.rows.as<uint32_t>();
-    p.query_filter = filter->query_filter;
+    p.query_filter = rows_of->query_filter;
     p.filter_words = (uint32_t)node_words(ix);
-    p.n_filters = (uint32_t)filter->n_filters;
+    p.n_filters = (uint32_t)rows_of->n_filters;
+    if (routed) {  // the rows' popcounts -> who goes to the scan before the search kernel has seen it
+      hipLaunchKernelGGL(route_queries_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, stream, table.query_filter, (uint32_t)nq,
+                         (uint32_t)table.n_filters, (const uint32_t*)(gw + ga.row_count), (uint64_t)ix->filter_scan_max,
+                         (uint32_t)(ix->filter_scan_on_overflow != 0), gw + ga.route);
+      HIP_TRY(hipGetLastError());
+      p.query_route = gw + ga.route;
+    }
   } else if (filter) {
     rc = launch_node_filter(ix, *filter, live, stream);
     if (rc) return rc;
@@ -657,6 +747,15 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   HIP_TRY(raise_lds_limit((const void*)kern.fn, ix->device, lds_bytes));
   hipLaunchKernelGGL(kern.fn, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
   HIP_TRY(hipGetLastError());
+  if (routed) {  // the scan stage, on the same stream: the queries whose route word is set, grouped by filter row into tiles
+    GroupedScanParams gp;
+    memset(&gp, 0, sizeof(gp));
+    rc = launch_grouping(ix, table, ga, sshape, nq, live, stream, gw + ga.route, &gp);
+    if (rc) return rc;
+    gp.s = scan_params(ix, sg, d_queries, nq, K, out, opt, sshape, live);
+    rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[sg.cfg][sg.full], gp, sshape, nq, stream, gw + ga.route, out.nhops);
+    if (rc) return rc;
+  }
   HIP_TRY(hipEventRecord(ix->ev1, stream));
   // (f) what the launch was: for the adaptive choice's next harvest, and for the fnv_last_* calls
   ix->sample_kernel = c.sample ? c.variant : -1;

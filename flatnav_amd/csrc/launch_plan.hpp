@@ -44,6 +44,9 @@ struct IndexOptions {
   int64_t half_rows = 1;  // searches read the half-width mirror of a float32 table while one is live (half_rows.hpp)
   int64_t overflow_list = -1;  // -1: automatic (a list in HBM only when the bitmap is larger than 512 KB)
   int64_t scan_segment_rows = 0;  // exhaustive search: candidate rows per block's segment (0: automatic)
+  // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
+  // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
+  int64_t filter_scan_max = 0, filter_scan_on_overflow = 0;
 };
 
 // What the planner reads of an index (fnv_index_s inherits it): the options, the table geometry, the device's size.

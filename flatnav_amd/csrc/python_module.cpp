@@ -341,6 +341,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
   void setDevices(const std::vector<int>& ordinals) { _index->setDevices(ordinals); }
   std::vector<int> devices() { return _index->devices(); }
   void syncDevice() { _index->syncDevice(); }
+  void setFilterRouting(int64_t scan_max_allowed, bool scan_on_overflow) { _index->setFilterRouting(scan_max_allowed, scan_on_overflow); }
   uintptr_t deviceHandle() { return reinterpret_cast<uintptr_t>(_index->deviceHandle()); }
   uint64_t currentNumNodes() { return _index->currentNumNodes(); }
   // zero-copy view of the AoS node store (for tests: graph-equality checks against the oracle)
@@ -406,6 +407,10 @@ void bindIndex(py::module_& m, const char* name) {
            "FLATNAV_DEVICES environment variable -- 'all' = every visible GPU --, else the primary GPU only).")
       .def_property_readonly("devices", &T::devices)
       .def("sync_device", &T::syncDevice, "Upload pending changes to HBM now instead of at the next search.")
+      .def("set_filter_routing", &T::setFilterRouting, py::arg("scan_max_allowed") = 0, py::arg("scan_on_overflow") = false,
+           "Filter routing of search_filtered / search_filtered_grouped: a query whose filter allows at most scan_max_allowed "
+           "nodes (0 = off), and with scan_on_overflow one whose search runs out of candidate room (instead of the call "
+           "raising), is answered by the exhaustive scan -- that row is search_exhaustive's.")
       .def("device_handle", &T::deviceHandle, "fnv_index_t of the device mirror as an integer.")
       .def("_raw_blob", &T::rawBlob)
       .def_property_readonly("_node_size_bytes", &T::nodeSizeBytes)

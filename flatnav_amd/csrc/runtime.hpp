@@ -264,7 +264,8 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
     DeviceBuf spill;   // uint64 [nslots][spill_entries]: what the candidates heap does not keep in LDS
     DeviceBuf tielog;  // uint64, merged-beam kernel: [nslots][log_entries] hand-over log (round 5)
     DeviceBuf scan;    // uint64, exhaustive search: [nq][segments][K] partial lists (scan.hpp)
-    DeviceBuf group;   // uint32, grouped exhaustive search: the grouping arrays (GroupArrays), O(nq + n_filters)
+    DeviceBuf group;   // uint32, grouped exhaustive search: the grouping arrays (GroupArrays), O(nq + n_filters); routed filtered
+                       // graph searches: the same for their scan stage, and the nq route words
     DeviceBuf rows;    // uint32, grouped searches: [n_filters + 2][capacity / 32] node bitmaps (node_filter_table_kernel) -- here,
                        // not in d_nodebits: the caller's n_filters sizes them, so lane admission and ws_bytes must see them
     size_t bytes() const { return bitmap.bytes + ovf.bytes + spill.bytes + tielog.bytes + scan.bytes + group.bytes + rows.bytes; }
@@ -346,6 +347,7 @@ bool half_rows_possible(const fnv_index_s* ix);
 int check_status(int32_t st, const char* advice = "raise the spill_entries option");
 int check_device_status(fnv_index_s* ix, const char* advice = "raise the spill_entries option");
 size_t filter_rows_bytes(const fnv_index_s* ix, const SearchFilter& f);
+size_t routed_workspace_bytes(fnv_index_s* ix, const SearchFilter& f, uint64_t nq, int K);
 int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
                        const SearchOutputs& out, void* hip_stream, const SearchOptions& opt = SearchOptions());
 int check_filter_args(const void* allowed_bits, uint64_t n_bits);

@@ -15,6 +15,8 @@
 //      (distance, label), padding, counters.
 // With one filter per query (fnv_search_batch_exhaustive_grouped) step 2 is exhaustive_scan_grouped_kernel: the same staging
 // and flushing around a walk of the tile's filter row; its batches are scored by scan_score_batch, a copy of step 2's loop.
+// A routed filtered graph search (scan_select.hpp, "filter routing") runs that grouped form as its second stage, on the queries
+// whose route word is set: route_queries_kernel, group_rows_routed_kernel and exhaustive_merge_routed_kernel below.
 #pragma once
 #include "distance.hpp"
 #include "heaps.hpp"
@@ -401,6 +403,15 @@ static __global__ __launch_bounds__(WAVE) void exhaustive_merge_grouped_kernel(c
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   scan_merge_query(gp.s, smem, [&] { return (uint64_t)gp.row_count[gp.query_row[blockIdx.x]]; });
 }
+// ... of a routed filtered graph search (scan_select.hpp, "filter routing"): one block per query of the call; only a query whose
+// route word is set has partial lists, and its n_hops = 0 tells its row from a graph search's.
+static __global__ __launch_bounds__(WAVE) void exhaustive_merge_routed_kernel(const GroupedScanParams gp, const uint32_t* route,
+                                                                              uint64_t* out_nhops) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (route[blockIdx.x] == ROUTE_GRAPH) return;  // (uniform over the block)
+  scan_merge_query(gp.s, smem, [&] { return (uint64_t)gp.row_count[gp.query_row[blockIdx.x]]; });
+  if (threadIdx.x == 0 && out_nhops) out_nhops[blockIdx.x] = 0ull;
+}
 
 // Grouping of a grouped launch's queries by filter row, in four small steps (rows = n_filters + 2; every array uint32):
 //   group_rows_kernel     query_row[q] = filter_row(query_filter[q]), counts[row]++          (counts zero at launch)
@@ -408,6 +419,8 @@ static __global__ __launch_bounds__(WAVE) void exhaustive_merge_grouped_kernel(c
 //   group_scatter_kernel  perm: the query indices, contiguous per row, in whatever order the atomics leave inside a row
 //                         (results go out at the original query index)                          (cursor zero at launch)
 //   group_tiles_kernel    the `bound` tile descriptors (scan_select.hpp, group_tile_at)
+// A routed filtered graph search groups the queries its scan stage answers and no others: group_rows_routed_kernel takes the
+// first step's place (query_row[q] = GROUP_NO_ROW for the rest, which group_scatter_kernel passes over), the others run as they are.
 static __global__ __launch_bounds__(256) void group_rows_kernel(const int32_t* query_filter, uint32_t nq, uint32_t n_filters,
                                                                 uint32_t* query_row, uint32_t* counts) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -415,6 +428,23 @@ static __global__ __launch_bounds__(256) void group_rows_kernel(const int32_t* q
   const uint32_t r = filter_row(query_filter[q], n_filters);
   query_row[q] = r;
   atomicAdd(counts + r, 1u);
+}
+static __global__ __launch_bounds__(256) void group_rows_routed_kernel(const int32_t* query_filter, const uint32_t* route, uint32_t nq,
+                                                                       uint32_t n_filters, uint32_t* query_row, uint32_t* counts) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const uint32_t r = routed_group_row(query_filter, q, n_filters, route);
+  query_row[q] = r;
+  if (r != GROUP_NO_ROW) atomicAdd(counts + r, 1u);
+}
+// The route words of a routed launch before its search kernel runs (row_count: node_filter_table_kernel's popcounts), and behind
+// them, at [nq], whether the search kernel hands a query whose candidates heap overflows to the scan.
+static __global__ __launch_bounds__(256) void route_queries_kernel(const int32_t* query_filter, uint32_t nq, uint32_t n_filters,
+                                                                   const uint32_t* row_count, uint64_t scan_max, uint32_t on_overflow,
+                                                                   uint32_t* route) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < nq) route[q] = route_at_launch(query_filter, q, n_filters, row_count, scan_max);
+  else if (q == nq) route[nq] = on_overflow;
 }
 static __global__ __launch_bounds__(256) void group_prefix_kernel(const uint32_t* counts, uint32_t rows, uint32_t tile,
                                                                   uint32_t* slot_start, uint32_t* tile_start) {
@@ -452,6 +482,7 @@ static __global__ __launch_bounds__(256) void group_scatter_kernel(const uint32_
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;
   const uint32_t r = query_row[q];
+  if (r == GROUP_NO_ROW) return;  // (routed launches: not a query of the scan stage)
   perm[slot_start[r] + atomicAdd(cursor + r, 1u)] = q;
 }
 static __global__ __launch_bounds__(256) void group_tiles_kernel(const uint32_t* slot_start, const uint32_t* tile_start, uint32_t rows,

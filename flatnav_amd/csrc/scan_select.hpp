@@ -111,6 +111,32 @@ FNV_SCAN_HD inline uint32_t filter_row(int32_t query_filter, uint32_t n_filters)
   return (uint32_t)query_filter < n_filters ? (uint32_t)query_filter : n_filters + 1u;
 }
 
+// ---- filter routing ("filter_scan_max" / "filter_scan_on_overflow"): graph search or scan, per query, inside one call --------
+// A filtered graph search keeps one ROUTE WORD per query.  Before the search kernel runs, a query whose filter row allows at
+// most `scan_max` live nodes (the row's popcount: a -1 row counts every live node, the empty row 0) is handed to the scan;
+// scan_max == 0 turns the rule off, whatever the count.  The search kernel skips such a query, and -- when overflow routing is
+// on -- marks a query whose candidates heap outgrew its room instead of failing the launch.  The scan stage that follows
+// answers exactly the queries whose word is not ROUTE_GRAPH.
+enum : uint32_t { ROUTE_GRAPH = 0u, ROUTE_SCAN = 1u, ROUTE_OVERFLOW = 2u };
+FNV_SCAN_HD inline uint32_t route_by_count(uint32_t allowed_nodes, uint64_t scan_max) {
+  return scan_max != 0u && (uint64_t)allowed_nodes <= scan_max ? ROUTE_SCAN : ROUTE_GRAPH;
+}
+// The filter row of query q in a routed launch: a null query_filter is the single-filter call -- a table of one, row 0 for all.
+FNV_SCAN_HD inline uint32_t routed_filter_row(const int32_t* query_filter, uint32_t q, uint32_t n_filters) {
+  return filter_row(query_filter ? query_filter[q] : 0, n_filters);
+}
+// ... and its route word before the search kernel runs, from the rows' popcounts.
+FNV_SCAN_HD inline uint32_t route_at_launch(const int32_t* query_filter, uint32_t q, uint32_t n_filters, const uint32_t* row_count,
+                                            uint64_t scan_max) {
+  return route_by_count(row_count[routed_filter_row(query_filter, q, n_filters)], scan_max);
+}
+// The scan stage groups the routed queries only: what query q puts into query_row (GROUP_NO_ROW: it takes no part, neither in
+// the rows' counts nor in the permutation; a real row is at most 2^31).
+constexpr uint32_t GROUP_NO_ROW = 0xFFFFFFFFu;
+FNV_SCAN_HD inline uint32_t routed_group_row(const int32_t* query_filter, uint32_t q, uint32_t n_filters, const uint32_t* route) {
+  return route[q] != ROUTE_GRAPH ? routed_filter_row(query_filter, q, n_filters) : GROUP_NO_ROW;
+}
+
 // The grouped scan's tiles.  Queries are permuted so that every filter row's queries are contiguous, and a tile holds at most
 // `tile` queries of ONE row: a block then walks one bitmap for all its queries.  How many tiles that takes depends on the data,
 //   sum_g ceil(c_g / tile)  <=  ceil(nq / tile) + min(rows, nq)   and never more than nq,

@@ -97,6 +97,10 @@ struct SearchParams {
   const int32_t* query_filter;  // [nq]
   uint32_t filter_words;
   uint32_t n_filters;
+  // Filter routing (beam_search_filtered_kernel only; scan_select.hpp, "filter routing"): [nq] route words and, at [nq], whether a
+  // candidates heap that overflows hands its query to the scan.  A query whose word is not ROUTE_GRAPH at launch is skipped; null =
+  // no routing.  (Cold, and behind every other field again.)
+  uint32_t* query_route;
 };
 
 // The fields of the visited-table geometry that the per-hop probe needs (kept in scalar registers).

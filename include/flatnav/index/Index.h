@@ -198,6 +198,8 @@ class Index {
   mutable bool _device_stale = true;       // the mirror misses host-side changes (new nodes and / or dirty link rows)
   mutable bool _device_rebuild = true;     // ... and they are not tracked: the whole store must be shipped again
   mutable size_t _device_capacity = 0;     // rows allocated on the device
+  int64_t _filter_scan_max = 0;            // setFilterRouting: re-applied whenever the mirror is created anew
+  bool _filter_scan_on_overflow = false;
   mutable size_t _device_synced_nodes = 0; // nodes [0, this) have their records on the device
   mutable detail::DirtyRows _dirty_rows;   // link rows of synced nodes that changed since
   int _device_ordinal = 0;
@@ -433,10 +435,17 @@ class Index {
         detail::throwOnDeviceError(fnv_index_set_live_nodes(_device_index, _cur_num_nodes));
       }
       _dirty_rows.drain(0);
+      applyFilterRouting();  // (a new handle starts with the library's defaults)
     }
     _device_synced_nodes = _cur_num_nodes;
     _device_stale = _device_rebuild = false;
     _replicas_stale = true;
+  }
+
+  void applyFilterRouting() const {
+    if (!_device_index || (_filter_scan_max == 0 && !_filter_scan_on_overflow)) return;
+    detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_max", _filter_scan_max));
+    detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_on_overflow", _filter_scan_on_overflow ? 1 : 0));
   }
 
   void dropReplicas() const {
@@ -553,6 +562,21 @@ class Index {
   void syncDevice() {
     std::lock_guard<std::mutex> g(_device_guard);
     ensureDevice();
+  }
+  // Filter routing (flatnav_hip.h, options "filter_scan_max" / "filter_scan_on_overflow"): in searchBatchFiltered and
+  // searchBatchFilteredGrouped a query whose filter allows at most scan_max_allowed live nodes (0: off) -- and, with
+  // scan_on_overflow, one whose candidates heap outgrows its room, instead of the call failing -- is answered by the exhaustive
+  // scan: that row is searchBatchExhaustive's for the same query and filter.  Applies to the device mirror now if there is one,
+  // and to every mirror made later.
+  void setFilterRouting(int64_t scan_max_allowed, bool scan_on_overflow) {
+    if (scan_max_allowed < 0) throw std::invalid_argument("setFilterRouting: scan_max_allowed must not be negative");
+    std::lock_guard<std::mutex> g(_device_guard);
+    _filter_scan_max = scan_max_allowed;
+    _filter_scan_on_overflow = scan_on_overflow;
+    if (_device_index) {
+      detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_max", _filter_scan_max));
+      detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_on_overflow", _filter_scan_on_overflow ? 1 : 0));
+    }
   }
   // The C-ABI handle of the device mirror (valid until the next mutation); for callers that drive
   // fnv_search_batch_device on their own buffers / streams.

@@ -251,6 +251,12 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *   "scan_segment_rows"  exhaustive search (fnv_search_batch_exhaustive): candidate rows that one block's row segment covers;
  *                     0 (default) = automatic (enough segments to fill the device, at most 64); tests force many segments and
  *                     a real merge on a small index with it (at most 1024 segments).  Same bytes.
+ *   "filter_scan_max"  filter routing (see "Filter routing" below; default 0 = off): in fnv_search_batch_filtered[_grouped][_device] a
+ *                     query whose filter allows at most this many live nodes is answered by the exhaustive scan instead of
+ *                     the graph search.  Keeps what fnv_tune / the adaptive choice measured, as the next one does.
+ *   "filter_scan_on_overflow"  filter routing (default 0 = off; any other value = on): a query of those calls whose candidates heap
+ *                     outgrows "cand_slots" + "spill_entries" is answered by the exhaustive scan, and the call does not report
+ *                     FNV_ERR_CAPACITY on its account.
  *   "half_rows"       1 (default): searches of a float32 index read its half-width mirror while one is live and covers every
  *                     live row (see fnv_index_half_rows); 0 = they read the float32 table.  Changing it discards what fnv_tune /
  *                     the adaptive choice measured (another kernel).  Same bytes.
@@ -313,7 +319,8 @@ int fnv_search_batch_device(fnv_index_t index, const void* d_queries, uint64_t n
  * without a filter.  With every label allowed the answers are exactly fnv_search_batch's: ids, distance bits, out_count,
  * out_ndist and out_nhops.  Fewer than K results is a normal outcome: the row is padded with (+inf, -1) and out_count[q]
  * says how many are real -- not an error.  A search that needs more candidate room than "spill_entries" (selective filters
- * keep the candidates heap busier) reports FNV_ERR_CAPACITY, as fnv_search_batch does.  Filtered launches always run the
+ * keep the candidates heap busier) reports FNV_ERR_CAPACITY, as fnv_search_batch does (unless "filter_scan_on_overflow" hands
+ * such a query to the exhaustive scan: "Filter routing" below).  Filtered launches always run the
  * two-heap kernel (never the merged-beam kernel), take no samples for the adaptive kernel choice and leave what it has
  * measured as it was.  The label bitmap is translated into a node bitmap in the workspace of whichever handle or lane runs
  * the call (labels as they are at launch time: after a reorder, for device-built indexes), so concurrent filtered calls
@@ -396,7 +403,33 @@ int fnv_search_batch_exhaustive_device(fnv_index_t index, const void* d_queries,
  *   same way; they always take the staged-copy path (the filter table and query_filter go through the handle's staging, never
  *   zero-copy).  The _device entry points (every buffer in the index's device memory) enqueue on `hip_stream` without
  *   synchronising; one launch in flight per handle.
- * Not covered: fnv_search_batch_multi / replicas, routing between the graph and the scan form, a K or ef_search per query. */
+ * Not covered: fnv_search_batch_multi / replicas, a K or ef_search per query.
+ *
+ * Filter routing: the graph form or the scan form, decided PER QUERY on the device inside one call of fnv_search_batch_filtered,
+ * fnv_search_batch_filtered_grouped or their _device forms -- two options, both off by default, no further entry point.
+ *   "filter_scan_max" = T > 0: a query whose filter row allows at most T live nodes -- the popcount of its node bitmap over
+ *     [0, n_live); a -1 row counts n_live, the empty row 0, and so does any out-of-range query_filter value on a _device entry
+ *     point -- is answered by the scan.  "filter_scan_on_overflow" != 0: so is a query whose candidates heap outgrows its room in
+ *     the search kernel; no status is set for it, so a call with this option on never returns FNV_ERR_CAPACITY (unless routing
+ *     does not apply, below).
+ *   A scanned row q holds exactly the bytes fnv_search_batch_exhaustive_grouped (the single-filter call:
+ *     fnv_search_batch_exhaustive with use_filter = 1) writes for that query and that filter: labels, distance bits, (+inf, -1)
+ *     padding, the (distance, node id) order with NaN last, out_count, out_ndist = candidates -- and out_nhops[q] = 0, which is
+ *     how a caller tells it from a graph row (a graph search of a non-empty index expands its entry node: at least one hop).
+ *     A graph row q holds exactly the bytes the call writes with both options off.
+ *   Routing is NOT applied where the scan cannot take the call -- K > 1024, or rows too long for the scan's LDS (what makes
+ *     fnv_search_batch_exhaustive return FNV_ERR_INVALID): the whole call then runs the graph form as with the options off,
+ *     FNV_ERR_CAPACITY included.  Turning an option on never makes a valid call invalid.  fnv_search_batch (no filter) and
+ *     fnv_search_batch_multi never route; there is no automatic threshold (profiles/filter_routing.md measures the crossover).
+ *   Launches: the filter rows and their popcounts, a small kernel that sets the route words, the filtered two-heap kernel -- it
+ *     skips a query that is already routed at the cost of one dispenser step --, then on the SAME stream the scan stage: the
+ *     routed queries alone grouped by filter row into tiles, the grouped scan kernel and a merge that leaves the other rows
+ *     alone.  The two stages do not overlap.  fnv_last_launch_geometry reports the search kernel's launch, fnv_last_kernel_ms
+ *     both stages.  Memory: the graph form's workspace, (n_filters + 2) node bitmaps (3 for the single-filter call), the
+ *     grouping arrays, nq + 1 route words and the scan's partial lists for nq queries (within 256 MB whenever there is more
+ *     than one segment) -- all in the workspace of the handle or lane that runs the call and counted towards its lane budget.
+ *     Routed host calls always take the staged-copy path.
+ *   With both options 0 every launch, every byte, the workspace and fnv_last_launch_geometry are as without this section. */
 int fnv_search_batch_filtered_grouped(fnv_index_t index, const void* queries, uint64_t nq, int K, int ef_search,
                                       int num_initializations, const void* filters, uint64_t n_filters,
                                       uint64_t filter_stride_bytes, uint64_t n_bits, const int32_t* query_filter, float* out_dist,

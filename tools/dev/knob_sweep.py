@@ -9,6 +9,9 @@ Builds the configuration's index with bench.py's own generator and the device bu
 option set: fnv_tune once, `--steps` timed launches over rotating query batches (HIP events on the launch stream), the
 sets alternating `--rounds` times.  Prints one line per (ef, set): kernel ms (each round), queries/s of the best round,
 algorithmic TB/s, launch geometry, chosen variant.  Results are never compared with the oracle here (parity tests do that).
+`--filter F` times FILTERED launches instead (fnv_search_batch_filtered_device; a random F of the labels allowed), `--tenants T`
+with it grouped ones (fnv_search_batch_filtered_grouped_device: T disjoint random sets of F each, the queries dealt evenly);
+use --no-tune with them (filtered launches never read the tuner).
 """
 import argparse
 import ctypes
@@ -39,6 +42,8 @@ ap.add_argument("--dtype", default="float32")
 ap.add_argument("--recall", action="store_true")
 ap.add_argument("--no-tune", action="store_true")
 ap.add_argument("--json", default="")
+ap.add_argument("--filter", type=float, default=0.0, help="time filtered launches: this fraction of the labels allowed")
+ap.add_argument("--tenants", type=int, default=0, help="with --filter: grouped launches over this many disjoint sets of that fraction")
 ap.add_argument("--libs", default="", help="name=path,... further builds of libflatnav_hip.so to A/B against the in-tree one "
                                            "(each gets its own copy of the index: fnv_index_alloc + device-to-device copy)")
 args = ap.parse_args()
@@ -137,13 +142,36 @@ DEFAULTS = dict(visited_factor=27, visited_slots=0, visited_floor=2048, occupanc
                 wide_table_max=-1, query_regs=1, tie_replay=1, tie_log_entries=0, half_rows=1)
 
 
+FILTER = None
+if args.filter > 0:  # labels are row numbers
+    frng = np.random.default_rng(7)
+    T = max(1, args.tenants)
+    per = max(1, int(round(args.filter * N)))
+    assert T * per <= N, "--tenants x --filter exceeds the labels"
+    perm = frng.permutation(N)
+    ftable, f_bits = hip.pack_filters([np.sort(perm[t * per:(t + 1) * per]) for t in range(T)])
+    FILTER = dict(table=torch.from_numpy(ftable).to(dev_t), n_bits=f_bits, stride=ftable.shape[1], n=T,
+                  qf=torch.from_numpy(frng.permutation(np.arange(NQ) % T).astype(np.int32)).to(dev_t))
+
+
+def launch(dev, q_ptr, ef):
+    if FILTER is None:
+        dev.search_device(q_ptr, NQ, K, ef, 100, od.data_ptr(), ol.data_ptr(), 0, nd.data_ptr(), nh.data_ptr(), stream=stream.cuda_stream)
+    elif args.tenants:
+        dev.search_device_filtered_grouped(q_ptr, NQ, K, ef, 100, FILTER["table"].data_ptr(), FILTER["n"], FILTER["stride"], FILTER["n_bits"],
+                                           FILTER["qf"].data_ptr(), od.data_ptr(), ol.data_ptr(), 0, nd.data_ptr(), nh.data_ptr(),
+                                           stream=stream.cuda_stream)
+    else:
+        dev.search_device_filtered(q_ptr, NQ, K, ef, 100, FILTER["table"].data_ptr(), FILTER["n_bits"], od.data_ptr(), ol.data_ptr(), 0,
+                                   nd.data_ptr(), nh.data_ptr(), stream=stream.cuda_stream)
+
+
 def timed(dev, ef, steps):
     evs = []
     for i in range(steps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(stream)
-        dev.search_device(dq[i % NB].data_ptr(), NQ, K, ef, 100, od.data_ptr(), ol.data_ptr(), 0, nd.data_ptr(), nh.data_ptr(),
-                          stream=stream.cuda_stream)
+        launch(dev, dq[i % NB].data_ptr(), ef)
         b.record(stream)
         evs.append((a, b))
     torch.cuda.synchronize()
