@@ -93,7 +93,7 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
   w.beam_dist = beams.dist;
   w.beam_ids = beams.labels;
   w.beam_count = beams.count;
-  w.dispenser = ix->d_dispenser;
+  w.dispenser = ix->d_dispenser + fnv_index_s::kBuilderWord;  // (a word of the builder's own: no search launch's block)
   w.first_node = (uint32_t)first_node;
   w.count = (uint32_t)count;
   w.W = (uint32_t)W;
@@ -131,7 +131,7 @@ int fnv_index_insert_batch(fnv_index_t ix, uint64_t first_node, uint64_t count, 
     // select: one unit of work per new node; connect: per 64 positions of the sorted request list
     const uint64_t units = phase == 0 ? count : (nreq + WAVE - 1) / WAVE;
     const uint32_t nslots = (uint32_t)std::min<uint64_t>(units, (uint64_t)bpc * (uint64_t)ix->num_cus);
-    HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, sizeof(uint32_t), ix->stream));
+    HIP_TRY(hipMemsetAsync(w.dispenser, 0, sizeof(uint32_t), ix->stream));
     hipLaunchKernelGGL(kern, dim3(nslots), dim3(WAVE), lds_bytes, ix->stream, w);
     HIP_TRY(hipGetLastError());
     if (phase == 0) {  // group the batch's back-link requests by target (stable: insertion order within a target)

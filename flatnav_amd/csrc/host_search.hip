@@ -71,6 +71,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   SearchFilter dev_filter{nullptr, 0};
   SearchOptions opt;
   opt.exhaustive = exhaustive;
+  opt.timed = true;  // (a host-buffer call waits for its launch anyway: fnv_last_kernel_ms works after it as ever)
   const bool grouped = host_filter && host_filter->grouped;
   // (filter routing: a routed call's scan stage writes whole rows a second time -- it takes the staged copies, as grouped calls do)
   const bool staged_only = grouped || (host_filter && !exhaustive && (ix->filter_scan_max > 0 || ix->filter_scan_on_overflow != 0));
@@ -191,7 +192,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
     uint8_t* slab = pinned ? h + ooff : ix->h_res.as<uint8_t>();
     int32_t* status = (int32_t*)(pinned ? h + soff : slab + ((obytes + 63) & ~(size_t)63));
     HIP_TRY(hipMemcpyAsync(slab, ix->d_out.ptr, obytes, hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipMemcpyAsync(status, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipMemcpyAsync(status, ix->last_block + 1, sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));  // (that launch's block)
     ix->pin.arm(lay_out_slab(slab, nq, K), status, user, nq, K);
     return FNV_OK;
   }

@@ -145,8 +145,9 @@ int index_common_init(fnv_index_s* ix) {
   HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreate(&ix->ev0));
   HIP_TRY(hipEventCreate(&ix->ev1));
-  HIP_TRY(hipMalloc(&ix->d_dispenser, 16 * sizeof(uint32_t)));
-  HIP_TRY(hipMemset(ix->d_dispenser, 0, 16 * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc(&ix->d_dispenser, fnv_index_s::kDispenserWords * sizeof(uint32_t)));
+  HIP_TRY(hipMemset(ix->d_dispenser, 0, fnv_index_s::kDispenserWords * sizeof(uint32_t)));
+  ix->last_block = ix->d_dispenser;
 #ifdef FNV_PHASE_TIMING
   HIP_TRY(hipMalloc(&ix->d_phase, NPHASE * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(ix->d_phase, 0, NPHASE * sizeof(unsigned long long)));
@@ -609,12 +610,13 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   else if (n == "filter_scan_max") ix->filter_scan_max = value;  // (read per filtered launch, like the next)
   else if (n == "filter_scan_on_overflow") ix->filter_scan_on_overflow = value != 0;
   else if (n == "half_rows") ix->half_rows = value;  // (read per launch; the mirror's launches are another kernel's: measurements go)
+  else if (n == "launch_timing") ix->time_launches = value != 0;  // (read per launch)
   else return fail(FNV_ERR_INVALID, "unknown option: " + n);
   // What fnv_tune measured (kernel variant, LDS layout) stays valid across options that change neither the launch plan
   // nor the kernel choice: Index.h::addBatchDevice flips output_node_ids around every device build, and a tune costs
   // dozens of launches.  (output_node_ids is read per launch; shadow_exact per launch; tune_layout by fnv_tune itself.)
   const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows" ||
-                            n == "filter_scan_max" || n == "filter_scan_on_overflow";  // (filtered launches never touch the tuner)
+                            n == "filter_scan_max" || n == "filter_scan_on_overflow" || n == "launch_timing";  // (filtered launches never touch the tuner)
   if (!keeps_tuning) {
     ix->options_version++;
     ix->tuner.clear();

@@ -235,8 +235,11 @@ __device__ __forceinline__ void clear_spill_bitmap(uint32_t* bitmap, const uint3
 }
 
 // Next work item of this slot (-1: none left).  A slot's FIRST item is its block index: no round trip before the first query,
-// and a launch does not open with every slot's atomic on one word.  The launch's atomic dispenser (zero at launch) hands out the
-// items from gridDim.x on, so every item below nq is still taken exactly once, in ascending order per slot.
+// and a launch does not open with every slot's atomic on one word.  The launch's atomic dispenser (zero at launch: the launch
+// before it on the handle zeroed the block, clear_next_dispenser below, or the host did) hands out the items from gridDim.x on,
+// so every item below nq is still taken exactly once, in ascending order per slot.
+// (Later items stay dynamic: between the end of a slot's query and the start of its next one lie 0.84-0.97 us at the median and
+// 1.6 us at most, also where 670 slots ask within 10 us -- one uncontended round trip, no queue: profiles/launch_edges.md.)
 __device__ __forceinline__ int next_query(int lane, bool first) {
   ColdArgs c = cold_args();
   int qi = (int)blockIdx.x;
@@ -246,6 +249,13 @@ __device__ __forceinline__ int next_query(int lane, bool first) {
   }
   if ((uint32_t)qi >= c->nq) return -1;
   return qi;
+}
+
+// The first lanes of block 0 zero the handle's other dispenser block (search_types.h dispenser_next) with plain stores, before
+// the block's first query: nothing in this launch reads it, and the next launch on the handle finds it zero.
+__device__ __forceinline__ void clear_next_dispenser(int lane) {
+  uint32_t* const next = cold_args()->dispenser_next;
+  if (blockIdx.x == 0 && next != nullptr && lane < 16) next[lane] = 0u;
 }
 
 // Entry point of query qi and its distance: from the batch kernel K0 if it ran, else the in-kernel scan.
@@ -810,6 +820,7 @@ __global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) vo
   x.stage_ids = reinterpret_cast<uint32_t*>(smem + p.off_stage_ids);
   x.ovf_list = reinterpret_cast<uint32_t*>(smem + p.off_ovf);
 
+  clear_next_dispenser(lane);
   for (bool first = true;; first = false) {
     const int qi = next_query(lane, first);
     if (qi < 0) break;
@@ -852,6 +863,7 @@ __global__ __launch_bounds__(WAVE, waves_per_simd<G>(FNV_MIN_WAVES_PER_SIMD)) vo
   x.stage_ids = reinterpret_cast<uint32_t*>(smem + p.off_stage_ids);
   x.ovf_list = reinterpret_cast<uint32_t*>(smem + p.off_ovf);
 
+  clear_next_dispenser(lane);
   for (bool first = true;; first = false) {
     const int qi = next_query(lane, first);
     if (qi < 0) break;

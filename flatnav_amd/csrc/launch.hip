@@ -177,8 +177,19 @@ int check_status(int32_t st, const char* advice) {
 }
 int check_device_status(fnv_index_s* ix, const char* advice) {  // (the stream has been waited for)
   int32_t st = 0;
-  HIP_TRY(hipMemcpy(&st, ix->d_dispenser + 1, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&st, ix->last_block + 1, sizeof(int32_t), hipMemcpyDeviceToHost));  // (the most recent launch's block)
   return check_status(st, advice);
+}
+// The dispenser block of the launch that is about to be enqueued on `stream`, zero when its kernel starts (THE RULE:
+// runtime.hpp, d_dispenser): the other block than the most recent launch's; the host's memset unless that launch's kernel
+// zeroes exactly this block ahead of us on the same stream.  The caller holds ix->mu.
+static int next_dispenser_block(fnv_index_s* ix, hipStream_t stream, uint32_t** block, uint32_t** other) {
+  const int mine = ix->last_block == ix->d_dispenser ? 1 : 0;
+  *block = ix->d_dispenser + mine * fnv_index_s::kDispenserStride;
+  *other = ix->d_dispenser + (1 - mine) * fnv_index_s::kDispenserStride;
+  const bool zeroed = ix->launched && ix->zeroed_block == mine && ix->last_stream == stream;
+  if (!zeroed) HIP_TRY(hipMemsetAsync(*block, 0, 16 * sizeof(uint32_t), stream));
+  return FNV_OK;
 }
 
 // ---- one search launch, step by step (search_device_impl runs them in this order under the handle's mutex) -----------
@@ -362,9 +373,14 @@ static bool batch_to_launch(const void* d_queries, uint64_t nq, const SearchOutp
   return *rc == FNV_OK;
 }
 // What the launch was, for the fnv_last_* calls: grid, block, LDS bytes, then five values of the kernel's own (geom[6]: its mode).
-static void record_launch(fnv_index_s* ix, hipStream_t stream, uint64_t grid, uint64_t block, uint64_t lds, uint64_t g3, uint64_t g4,
-                          uint64_t g5, uint64_t mode, uint64_t g7) {
+// `dispenser`: the block the launch owns; `zeroed`: the block its kernel zeroes for the next launch (-1: none); `timed`: ev0 / ev1
+// bracket it.
+static void record_launch(fnv_index_s* ix, hipStream_t stream, uint32_t* dispenser, int zeroed, bool timed, uint64_t grid, uint64_t block,
+                          uint64_t lds, uint64_t g3, uint64_t g4, uint64_t g5, uint64_t mode, uint64_t g7) {
   ix->last_stream = stream;
+  ix->last_block = dispenser;
+  ix->zeroed_block = zeroed;
+  ix->last_timed = timed;
   ix->launched = true;
   if (!ix->is_lane) ix->last_served = nullptr;  // the handle's own launch is its most recent one
   const uint64_t geom[8] = {grid, block, lds, g3, g4, g5, mode, g7};
@@ -555,7 +571,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
 
   ScanParams p = scan_params(ix, g, d_queries, nq, K, out, opt, shape, live);
 
-  HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));  // (the status word: this path never sets it)
+  // (the status word: this path never sets it; the scan's kernels zero no block, so the next search launch memsets its own)
+  uint32_t* const block = ix->last_block;
+  HIP_TRY(hipMemsetAsync(block, 0, 16 * sizeof(uint32_t), stream));
   GroupedScanParams gp;
   memset(&gp, 0, sizeof(gp));
   if (grouped) {  // the filter table -> this handle's node bitmaps and their popcounts; the queries grouped by row into tiles
@@ -591,8 +609,8 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ix->ev1, stream));
   // (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id queue, row segments)
-  record_launch(ix, stream, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped ? shape.tile : 0, grouped ? SCAN_QUEUE_IDS : 0,
-                grouped ? shape.segments : 0, 3, 0);
+  record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped ? shape.tile : 0,
+                grouped ? SCAN_QUEUE_IDS : 0, grouped ? shape.segments : 0, 3, 0);
   return FNV_OK;
 }
 
@@ -679,14 +697,19 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   p.cand_spill = ix->ws.spill.as<unsigned long long>();
   p.tie_log = ix->ws.tielog.as<unsigned long long>();
   if (!sorted) p.log_entries = 0u;
-  p.dispenser = ix->d_dispenser;
-  p.status = (int32_t*)(ix->d_dispenser + 1);
+  uint32_t *block = nullptr, *other = nullptr;
+  rc = next_dispenser_block(ix, stream, &block, &other);
+  if (rc) return rc;
+  p.dispenser = block;
+  p.dispenser_next = other;
+  p.status = (int32_t*)(block + 1);
   p.host_status = opt.host_status;
-  p.redo_count = ix->d_dispenser + 3;  // [3] queries searched exactly after a tie, [4..7] by reason
+  p.redo_count = block + 3;  // [3] queries searched exactly after a tie, [4..7] by reason
   p.phase_cycles = ix->d_phase;
   p.tail_exact = shape.tail_exact;
+  // ev0 / ev1 only where somebody will read them (runtime.hpp, time_launches)
+  const bool timed = c.sample || opt.timed || opt.force_variant >= 0 || ix->time_launches.load();
 
-  HIP_TRY(hipMemsetAsync(ix->d_dispenser, 0, 16 * sizeof(uint32_t), stream));
   uint32_t* const gw = routed ? ix->ws.group.as<uint32_t>() : nullptr;
   if (rows_of) {  // the filter table -> this handle's node bitmaps; every query reads its own row
     if (routed) HIP_TRY(hipMemsetAsync(gw + ga.counts, 0, (size_t)3 * table.rows() * 4, stream));  // counts | cursor | row_count
@@ -708,7 +731,7 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
     if (rc) return rc;
     p.node_bits = ix->d_nodebits.as<uint32_t>();
   }
-  HIP_TRY(hipEventRecord(ix->ev0, stream));
+  if (timed) HIP_TRY(hipEventRecord(ix->ev0, stream));
   if (ix->entry_kernel && !ix->tail_bytes) {  // (split rows: K0's LDS tiles hold one table's rows; the in-kernel scan serves them)
     // K0: one pass over the shared entry-scan nodes for the whole batch (LDS-staged), same stream
     rc = ix->d_entry.grow((size_t)nq * 8);
@@ -747,6 +770,10 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   HIP_TRY(raise_lds_limit((const void*)kern.fn, ix->device, lds_bytes));
   hipLaunchKernelGGL(kern.fn, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
   HIP_TRY(hipGetLastError());
+  // the blocks change hands HERE: whatever fails below, the next launch must not take this one's block for a zeroed one
+  ix->last_stream = stream;
+  ix->last_block = block;
+  ix->zeroed_block = (int)(other != ix->d_dispenser);
   if (routed) {  // the scan stage, on the same stream: the queries whose route word is set, grouped by filter row into tiles
     GroupedScanParams gp;
     memset(&gp, 0, sizeof(gp));
@@ -756,9 +783,9 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
     rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[sg.cfg][sg.full], gp, sshape, nq, stream, gw + ga.route, out.nhops);
     if (rc) return rc;
   }
-  HIP_TRY(hipEventRecord(ix->ev1, stream));
+  if (timed) HIP_TRY(hipEventRecord(ix->ev1, stream));
   // (f) what the launch was: for the adaptive choice's next harvest, and for the fnv_last_* calls
-  ix->sample_kernel = c.sample ? c.variant : -1;
+  ix->sample_kernel = c.sample ? c.variant : -1;  // (a sample is always timed)
   ix->sample_B = tuner_key(B, c.multi_round);
   ix->sample_nq = nq;
   ix->last_variant = sorted ? std::max(c.variant, 1) : 0;
@@ -766,8 +793,8 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   if (c.exploratory) ix->explored_launches++;
   ix->last_shadow = shadow;
   ix->last_half = kern.half_rows;
-  record_launch(ix, stream, nslots, WAVE, lds_bytes, (uint64_t)bpc, p.vis_slots, p.cand_slots, (uint64_t)(sorted ? plan.mode : MODE_HEAPS),
-                p.tail_exact);
+  record_launch(ix, stream, block, (int)(other != ix->d_dispenser), timed, nslots, WAVE, lds_bytes, (uint64_t)bpc, p.vis_slots, p.cand_slots,
+                (uint64_t)(sorted ? plan.mode : MODE_HEAPS), p.tail_exact);
   return FNV_OK;
 }
 

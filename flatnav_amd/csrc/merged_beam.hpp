@@ -121,6 +121,7 @@ __global__ __launch_bounds__(WAVE, CU == 1 ? 5 : R == MB_R ? 3 : waves_per_simd<
   const int lane_of_kernel = threadIdx.x;
   const float INF = std::numeric_limits<float>::infinity();
 
+  clear_next_dispenser(lane_of_kernel);
   for (bool first = true;; first = false) {
     // (opaque per query, like the tail's below: lane-derived constants of the prologue are computed per query, not kept
     // alive -- in scratch, in the four-chunk form -- from the kernel's entry on)

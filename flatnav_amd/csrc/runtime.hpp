@@ -146,6 +146,7 @@ static SearchOutputs lay_out_slab(void* base, uint64_t nq, int K, size_t* bytes 
 
 // What one search launch does differently from a plain one: a call names only what it changes.
 struct SearchOptions {
+  bool timed = false;               // bracket the launch with the handle's events (fnv_tune, the host-buffer entry points)
   bool node_ids = false;            // write node ids whatever "output_node_ids" says (the device builder's beams)
   int force_variant = -1;           // >= 0: fnv_tune's launches (an argument, not index state: a concurrent caller's launch on
                                     // the same handle is never forced)
@@ -254,8 +255,27 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
   bool last_shadow = false;       // ... and whether every query had an exact shadow (small launches)
   // host-buffer searches: steady-clock time of launch / of completion (atomic: every lane's caller reports into the handle)
   std::atomic<uint64_t> t_enqueue_ns{0}, t_complete_ns{0};
-  uint32_t* d_dispenser = nullptr;  // [0] dispenser, [1] status, [3] queries a merged-beam launch handed to the exact search, [4..7] by
-                                    // reason, [8] of them resumed from their log, [9] hops taken from logs, [10] hops of those queries
+  // TWO dispenser blocks of 16 words, kDispenserStride words apart.  A block: [0] dispenser, [1] status, [3] queries a merged-beam
+  // launch handed to the exact search, [4..7] by reason, [8] of them resumed from their log, [9] hops taken from logs, [10] hops
+  // of those queries.  A search launch owns ONE block and zeroes the OTHER one from its kernel (kernels.hpp
+  // clear_next_dispenser); the next launch on the handle takes that other block, so that a call enqueues no memset of its own.
+  // THE RULE (next_dispenser_block, launch.hip): the kernel-side clear is ordered against the next launch only by stream order,
+  // so it counts only while `zeroed_block` names a block and the new launch is on `last_stream`; every other launch -- the
+  // first one, one on another stream, one after an exhaustive search (which memsets the block it reports its status in and
+  // resets zeroed_block) -- memsets the block it takes, as every launch once did.  The device builder's wiring kernels and
+  // gather_ceiling write words of their own behind the two blocks (kBuilderWord).  Each handle, view and hidden lane has its
+  // own allocation.  Whoever reads a launch's status word or counters reads `last_block`, the block of that launch.
+  static constexpr uint32_t kDispenserStride = 32;  // (128 bytes: the two blocks never share a cache line)
+  static constexpr uint32_t kBuilderWord = 64;      // the device builder's own dispenser word; [+1]: gather_ceiling's sink
+  static constexpr uint32_t kDispenserWords = 80;
+  uint32_t* d_dispenser = nullptr;
+  uint32_t* last_block = nullptr;  // the block of the most recent launch (record_launch); before any: d_dispenser
+  int zeroed_block = -1;           // 0 / 1: the block the most recent launch's kernel zeroes on last_stream; -1: none
+  // ev0 / ev1 bracket a launch only when somebody will read them: a sample of the adaptive choice, fnv_tune's launches, the
+  // host-buffer entry points (fnv_last_kernel_ms after fnv_search_batch works as ever), and -- device-buffer entry points --
+  // once "launch_timing" is set or fnv_last_kernel_ms has been called on the handle (which arms it for the launches after).
+  std::atomic<bool> time_launches{false};
+  bool last_timed = false;         // ev0 / ev1 bracket the most recent launch
   unsigned long long* d_phase = nullptr;  // profiling builds only
   // The launch workspace, per query slot: what search_device_impl grows, free_lane_workspace gives back and ws_bytes counts.
   struct Workspace {

@@ -101,6 +101,9 @@ struct SearchParams {
   // candidates heap that overflows hands its query to the scan.  A query whose word is not ROUTE_GRAPH at launch is skipped; null =
   // no routing.  (Cold, and behind every other field again.)
   uint32_t* query_route;
+  // The handle's OTHER dispenser block (runtime.hpp, fnv_index_s::d_dispenser): this launch zeroes its 16 words for the launch
+  // that follows it on the handle and touches it in no other way; null: nothing to zero.
+  uint32_t* dispenser_next;
 };
 
 // The fields of the visited-table geometry that the per-hop probe needs (kept in scalar registers).

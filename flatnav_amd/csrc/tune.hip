@@ -133,6 +133,7 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
   auto launch = [&](int variant, uint64_t rotate = 0) -> int {
     SearchOptions opt;
     opt.force_variant = variant;
+    opt.timed = true;  // (time_variant reads ev0 / ev1)
     return search_device_impl(ix, dq2 + (rotate % nq) * qrow_bytes, nq, K, ef_search, num_initializations, scratch, ix->stream, opt);
   };
   // what kind of launch is this?  (one probing launch of the merged-beam kernel tells: plan, round size)
@@ -321,7 +322,7 @@ int fnv_gather_ceiling(fnv_index_t ix, int waves_per_cu, double* gbps_out) {
   const uint32_t blocks = (uint32_t)(ix->num_cus * wpc);
   const double rows_per_iter = (double)blocks * (WAVE / G) * PU;  // rows one iteration of the whole grid reads
   const int iters = (int)std::max<double>(8.0, 120e9 / (rows_per_iter * (double)ix->row_bytes));  // ~120 GB ~ 20 ms
-  uint32_t* d_sink = ix->d_dispenser + 2;  // an unused word of the workspace
+  uint32_t* d_sink = ix->d_dispenser + fnv_index_s::kBuilderWord + 1;  // an unused word of the workspace
   hipLaunchKernelGGL(kGather[cfg], dim3(blocks), dim3(WAVE), 0, ix->stream, ix->d_vectors, n_rows, ix->row_bytes, iters / 8 + 1, d_sink);  // warm
   HIP_TRY(hipEventRecord(ix->ev0, ix->stream));
   hipLaunchKernelGGL(kGather[cfg], dim3(blocks), dim3(WAVE), 0, ix->stream, ix->d_vectors, n_rows, ix->row_bytes, iters, d_sink);
@@ -347,8 +348,14 @@ int fnv_last_launch_info(fnv_index_t ix, uint64_t info[4]) {
 
 int fnv_last_kernel_ms(fnv_index_t ix, float* ms) {
   if (!ix || !ms) return fail(FNV_ERR_INVALID, "null argument");
+  // ev0 / ev1 bracket a launch only where somebody reads them (runtime.hpp, time_launches): asking arms the handle's
+  // device-buffer launches from here on; the launch that was not timed has no duration to report
+  ix->time_launches = true;
   ix = last_launcher(ix);
   if (!ix->launched) return fail(FNV_ERR_RUNTIME, "no search has been launched on this index");
+  if (!ix->last_timed)
+    return fail(FNV_ERR_RUNTIME, "the most recent launch was not timed: fnv_search_batch_device records its events once \"launch_timing\" is set "
+                                 "or fnv_last_kernel_ms has been called (timing is armed for the launches that follow)");
   ON_DEVICE(ix->device);
   HIP_TRY(hipEventSynchronize(ix->ev1));
   HIP_TRY(hipEventElapsedTime(ms, ix->ev0, ix->ev1));
@@ -385,7 +392,7 @@ int fnv_debug_spec_stats(fnv_index_t ix, uint64_t out[2]) {
   ON_DEVICE(ix->device);
   HIP_TRY(hipStreamSynchronize(ix->last_stream));
   uint32_t w[2];
-  HIP_TRY(hipMemcpy(w, ix->d_dispenser + 11, sizeof(w), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w, ix->last_block + 11, sizeof(w), hipMemcpyDeviceToHost));
   out[0] = w[0];
   out[1] = w[1];
   return FNV_OK;
@@ -400,7 +407,7 @@ int fnv_last_replayed_queries(fnv_index_t ix, uint64_t out[5]) {
   ON_DEVICE(ix->device);
   HIP_TRY(hipStreamSynchronize(ix->last_stream));
   uint32_t w[5];
-  HIP_TRY(hipMemcpy(w, ix->d_dispenser + 3, sizeof(w), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w, ix->last_block + 3, sizeof(w), hipMemcpyDeviceToHost));  // (the most recent launch's block)
   for (int i = 0; i < 5; i++) out[i] = w[i];
   return FNV_OK;
 }
@@ -413,7 +420,7 @@ int fnv_last_handover_stats(fnv_index_t ix, uint64_t out[4]) {
   ON_DEVICE(ix->device);
   HIP_TRY(hipStreamSynchronize(ix->last_stream));
   uint32_t w[8];
-  HIP_TRY(hipMemcpy(w, ix->d_dispenser + 3, sizeof(w), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(w, ix->last_block + 3, sizeof(w), hipMemcpyDeviceToHost));
   out[0] = w[5];         // queries resumed from their hand-over log
   out[1] = w[6];         // hops taken from the logs
   out[2] = w[7];         // hops the merged-beam passes of those queries had made

@@ -260,6 +260,10 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *   "half_rows"       1 (default): searches of a float32 index read its half-width mirror while one is live and covers every
  *                     live row (see fnv_index_half_rows); 0 = they read the float32 table.  Changing it discards what fnv_tune /
  *                     the adaptive choice measured (another kernel).  Same bytes.
+ *   "launch_timing"   0 (default): the _device entry points bracket a launch with the handle's HIP events only where the
+ *                     library reads them itself (samples of the adaptive choice, fnv_tune); any other value: every launch, so that
+ *                     fnv_last_kernel_ms can report it.  The host-buffer entry points always do.  Keeps what fnv_tune measured.
+ *                     Same bytes.
  *   "tune_layout"     1 (default): fnv_tune also measures the LDS layout (see fnv_tune); 0 = kernel variants only
  *   "sorted_beam_min" smallest beam width the merged-beam kernel is used for (default 1)
  *   "sorted_cand_lds" where the exact re-run of the merged-beam kernel keeps its candidates heap: 2 (default) = in LDS
@@ -477,7 +481,11 @@ int fnv_search_batch_multi(fnv_index_t* indexes, int n_indexes, const void* quer
 int fnv_search_status(fnv_index_t index);
 
 /* Duration (ms, HIP events on the launch stream) of the search kernel of the most recent
- * fnv_search_batch[_device] call on this index; synchronises with that launch. */
+ * fnv_search_batch[_device] call on this index; synchronises with that launch.
+ * A launch is bracketed by events only where somebody reads them: always after the host-buffer entry points; after a _device
+ * entry point once "launch_timing" is set or this function has been called on the handle -- the call arms the launches that
+ * follow, and for a launch that was not timed it returns FNV_ERR_RUNTIME (an untimed steady-state call enqueues its kernel
+ * and nothing else). */
 int fnv_last_kernel_ms(fnv_index_t index, float* ms);
 
 /* The merged-beam kernel searches a query again with the exact (libstdc++-replay) two-heap code when equal
