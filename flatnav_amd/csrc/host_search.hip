@@ -46,14 +46,14 @@ size_t release_idle_lanes(fnv_index_s* ix, const fnv_index_s* keep) {
   return release_idle_lanes_locked(ix, keep);
 }
 
-// HBM a launch of `nq` queries needs as per-slot workspace on a handle of this index (what grow_workspace grows).
+// HBM a launch of `nq` queries needs as per-slot workspace on a handle of this index (slot_workspace, launch_plan.hpp).
 static size_t launch_workspace_bytes(fnv_index_s* ix, uint64_t nq) {
   std::lock_guard<std::mutex> lock(ix->mu);
   const int per_cu = ix->plan.valid ? std::max(ix->plan.bpc, ix->plan.sbpc) : 32;  // (no plan yet: the hardware's 32 waves per CU)
   const uint64_t slots = std::min<uint64_t>(2 * nq, (uint64_t)per_cu * (uint64_t)ix->num_cus);  // (small launches: a shadow per query)
   // (the plan's own formula -- plan.sorted is unset while the plan runs the two-heap kernel only; no plan yet: the largest automatic log)
   const uint64_t log_entries = ix->plan.valid ? log_entries_for(ix, ix->plan.B) : (ix->tie_replay ? std::max<uint64_t>(16384u, (uint64_t)ix->tie_log_entries) : 0u);
-  return (size_t)(slots * ((uint64_t)bitmap_words_of(ix) * 4 + (uint64_t)ovf_cap_of(ix) * 4 + (uint64_t)ix->spill_entries * 8 + log_entries * 8));
+  return (size_t)(slots * slot_workspace(ix, log_entries).bytes());
 }
 
 static uint64_t now_ns() {
@@ -74,7 +74,7 @@ static int search_host_enqueue(fnv_index_t ix, const void* queries, uint64_t nq,
   opt.timed = true;  // (a host-buffer call waits for its launch anyway: fnv_last_kernel_ms works after it as ever)
   const bool grouped = host_filter && host_filter->grouped;
   // (filter routing: a routed call's scan stage writes whole rows a second time -- it takes the staged copies, as grouped calls do)
-  const bool staged_only = grouped || (host_filter && !exhaustive && (ix->filter_scan_max > 0 || ix->filter_scan_on_overflow != 0));
+  const bool staged_only = grouped || (host_filter && !exhaustive && filter_routing_on(ix));
   if (grouped) {  // the filter table (its rows `stride` apart, as the caller has them), then query_filter, through d_allowed
     const size_t row_bytes = (size_t)((host_filter->n_bits + 7) / 8);
     const size_t tbytes = host_filter->n_filters && row_bytes ? (size_t)(host_filter->n_filters - 1) * host_filter->stride + row_bytes : 0;
@@ -275,7 +275,7 @@ static int search_batch_host(fnv_index_t ix, const void* queries, uint64_t nq, i
     // (a routed filtered search: its node bitmaps -- the grouped call's own among them --, grouping arrays, route words and partial lists)
     const size_t routed_need = host_filter && !exhaustive ? routed_workspace_bytes(ix, *host_filter, nq, K) : 0;
     const size_t need = launch_workspace_bytes(ix, nq) +
-                        (routed_need ? routed_need : host_filter && host_filter->grouped ? filter_rows_bytes(ix, *host_filter) : 0);
+                        (routed_need ? routed_need : host_filter && host_filter->grouped ? filter_rows_bytes(ix, host_filter->rows()) : 0);
     if (need <= ix->lane_budget_bytes) {
       std::lock_guard<std::mutex> admission(ix->lane_mu);
       for (int which = 1; which < fnv_index_s::kMaxLanes; which++) {

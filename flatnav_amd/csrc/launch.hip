@@ -1,6 +1,8 @@
-// launch.hip -- one search launch of the host runtime (runtime.hpp): kernel lookup, the cached launch plan, the kernel
-// choice, the workspace, the filter bitmaps, the graph search's and the exhaustive scan's launches, the status word, and
-// the entry points that take device buffers.  The only host unit that includes scan.hpp (its non-template kernels).
+// launch.hip -- one search launch of the host runtime (runtime.hpp): kernel lookup, the cached launch plan, the measurements
+// of the adaptive kernel choice, the workspace, the filter bitmaps, the graph search's and the exhaustive scan's launches as
+// sequences of named steps, the status word, and the entry points that take device buffers.  What a launch looks like -- its
+// shape, LDS bytes, tiles, segments, byte counts -- is asked of the planner (launch_plan.hpp); here are the HIP calls.
+// The only host unit that includes scan.hpp (its non-template kernels).
 #include "runtime.hpp"
 #ifdef FNV_DEV_FAST_BUILD
 #include "kernels.hpp"
@@ -192,7 +194,8 @@ static int next_dispenser_block(fnv_index_s* ix, hipStream_t stream, uint32_t** 
   return FNV_OK;
 }
 
-// ---- one search launch, step by step (search_device_impl runs them in this order under the handle's mutex) -----------
+// ---- what a search launch is made of (search_device_impl and scan_device_impl, below, run the steps in order under the
+// handle's mutex; every decision that is arithmetic is the planner's, launch_plan.hpp) ------------------------------------
 // (a) The launch plan: depends on (beam width, K, live geometry, options) only -> cached between calls.
 // The HIP runtime as the planner sees it: the kernels of one (index, beam width) by MODE_*.
 // A launch reads the mirror only while it is live, covers every live row and the option is on.
@@ -266,60 +269,54 @@ static int ensure_plan(fnv_index_s* ix, int B, int K, bool half_rows) {
 }
 
 // (b) Which kernel variant the launch runs, and whether it is a sample for the adaptive choice (KernelChoice and the rules
-// of each pick: launch_plan.hpp).
-// (tests/launch_plan_harness.cpp, lph_launch, repeats the pinned branch below and search_device_impl's choice of bpc / LDS bytes /
-// DIRECT form to shape launches on the CPU: a change here or there belongs in that twin as well)
+// of each pick: launch_plan.hpp).  Here only what needs the handle and the runtime: the measurements of an adaptive choice.
 static KernelChoice choose_kernel(fnv_index_s* ix, int B, uint64_t nq, int force_variant, bool filtered) {
-  const LaunchPlan& plan = ix->plan;
-  KernelChoice c = default_choice(ix, plan, nq, filtered);  // (what the plan prefers; below: what was pinned or measured)
+  KernelChoice c = default_choice(ix, ix->plan, nq, filtered, force_variant);  // (what the plan prefers, or what was pinned)
+  if (!c.adaptive) return c;
   const bool multi_round = c.multi_round;
-  const int pinned = force_variant >= 0 ? force_variant : (int)ix->sorted_variant;  // fnv_tune / "sorted_variant"
   const bool shadows_on = ix->shadow_exact != 0;
   const bool try_tail = ix->sorted_tail_exact_pct < 0;
-  if (c.sorted && pinned >= 0) {
-    c.variant = pinned_variant(pinned, multi_round, shadows_on);
-  } else if (c.sorted && ix->sorted_beam == 2 && ix->is_lane) {
+  if (ix->is_lane) {
     // a hidden lane runs what its owner has measured (copied by sync_lane) and never explores or samples: a production
     // caller that happens to land on a lane must not pay for 3 x variants exploratory launches per lane
     if (auto it = ix->tuner.find(tuner_key(B, multi_round)); nq >= 2048 && it != ix->tuner.end())
-      if (const int best = lane_variant(it->second, multi_round, try_tail, shadows_on); best >= 0) c.variant = best;
-  } else if (c.sorted && ix->sorted_beam == 2) {
-    if (ix->sample_kernel >= 0 && ix->launched && hipEventQuery(ix->ev1) == hipSuccess) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) == hipSuccess && ms > 0.f) {
-        Tuner& t = ix->tuner[ix->sample_B];
-        const float per_q = ms / (float)ix->sample_nq;
-        if (t.samples[ix->sample_kernel] == 0 || per_q < t.best[ix->sample_kernel]) t.best[ix->sample_kernel] = per_q;
-        t.samples[ix->sample_kernel]++;
-        ix->tune_epoch++;  // (lanes re-copy the measurements)
-      }
-      ix->sample_kernel = -1;
-    }
-    if (nq >= 2048) {
-      Tuner& t = ix->tuner[tuner_key(B, multi_round)];
-      // three samples each (the first launch of a kernel is a cold one; the best of the rest decides), then the fastest
-      // (fnv_tune takes all the samples in one call, so that no caller's launch is an exploratory one)
-      c.variant = owner_next_sample(t, multi_round, try_tail, shadows_on);
-      c.exploratory = c.variant >= 0;
-      if (c.variant < 0) c.variant = owner_final_variant(t, multi_round, try_tail, shadows_on);
-      c.sample = t.samples[c.variant] < 4;
-    }
+      if (const int best = lane_variant(it->second, multi_round, try_tail, shadows_on); best >= 0) set_variant(c, best);
+    return c;
   }
-  c.sorted = c.variant != 0;  // (unchanged where nothing was pinned or measured: variant 1 of a merged-beam plan, else 0)
-  if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
+  if (ix->sample_kernel >= 0 && ix->launched && hipEventQuery(ix->ev1) == hipSuccess) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) == hipSuccess && ms > 0.f) {
+      Tuner& t = ix->tuner[ix->sample_B];
+      const float per_q = ms / (float)ix->sample_nq;
+      if (t.samples[ix->sample_kernel] == 0 || per_q < t.best[ix->sample_kernel]) t.best[ix->sample_kernel] = per_q;
+      t.samples[ix->sample_kernel]++;
+      ix->tune_epoch++;  // (lanes re-copy the measurements)
+    }
+    ix->sample_kernel = -1;
+  }
+  if (nq >= 2048) {
+    Tuner& t = ix->tuner[tuner_key(B, multi_round)];
+    // three samples each (the first launch of a kernel is a cold one; the best of the rest decides), then the fastest
+    // (fnv_tune takes all the samples in one call, so that no caller's launch is an exploratory one)
+    int v = owner_next_sample(t, multi_round, try_tail, shadows_on);
+    c.exploratory = v >= 0;
+    if (v < 0) v = owner_final_variant(t, multi_round, try_tail, shadows_on);
+    c.sample = t.samples[v] < 4;
+    set_variant(c, v);
+  }
   return c;
 }
 
 // (c) The workspace, grown on demand and sized for whichever kernel keeps more slots resident.
 static int grow_workspace(fnv_index_s* ix, uint32_t max_slots, uint64_t nq, bool sorted, bool done_flags, bool filtered) {
-  const LaunchPlan& plan = ix->plan;
+  const SlotWorkspace per_slot = slot_workspace(ix, sorted ? ix->plan.sorted.log_entries : 0);
   int rc = FNV_OK;
   for (int attempt = 0; attempt < 2; attempt++) {
-    rc = ix->ws.bitmap.grow((size_t)max_slots * plan.heaps.bitmap_words * 4, true);
-    if (!rc) rc = ix->ws.ovf.grow((size_t)max_slots * plan.heaps.ovf_cap * 4);
-    if (!rc) rc = ix->ws.spill.grow((size_t)max_slots * plan.heaps.spill_entries * 8);
+    rc = ix->ws.bitmap.grow((size_t)max_slots * per_slot.bitmap, true);
+    if (!rc) rc = ix->ws.ovf.grow((size_t)max_slots * per_slot.ovf);
+    if (!rc) rc = ix->ws.spill.grow((size_t)max_slots * per_slot.spill);
     if (!rc && done_flags) rc = ix->d_done.grow((size_t)nq * 4);
-    if (!rc && sorted) rc = ix->ws.tielog.grow((size_t)max_slots * plan.sorted.log_entries * 8);
+    if (!rc && sorted) rc = ix->ws.tielog.grow((size_t)max_slots * per_slot.tielog);
     if (!rc && filtered) rc = ix->d_nodebits.grow((size_t)node_words(ix) * 4);
     ix->ws_bytes = ix->ws.bytes();
     // out of memory on the handle itself: the hidden lanes' idle workspaces go first, then once more (the lock order: fnv_index_s)
@@ -330,16 +327,12 @@ static int grow_workspace(fnv_index_s* ix, uint32_t max_slots, uint64_t nq, bool
   return rc;
 }
 
-// (d) Small launches on small indexes run the kernel's DIRECT form on a bitmap of all node ids: lay_out_direct (launch_plan.hpp).
-
 // ---- grouped filters: the node bitmaps of a launch with one filter per query ---------------------------------------
-// ws.rows for the n_filters + 2 rows of a grouped launch.  The one allocation of the library whose size the caller's
-// n_filters decides: its failure says how much that was, and a host-buffer caller's lane is admitted with it counted.
-size_t filter_rows_bytes(const fnv_index_s* ix, const SearchFilter& f) {
-  return (size_t)f.rows() * (size_t)node_words(ix) * 4;
-}
+// ws.rows for the n_filters + 2 rows of a grouped launch (filter_rows_bytes, launch_plan.hpp).  The one allocation of the
+// library whose size the caller's n_filters decides: its failure says how much that was, and a host-buffer caller's lane is
+// admitted with it counted.
 static int grow_filter_rows(fnv_index_s* ix, const SearchFilter& f) {
-  const size_t need = filter_rows_bytes(ix, f);
+  const size_t need = filter_rows_bytes(ix, f.rows());
   const int rc = ix->ws.rows.grow(need);
   ix->ws_bytes = ix->ws.bytes();
   if (rc == FNV_OK) return FNV_OK;
@@ -347,9 +340,13 @@ static int grow_filter_rows(fnv_index_s* ix, const SearchFilter& f) {
   return fail(FNV_ERR_RUNTIME, "the filter rows of this launch need " + std::to_string(need) + " bytes of device memory (" +
                                    std::to_string(f.rows()) + " node bitmaps), which could not be allocated");
 }
-// ... filled from the filter table and the labels as they are now; row_count (null: not wanted, else zero): nodes set per row
-static int launch_filter_rows(fnv_index_s* ix, const SearchFilter& f, uint64_t live, hipStream_t stream, uint32_t* row_count) {
+// ... filled from the filter table and the labels as they are now.  `ga` (null: not wanted): the launch's grouping arrays in
+// ws.group -- their cleared prefix is zeroed here, and row_count takes the nodes set per row.
+static int launch_filter_rows(fnv_index_s* ix, const SearchFilter& f, uint64_t live, hipStream_t stream, const GroupArrays* ga) {
   const uint64_t words = node_words(ix);
+  uint32_t* const w = ix->ws.group.as<uint32_t>();
+  if (ga) HIP_TRY(hipMemsetAsync(w + ga->counts, 0, ga->cleared_bytes, stream));
+  uint32_t* const row_count = ga ? w + ga->row_count : nullptr;
   const dim3 grid((unsigned)((words * 32 + 255) / 256), (unsigned)std::min<uint64_t>(f.rows(), 65535));
   hipLaunchKernelGGL(node_filter_table_kernel, grid, dim3(256), 0, stream, (const int32_t*)ix->d_labels, live, words, f.bits, f.stride,
                      f.n_bits, (uint32_t)f.n_filters, ix->ws.rows.as<uint32_t>(), row_count);
@@ -386,71 +383,18 @@ static void record_launch(fnv_index_s* ix, hipStream_t stream, uint32_t* dispens
   const uint64_t geom[8] = {grid, block, lds, g3, g4, g5, mode, g7};
   for (int i = 0; i < 8; i++) ix->geom[i] = geom[i];
 }
-// The grouping arrays of a grouped scan (scan.hpp's group_* kernels), as uint32 offsets into one buffer.
-// `routed` (the scan stage of a routed filtered graph search): nq route words and the overflow flag behind them as well.
-struct GroupArrays {
-  size_t query_row, perm, counts, cursor, row_count, slot_start, tile_start, tiles, route, bytes;
-  GroupArrays(uint64_t nq, uint64_t rows, uint64_t tile_bound, bool routed = false) {
-    query_row = 0;
-    perm = query_row + nq;
-    counts = perm + nq;  // counts | cursor | row_count: cleared by one memset
-    cursor = counts + rows;
-    row_count = cursor + rows;
-    slot_start = row_count + rows;
-    tile_start = slot_start + rows + 1;
-    tiles = tile_start + rows + 1;
-    route = tiles + 3 * tile_bound;
-    bytes = (route + (routed ? nq + 1 : 0)) * 4;
-  }
-};
-
 // ---- exhaustive search (scan.hpp): the launch ---------------------------------------------------------------------
-// How a launch of `nq` queries for K results is cut up: queries per tile (as many as a block's LDS budget holds next to their
-// result lists, at most 32), row segments (enough blocks to fill the device, at most 64 and at most what keeps the partial
-// lists within 256 MB; or what "scan_segment_rows" asks for).
-constexpr uint32_t kScanLdsBudget = 20u << 10;  // per block: eight blocks per CU = two wavefronts per SIMD
-constexpr uint32_t kScanMaxTile = 32, kScanMaxSegments = 64, kScanForcedSegments = 1024;
-constexpr uint64_t kScanPartialBudget = 256ull << 20;
-constexpr uint32_t kScanMaxLds = 160u << 10;  // one query and its list must fit a block's LDS
-struct ScanShape {
-  uint32_t tile, tiles, segments, lds;
-};
-// `filter_rows` != 0: a grouped launch over that many filter rows -- the id queue comes out of the block's LDS budget, and
-// `tiles` is the bound on the data-dependent tile count that the launch covers (scan_select.hpp, group_tile_bound).
-static ScanShape scan_shape(const fnv_index_s* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows = 0) {
-  ScanShape s;
-  const uint32_t per_query = g.q_chunks * 16u + (uint32_t)K * 8u;
-  const uint32_t queue = filter_rows ? SCAN_QUEUE_IDS * 4u : 0u;
-  s.tile = std::max(1u, std::min(kScanMaxTile, (kScanLdsBudget - queue) / per_query));
-  s.tile = (uint32_t)std::min<uint64_t>(s.tile, nq);
-  s.lds = s.tile * per_query + queue;
-  s.tiles = (uint32_t)(filter_rows ? group_tile_bound(nq, filter_rows, s.tile) : (nq + s.tile - 1) / s.tile);
-  uint64_t seg;
-  if (ix->scan_segment_rows > 0) {
-    seg = std::min<uint64_t>((live + (uint64_t)ix->scan_segment_rows - 1) / (uint64_t)ix->scan_segment_rows, kScanForcedSegments);
-  } else {
-    const uint64_t want_blocks = (uint64_t)std::max(1, ix->num_cus) * 8u;
-    seg = std::min<uint64_t>((want_blocks + s.tiles - 1) / s.tiles, std::max<uint64_t>(1, live / 1024));
-    seg = std::min<uint64_t>(seg, kScanMaxSegments);
-    seg = std::min<uint64_t>(seg, std::max<uint64_t>(1, kScanPartialBudget / (nq * (uint64_t)K * 8u)));
-  }
-  seg = std::min<uint64_t>(seg, 0x7FFFFFFFull / s.tiles);
-  s.segments = (uint32_t)std::max<uint64_t>(1, seg);
-  return s;
-}
+// (how a launch is cut up, its grouping arrays and byte counts: scan_shape, GroupArrays and their neighbours in launch_plan.hpp)
 
-// Filter routing of a filtered graph search ("filter_scan_max" / "filter_scan_on_overflow", scan_select.hpp): whether this launch
-// routes, its filter as a TABLE -- the grouped call's own, or, the single-filter call, a table of that one filter with a null
-// query_filter (every query reads row 0) -- and the shape of the scan stage.  Routing is not applied where the scan cannot take
-// the call (K beyond its lists, rows too long for its LDS): an option never makes a valid call invalid.
-struct RoutedLaunch {
-  bool on = false;
+// Filter routing of a filtered graph search (plan_scan_routing, launch_plan.hpp): whether this launch routes, the shape of the
+// scan stage, and its filter as a TABLE -- the grouped call's own, or, the single-filter call, a table of that one filter with a
+// null query_filter (every query reads row 0).
+struct RoutedLaunch : ScanRouting {
   SearchFilter table{nullptr, 0};
-  ScanShape shape{};
 };
 static RoutedLaunch plan_routing(const fnv_index_s* ix, const SearchFilter* filter, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
   RoutedLaunch r;
-  if (!filter || (ix->filter_scan_max <= 0 && ix->filter_scan_on_overflow == 0) || K > SCAN_MAX_K) return r;
+  if (!filter || !filter_routing_on(ix)) return r;  // (as the planner will say: nothing to rewrite for it)
   r.table = *filter;
   if (!filter->grouped) {
     r.table.grouped = true;
@@ -458,20 +402,17 @@ static RoutedLaunch plan_routing(const fnv_index_s* ix, const SearchFilter* filt
     r.table.stride = (filter->n_bits + 7) / 8;
     r.table.query_filter = nullptr;
   }
-  r.shape = scan_shape(ix, g, nq, K, live, r.table.rows());
-  r.on = r.shape.lds <= kScanMaxLds;
+  static_cast<ScanRouting&>(r) = plan_scan_routing(ix, g, nq, K, live, r.table.rows());
   return r;
 }
-// HBM a routed launch of `nq` queries takes on top of the search kernel's per-slot workspace (0: the launch does not route): the
-// node bitmaps, the grouping arrays with the route words, the partial lists.  What a host-buffer caller's lane is admitted with.
+// HBM a routed launch of `nq` queries takes on top of the search kernel's per-slot workspace (0: the launch does not route).
+// What a host-buffer caller's lane is admitted with.
 size_t routed_workspace_bytes(fnv_index_s* ix, const SearchFilter& f, uint64_t nq, int K) {
   std::lock_guard<std::mutex> lock(ix->mu);
   const uint64_t live = live_nodes(ix);
   if (nq == 0 || nq > 0x7FFFFFFFull || K < 1) return 0;
   const RoutedLaunch r = plan_routing(ix, &f, row_geometry(ix), nq, K, live);
-  if (!r.on) return 0;
-  return filter_rows_bytes(ix, r.table) + GroupArrays(nq, r.table.rows(), r.shape.tiles, true).bytes +
-         (size_t)nq * r.shape.segments * (size_t)K * 8;
+  return r.on ? routed_scan_bytes(ix, r.table.rows(), nq, K, r.shape) : 0;
 }
 
 // What the scan kernels are told about the index and the call (cand_ids / cand_count, the single-filter scan's own, stay null).
@@ -533,7 +474,7 @@ static int launch_grouping(fnv_index_s* ix, const SearchFilter& f, const GroupAr
 // The grouped scan and its merge.  `route` as above: the merge then answers the routed queries only and zeroes their out_nhops.
 static int launch_grouped_scan(fnv_index_s* ix, scan_grouped_fn kern_g, const GroupedScanParams& gp, const ScanShape& shape, uint64_t nq,
                                hipStream_t stream, const uint32_t* route = nullptr, uint64_t* out_nhops = nullptr) {
-  const uint32_t merge_lds = 3u * gp.s.K * 8u;
+  const uint32_t merge_lds = scan_merge_lds(gp.s.K);
   HIP_TRY(raise_lds_limit((const void*)kern_g, ix->device, shape.lds));
   hipLaunchKernelGGL(kern_g, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp);
   HIP_TRY(hipGetLastError());
@@ -543,6 +484,21 @@ static int launch_grouped_scan(fnv_index_s* ix, scan_grouped_fn kern_g, const Gr
   return FNV_OK;
 }
 
+// The single-filter scan's candidates: the label bitmap -> this handle's node bitmap -> the list of allowed node ids.
+static int launch_candidate_list(fnv_index_s* ix, const SearchFilter& f, uint64_t live, hipStream_t stream, ScanParams* p) {
+  uint32_t* const ids = ix->d_scanids.as<uint32_t>();
+  const int rc = launch_node_filter(ix, f, live, stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(ids, 0, 16, stream));
+  hipLaunchKernelGGL(exhaustive_compact_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, stream,
+                     (const uint32_t*)ix->d_nodebits.as<uint32_t>(), live, ids + 4, ids);
+  HIP_TRY(hipGetLastError());
+  p->cand_ids = ids + 4;
+  p->cand_count = ids;
+  return FNV_OK;
+}
+
+// One exhaustive search: shape (planner), workspace, filter bitmaps, the scan and its merge, record.
 static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, const SearchOutputs& out, void* hip_stream,
                             const SearchOptions& opt) {
   int rc;
@@ -554,64 +510,163 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const SearchFilter* filter = opt.filter;
   const uint64_t live = live_nodes(ix);
   const RowGeometry g = row_geometry(ix);
-  const bool grouped = filter && filter->grouped;
+  const bool grouped = filter && filter->grouped, listed = filter && !grouped;
+
+  // -- shape
   const ScanShape shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
   if (shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
-  const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
-  const scan_grouped_fn kern_g = kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full];
   const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
-  rc = ix->ws.scan.grow((size_t)nq * shape.segments * (size_t)K * 8);
+  // -- workspace
+  rc = ix->ws.scan.grow(scan_partial_bytes(nq, shape, K));
   if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
   if (!rc && grouped) rc = ix->ws.group.grow(ga.bytes);
-  if (!rc && filter && !grouped) rc = ix->d_nodebits.grow((size_t)node_words(ix) * 4);
-  if (!rc && filter && !grouped) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
+  if (!rc && listed) rc = ix->d_nodebits.grow((size_t)node_words(ix) * 4);
+  if (!rc && listed) rc = ix->d_scanids.grow(16 + (size_t)ix->capacity * 4);
   ix->ws_bytes = ix->ws.bytes();
   if (rc) return rc;
 
-  ScanParams p = scan_params(ix, g, d_queries, nq, K, out, opt, shape, live);
-
+  // -- filter bitmaps (grouped: with their popcounts, and the queries grouped by row into tiles)
+  GroupedScanParams gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.s = scan_params(ix, g, d_queries, nq, K, out, opt, shape, live);
   // (the status word: this path never sets it; the scan's kernels zero no block, so the next search launch memsets its own)
   uint32_t* const block = ix->last_block;
   HIP_TRY(hipMemsetAsync(block, 0, 16 * sizeof(uint32_t), stream));
-  GroupedScanParams gp;
-  memset(&gp, 0, sizeof(gp));
-  if (grouped) {  // the filter table -> this handle's node bitmaps and their popcounts; the queries grouped by row into tiles
-    uint32_t* const w = ix->ws.group.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(w + ga.counts, 0, (size_t)3 * filter->rows() * 4, stream));  // counts | cursor | row_count
-    rc = launch_filter_rows(ix, *filter, live, stream, w + ga.row_count);
-    if (!rc) rc = launch_grouping(ix, *filter, ga, shape, nq, live, stream, nullptr, &gp);
-    if (rc) return rc;
-  } else if (filter) {  // the label bitmap -> this handle's node bitmap -> the list of allowed node ids
-    uint32_t* const ids = ix->d_scanids.as<uint32_t>();
-    rc = launch_node_filter(ix, *filter, live, stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ids, 0, 16, stream));
-    hipLaunchKernelGGL(exhaustive_compact_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, stream,
-                       (const uint32_t*)ix->d_nodebits.as<uint32_t>(), live, ids + 4, ids);
-    HIP_TRY(hipGetLastError());
-    p.cand_ids = ids + 4;
-    p.cand_count = ids;
-  }
+  if (grouped) rc = launch_filter_rows(ix, *filter, live, stream, &ga);
+  if (!rc && grouped) rc = launch_grouping(ix, *filter, ga, shape, nq, live, stream, nullptr, &gp);
+  if (listed) rc = launch_candidate_list(ix, *filter, live, stream, &gp.s);
+  if (rc) return rc;
+
+  // -- the scan and its merge
   ix->sample_kernel = -1;  // ev0 / ev1 no longer bracket a graph-search launch: a pending sample of the adaptive choice is dropped
   HIP_TRY(hipEventRecord(ix->ev0, stream));
-  const uint32_t merge_lds = 3u * (uint32_t)K * 8u;
   if (grouped) {
-    gp.s = p;
-    rc = launch_grouped_scan(ix, kern_g, gp, shape, nq, stream);
+    rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full], gp, shape, nq, stream);
     if (rc) return rc;
   } else {
+    const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
     HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
-    hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp.s);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(exhaustive_merge_kernel, dim3((unsigned)nq), dim3(WAVE), merge_lds, stream, p);
+    hipLaunchKernelGGL(exhaustive_merge_kernel, dim3((unsigned)nq), dim3(WAVE), scan_merge_lds((uint32_t)K), stream, gp.s);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ix->ev1, stream));
-  // (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id queue, row segments)
+
+  // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
+  // queue, row segments)
   record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped ? shape.tile : 0,
                 grouped ? SCAN_QUEUE_IDS : 0, grouped ? shape.segments : 0, 3, 0);
   return FNV_OK;
+}
+
+// ---- one graph search: plan, shape (planner), workspace, filter bitmaps, K0, the launch, scan stage, record ---------------
+// Plan: the mirror's state, the cached plan, and -- a filtered launch's first -- the filtered kernel with its residency.
+static int plan_search(fnv_index_s* ix, int B, int K, uint64_t live, bool filtered) {
+  // The half-width mirror (half_rows.hpp): its state is the source's, read at every launch.  Launches with and without it run
+  // different kernels, so what was measured in the other mode (kernel variant, LDS layout) is discarded with the plan.
+  const bool half_rows = half_rows_usable(ix, live);
+  if (ix->measured_half >= 0 && ix->measured_half != (int)half_rows) {
+    ix->tuner.clear();
+    ix->layouts.clear();
+    ix->sample_kernel = -1;
+    ix->tune_epoch++;
+    ix->plan.valid = false;
+  }
+  ix->measured_half = (int)half_rows;
+  const int rc = ensure_plan(ix, B, K, half_rows);
+  if (rc) return rc;
+  PlannedLaunch& plan = ix->plan;
+  if (filtered && !plan.fkern.fn) {
+    plan.fkern = bind_search_kernel(ix, row_geometry(ix), KERNEL_FILTERED, false, B, half_rows);
+    HIP_TRY(raise_lds_limit((const void*)plan.fkern.fn, ix->device, plan.lds));
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern.fn, WAVE, plan.lds) != hipSuccess) n = 0;
+    plan.fbpc = std::max(1, std::min(plan.bpc, n));
+  }
+  return FNV_OK;
+}
+// The per-call fields of the parameter block (the plan left them unset), the dispenser block's among them.
+static void fill_call_fields(fnv_index_s* ix, SearchParams& p, const void* d_queries, uint64_t nq, const SearchOutputs& out,
+                             const SearchOptions& opt, const SearchLaunch& L, bool sorted, uint64_t live, uint32_t* block, uint32_t* other) {
+  p.labels = (opt.node_ids || ix->output_node_ids != 0) ? nullptr : ix->d_labels;  // ("output_node_ids": read under the handle's mutex)
+  p.queries = (const uint8_t*)d_queries;
+  p.out_dist = out.dist;
+  p.out_labels = out.labels;
+  p.out_count = out.count;
+  p.out_ndist = out.ndist;
+  p.out_nhops = out.nhops;
+  p.n_nodes = live;
+  p.nq = (uint32_t)nq;
+  p.scan_step = L.scan_step;  // Index.h:851-861
+  p.n_scan = L.n_scan;
+  p.ovf_bitmap = ix->ws.bitmap.as<uint32_t>();
+  p.ovf_glist = ix->ws.ovf.as<uint32_t>();
+  p.cand_spill = ix->ws.spill.as<unsigned long long>();
+  p.tie_log = ix->ws.tielog.as<unsigned long long>();
+  if (!sorted) p.log_entries = 0u;
+  p.dispenser = block;
+  p.dispenser_next = other;
+  p.status = (int32_t*)(block + 1);
+  p.host_status = opt.host_status;
+  p.redo_count = block + 3;  // [3] queries searched exactly after a tie, [4..7] by reason
+  p.phase_cycles = ix->d_phase;
+  p.tail_exact = L.tail_exact;
+}
+// Filter bitmaps: the filter table -> this handle's node bitmaps, every query reading its own row (routed: the rows' popcounts
+// -> who goes to the scan, before the search kernel has seen it); or the one filter -> d_nodebits.
+static int launch_search_filter(fnv_index_s* ix, const SearchFilter* filter, const SearchFilter* rows_of, const RoutedLaunch& routing,
+                                const GroupArrays& ga, uint64_t nq, uint64_t live, hipStream_t stream, SearchParams& p) {
+  if (!rows_of) {
+    if (filter) p.node_bits = ix->d_nodebits.as<uint32_t>();
+    return filter ? launch_node_filter(ix, *filter, live, stream) : FNV_OK;
+  }
+  const int rc = launch_filter_rows(ix, *rows_of, live, stream, routing.on ? &ga : nullptr);
+  if (rc) return rc;
+  p.node_bits = ix->ws.rows.as<uint32_t>();
+  p.query_filter = rows_of->query_filter;
+  p.filter_words = (uint32_t)node_words(ix);
+  p.n_filters = (uint32_t)rows_of->n_filters;
+  if (routing.on) {
+    uint32_t* const gw = ix->ws.group.as<uint32_t>();
+    hipLaunchKernelGGL(route_queries_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, stream, routing.table.query_filter,
+                       (uint32_t)nq, (uint32_t)routing.table.n_filters, (const uint32_t*)(gw + ga.row_count), (uint64_t)ix->filter_scan_max,
+                       (uint32_t)(ix->filter_scan_on_overflow != 0), gw + ga.route);
+    HIP_TRY(hipGetLastError());
+    p.query_route = gw + ga.route;
+  }
+  return FNV_OK;
+}
+// K0: one pass over the shared entry-scan nodes for the whole batch (LDS-staged, entry_scan_tile), same stream.
+static int launch_entry_scan(fnv_index_s* ix, SearchParams& p, uint64_t nq, hipStream_t stream) {
+  const int rc = ix->d_entry.grow((size_t)nq * 8);
+  if (rc) return rc;
+  p.entry_node_out = ix->d_entry.as<uint32_t>();
+  p.entry_dist_out = (float*)(ix->d_entry.as<uint8_t>() + (size_t)nq * 4);
+  p.vectors = ix->d_vectors;  // (K0 stages float32 rows in LDS whichever table the search kernel reads)
+  p.row_bytes = ix->row_bytes;
+  const EntryScanTile tile = entry_scan_tile(p.row_bytes, p.q_chunks, p.n_scan, nq);
+  p.scan_tile_stride = tile.stride;
+  p.scan_tile_rows = tile.rows;
+  kernel_fn scan = pick_scan_kernel(ix->dtype, ix->metric, ix->plan.cfg, ix->plan.full);
+  HIP_TRY(raise_lds_limit((const void*)scan, ix->device, tile.lds));
+  hipLaunchKernelGGL(scan, dim3(tile.grid), dim3(SCAN_WAVES * WAVE), tile.lds, stream, p);
+  HIP_TRY(hipGetLastError());
+  p.entry_node = p.entry_node_out;
+  p.entry_dist = p.entry_dist_out;
+  return FNV_OK;
+}
+// Scan stage of a routed launch, on the same stream: the queries whose route word is set, grouped by filter row into tiles.
+static int launch_scan_stage(fnv_index_s* ix, const RoutedLaunch& routing, const GroupArrays& ga, const RowGeometry& g, const void* d_queries,
+                             uint64_t nq, int K, const SearchOutputs& out, const SearchOptions& opt, uint64_t live, hipStream_t stream) {
+  uint32_t* const route = ix->ws.group.as<uint32_t>() + ga.route;
+  GroupedScanParams gp;
+  memset(&gp, 0, sizeof(gp));
+  const int rc = launch_grouping(ix, routing.table, ga, routing.shape, nq, live, stream, route, &gp);
+  if (rc) return rc;
+  gp.s = scan_params(ix, g, d_queries, nq, K, out, opt, routing.shape, live);
+  return launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full], gp, routing.shape, nq, stream, route, out.nhops);
 }
 
 int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
@@ -625,176 +680,85 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   ON_DEVICE(ix->device);
   hipStream_t stream = (hipStream_t)hip_stream;
   const SearchFilter* filter = opt.filter;
-
   const int B = std::max(ef_search, K);  // Index.h:392
   const uint64_t live = live_nodes(ix);
-  // The half-width mirror (half_rows.hpp): its state is the source's, read at every launch.  Launches with and without it run
-  // different kernels, so what was measured in the other mode (kernel variant, LDS layout) is discarded with the plan.
-  const bool half_rows = half_rows_usable(ix, live);
-  if (ix->measured_half >= 0 && ix->measured_half != (int)half_rows) {
-    ix->tuner.clear();
-    ix->layouts.clear();
-    ix->sample_kernel = -1;
-    ix->tune_epoch++;
-    ix->plan.valid = false;
-  }
-  ix->measured_half = (int)half_rows;
-  rc = ensure_plan(ix, B, K, half_rows);
+
+  // -- plan
+  rc = plan_search(ix, B, K, live, filter != nullptr);
   if (rc) return rc;
-  PlannedLaunch& plan = ix->plan;
-  if (filter && !plan.fkern.fn) {
-    plan.fkern = bind_search_kernel(ix, row_geometry(ix), KERNEL_FILTERED, false, B, half_rows);
-    HIP_TRY(raise_lds_limit((const void*)plan.fkern.fn, ix->device, plan.lds));
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)plan.fkern.fn, WAVE, plan.lds) != hipSuccess) n = 0;
-    plan.fbpc = std::max(1, std::min(plan.bpc, n));
-  }
+  const PlannedLaunch& plan = ix->plan;
+
+  // -- shape: the kernel variant, then everything shape_search (launch_plan.hpp) derives from it -- shadow mode, tail shadows,
+  // the grid, the DIRECT form, the parameter block `p`; and whether the launch routes (a scan stage follows the search kernel)
   const KernelChoice c = choose_kernel(ix, B, nq, opt.force_variant, filter != nullptr);
   const bool sorted = c.sorted;
-  const int bpc = sorted ? plan.sbpc : opt.filter ? plan.fbpc : plan.bpc;
-  uint32_t lds_bytes = sorted ? plan.slds : plan.lds;
-  // (shadow mode, tail shadows, the grid: launch_shape, launch_plan.hpp)
-  const LaunchShape shape = launch_shape(ix, plan, c, bpc, nq, num_initializations, live);
-  const bool small_launch = shape.small_launch, shadow = shape.shadow;
-  const uint32_t nslots = shape.nslots, tail_shadows = shape.tail_shadows;
-
-  const bool grouped = filter && filter->grouped;
-  // Filter routing (scan_select.hpp): with an option on, and wherever the scan can take the call (else the graph form as ever),
-  // the launch keeps a route word per query and a scan stage follows the search kernel.  One routed implementation: the
-  // single-filter call becomes a grouped launch over a table of one filter (a null query_filter reads row 0).
+  SearchParams p;
+  const SearchLaunch L = shape_search(ix, plan, c, filter ? plan.fbpc : 0, nq, num_initializations, live, p);
   const RowGeometry sg = row_geometry(ix);
   const RoutedLaunch routing = plan_routing(ix, filter, sg, nq, K, live);
-  const bool routed = routing.on;
-  const SearchFilter& table = routing.table;
-  const ScanShape& sshape = routing.shape;
-  const SearchFilter* const rows_of = routed ? &table : grouped ? filter : nullptr;  // the launch reads a table of node bitmaps
-  const GroupArrays ga(nq, routed ? table.rows() : 0, sshape.tiles, true);
-  rc = grow_workspace(ix, shape.max_slots, nq, sorted, shadow || tail_shadows, filter != nullptr && !rows_of);
+  const SearchFilter* const rows_of = routing.on ? &routing.table : filter && filter->grouped ? filter : nullptr;  // a table of node bitmaps
+  const GroupArrays ga(nq, routing.on ? routing.table.rows() : 0, routing.shape.tiles, true);
+
+  // -- workspace (per slot; the node bitmaps; routed: the scan stage's lists and arrays), then the per-call fields
+  rc = grow_workspace(ix, L.max_slots, nq, sorted, L.shadow || L.tail_shadows, filter != nullptr && !rows_of);
   if (!rc && rows_of) rc = grow_filter_rows(ix, *rows_of);
-  if (!rc && routed) rc = ix->ws.scan.grow((size_t)nq * sshape.segments * (size_t)K * 8);
-  if (!rc && routed) rc = ix->ws.group.grow(ga.bytes);
+  if (!rc && routing.on) rc = ix->ws.scan.grow(scan_partial_bytes(nq, routing.shape, K));
+  if (!rc && routing.on) rc = ix->ws.group.grow(ga.bytes);
   ix->ws_bytes = ix->ws.bytes();
   if (rc) return rc;
-
-  SearchParams p = sorted ? plan.sorted : plan.heaps;
-  const bool direct = sorted && small_launch && lay_out_direct(ix, p, &lds_bytes, bpc, nslots);
-
-  // (e) the per-call fields, and the launch
-  const BoundKernel& kern = filter ? plan.fkern : !sorted ? plan.kern : direct ? plan.skern_direct : plan.skern;
-  p.labels = (opt.node_ids || ix->output_node_ids != 0) ? nullptr : ix->d_labels;  // ("output_node_ids": read under the handle's mutex)
-  p.queries = (const uint8_t*)d_queries;
-  p.out_dist = out.dist;
-  p.out_labels = out.labels;
-  p.out_count = out.count;
-  p.out_ndist = out.ndist;
-  p.out_nhops = out.nhops;
-  p.n_nodes = live;
-  p.nq = (uint32_t)nq;
-  p.scan_step = shape.scan_step;  // Index.h:851-861
-  p.n_scan = shape.n_scan;
-  p.ovf_bitmap = ix->ws.bitmap.as<uint32_t>();
-  p.ovf_glist = ix->ws.ovf.as<uint32_t>();
-  p.cand_spill = ix->ws.spill.as<unsigned long long>();
-  p.tie_log = ix->ws.tielog.as<unsigned long long>();
-  if (!sorted) p.log_entries = 0u;
+  const BoundKernel& kern = filter ? plan.fkern : !sorted ? plan.kern : L.direct ? plan.skern_direct : plan.skern;
   uint32_t *block = nullptr, *other = nullptr;
   rc = next_dispenser_block(ix, stream, &block, &other);
   if (rc) return rc;
-  p.dispenser = block;
-  p.dispenser_next = other;
-  p.status = (int32_t*)(block + 1);
-  p.host_status = opt.host_status;
-  p.redo_count = block + 3;  // [3] queries searched exactly after a tie, [4..7] by reason
-  p.phase_cycles = ix->d_phase;
-  p.tail_exact = shape.tail_exact;
+  fill_call_fields(ix, p, d_queries, nq, out, opt, L, sorted, live, block, other);
   // ev0 / ev1 only where somebody will read them (runtime.hpp, time_launches)
   const bool timed = c.sample || opt.timed || opt.force_variant >= 0 || ix->time_launches.load();
 
-  uint32_t* const gw = routed ? ix->ws.group.as<uint32_t>() : nullptr;
-  if (rows_of) {  // the filter table -> this handle's node bitmaps; every query reads its own row
-    if (routed) HIP_TRY(hipMemsetAsync(gw + ga.counts, 0, (size_t)3 * table.rows() * 4, stream));  // counts | cursor | row_count
-    rc = launch_filter_rows(ix, *rows_of, live, stream, routed ? gw + ga.row_count : nullptr);
-    if (rc) return rc;
-    p.node_bits = ix->ws.rows.as<uint32_t>();
-    p.query_filter = rows_of->query_filter;
-    p.filter_words = (uint32_t)node_words(ix);
-    p.n_filters = (uint32_t)rows_of->n_filters;
-    if (routed) {  // the rows' popcounts -> who goes to the scan before the search kernel has seen it
-      hipLaunchKernelGGL(route_queries_kernel, dim3((unsigned)((nq + 1 + 255) / 256)), dim3(256), 0, stream, table.query_filter, (uint32_t)nq,
-                         (uint32_t)table.n_filters, (const uint32_t*)(gw + ga.row_count), (uint64_t)ix->filter_scan_max,
-                         (uint32_t)(ix->filter_scan_on_overflow != 0), gw + ga.route);
-      HIP_TRY(hipGetLastError());
-      p.query_route = gw + ga.route;
-    }
-  } else if (filter) {
-    rc = launch_node_filter(ix, *filter, live, stream);
-    if (rc) return rc;
-    p.node_bits = ix->d_nodebits.as<uint32_t>();
-  }
+  // -- filter bitmaps
+  rc = launch_search_filter(ix, filter, rows_of, routing, ga, nq, live, stream, p);
+  if (rc) return rc;
   if (timed) HIP_TRY(hipEventRecord(ix->ev0, stream));
-  if (ix->entry_kernel && !ix->tail_bytes) {  // (split rows: K0's LDS tiles hold one table's rows; the in-kernel scan serves them)
-    // K0: one pass over the shared entry-scan nodes for the whole batch (LDS-staged), same stream
-    rc = ix->d_entry.grow((size_t)nq * 8);
-    if (rc) return rc;
-    p.entry_node_out = ix->d_entry.as<uint32_t>();
-    p.entry_dist_out = (float*)(ix->d_entry.as<uint8_t>() + (size_t)nq * 4);
-    p.vectors = ix->d_vectors;  // (K0 stages float32 rows in LDS whichever table the search kernel reads)
-    p.row_bytes = ix->row_bytes;
-    p.scan_tile_stride = p.row_bytes + 16;
-    const uint32_t fixed = SCAN_WAVES * p.q_chunks * 16 + SCAN_QPB * 8;
-    p.scan_tile_rows = std::max<uint32_t>(1, std::min<uint32_t>(p.n_scan, (64u * 1024u) / p.scan_tile_stride));
-    const uint32_t scan_lds = fixed + p.scan_tile_rows * p.scan_tile_stride;
-    kernel_fn scan = pick_scan_kernel(ix->dtype, ix->metric, plan.cfg, plan.full);
-    HIP_TRY(raise_lds_limit((const void*)scan, ix->device, scan_lds));
-    hipLaunchKernelGGL(scan, dim3((unsigned)((nq + SCAN_QPB - 1) / SCAN_QPB)), dim3(SCAN_WAVES * WAVE), scan_lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    p.entry_node = p.entry_node_out;
-    p.entry_dist = p.entry_dist_out;
-  }
-  if (tail_shadows) {  // the queries, then exact shadows of the last `tail_shadows` of them (pulled by slots that would go idle)
+
+  // -- K0 (split rows: its LDS tiles hold one table's rows; the in-kernel scan serves them)
+  if (ix->entry_kernel && !ix->tail_bytes) rc = launch_entry_scan(ix, p, nq, stream);
+  if (rc) return rc;
+  // -- shadows: from here on the launch has more work items than queries -- the queries, then exact shadows of all of them
+  // (shadow mode) or of the last `tail_shadows` (pulled by slots that would go idle); the two never meet in one launch
+  if (L.shadow || L.tail_shadows) {
     HIP_TRY(hipMemsetAsync(ix->d_done.ptr, 0, (size_t)nq * 4, stream));
     p.shadow_base = (uint32_t)nq;
     p.done_flags = ix->d_done.as<uint32_t>();
-    p.nq = (uint32_t)(nq + tail_shadows);
+    p.nq = (uint32_t)(nq + (L.shadow ? nq : L.tail_shadows));
     p.tail_exact = 0u;
   }
-  if (shadow) {  // from here on the launch has 2 nq work items: the queries, then their exact shadows
-    HIP_TRY(hipMemsetAsync(ix->d_done.ptr, 0, (size_t)nq * 4, stream));
-    p.shadow_base = (uint32_t)nq;
-    p.done_flags = ix->d_done.as<uint32_t>();
-    p.nq = (uint32_t)(2 * nq);
-    p.tail_exact = 0u;
-  }
+
+  // -- the launch
   p.vectors = kern.rows;  // the kernel and the table it reads: one BoundKernel
   p.row_bytes = kern.stride;
-  HIP_TRY(raise_lds_limit((const void*)kern.fn, ix->device, lds_bytes));
-  hipLaunchKernelGGL(kern.fn, dim3(nslots), dim3(WAVE), lds_bytes, stream, p);
+  HIP_TRY(raise_lds_limit((const void*)kern.fn, ix->device, L.lds));
+  hipLaunchKernelGGL(kern.fn, dim3(L.nslots), dim3(WAVE), L.lds, stream, p);
   HIP_TRY(hipGetLastError());
   // the blocks change hands HERE: whatever fails below, the next launch must not take this one's block for a zeroed one
   ix->last_stream = stream;
   ix->last_block = block;
   ix->zeroed_block = (int)(other != ix->d_dispenser);
-  if (routed) {  // the scan stage, on the same stream: the queries whose route word is set, grouped by filter row into tiles
-    GroupedScanParams gp;
-    memset(&gp, 0, sizeof(gp));
-    rc = launch_grouping(ix, table, ga, sshape, nq, live, stream, gw + ga.route, &gp);
-    if (rc) return rc;
-    gp.s = scan_params(ix, sg, d_queries, nq, K, out, opt, sshape, live);
-    rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[sg.cfg][sg.full], gp, sshape, nq, stream, gw + ga.route, out.nhops);
-    if (rc) return rc;
-  }
+
+  // -- scan stage
+  if (routing.on) rc = launch_scan_stage(ix, routing, ga, sg, d_queries, nq, K, out, opt, live, stream);
+  if (rc) return rc;
   if (timed) HIP_TRY(hipEventRecord(ix->ev1, stream));
-  // (f) what the launch was: for the adaptive choice's next harvest, and for the fnv_last_* calls
+
+  // -- record: for the adaptive choice's next harvest, and for the fnv_last_* calls
   ix->sample_kernel = c.sample ? c.variant : -1;  // (a sample is always timed)
   ix->sample_B = tuner_key(B, c.multi_round);
   ix->sample_nq = nq;
   ix->last_variant = sorted ? std::max(c.variant, 1) : 0;
   ix->last_exploratory = c.exploratory;
   if (c.exploratory) ix->explored_launches++;
-  ix->last_shadow = shadow;
+  ix->last_shadow = L.shadow;
   ix->last_half = kern.half_rows;
-  record_launch(ix, stream, block, (int)(other != ix->d_dispenser), timed, nslots, WAVE, lds_bytes, (uint64_t)bpc, p.vis_slots, p.cand_slots,
-                (uint64_t)(sorted ? plan.mode : MODE_HEAPS), p.tail_exact);
+  record_launch(ix, stream, block, (int)(other != ix->d_dispenser), timed, L.nslots, WAVE, L.lds, (uint64_t)L.bpc, p.vis_slots, p.cand_slots,
+                (uint64_t)L.mode, p.tail_exact);
   return FNV_OK;
 }
 

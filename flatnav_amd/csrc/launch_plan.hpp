@@ -1,8 +1,10 @@
 // launch_plan.hpp -- part of the gfx950 search engine: the launch planner, in plain C++ (no HIP header; compiles with g++).
 // Everything the host decides about a search launch by arithmetic alone: the row layout, the visited-table geometry and the
-// LDS layout of a query slot, the table-size ladder and its occupancy trade, the choice of kernel family and variant, the
-// shape of one launch, the layouts fnv_tune tries.  The host units (runtime.hpp) own the HIP runtime (kernel pointers, occupancy
-// queries, LDS limits, events, buffers) and hands the planner what it needs of it as a `Runtime` object:
+// LDS layout of a query slot, the table-size ladder and its occupancy trade, the choice of kernel family and variant, one
+// graph-search launch whole (shape_search: the function launch.hip launches by and the CPU test reports), K0's tile, the
+// per-slot workspace, the exhaustive scan's tiles, segments, grouping arrays, routing and byte counts, the layouts fnv_tune
+// tries.  It deals in counts and option values, never in pointers.  The host units (runtime.hpp) own the HIP runtime (kernel
+// pointers, occupancy queries, LDS limits, events, buffers) and hand the planner what it needs of it as a `Runtime` object:
 //   int occupancy(int mode, uint32_t lds)                workgroups of MODE_*'s kernel one CU holds with `lds` bytes each (0: error)
 //   const char* raise_lds_limit(int mode, uint32_t lds)  that kernel may be launched with `lds` bytes: null, or the runtime's error
 // A plan that fails returns its code and says why in `err`.
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "../../include/flatnav_hip.h"
+#include "scan_select.hpp"
 #include "search_types.h"
 
 namespace fnv_dev {
@@ -447,10 +450,26 @@ struct KernelChoice {
   bool sorted;  // the merged-beam kernel (else the two-heap kernel, or its filtered form)
   int variant;
   bool multi_round, sample = false, exploratory = false;
+  bool adaptive = false;  // nothing is pinned and "sorted_beam" = 2: the variant is for the measurements to decide (choose_kernel)
   int64_t tail_pct;
 };
-// Before any measurement: the kernel the plan prefers, whether the launch is longer than one round, the tail the option asks for.
-inline KernelChoice default_choice(const PlanInputs* ix, const LaunchPlan& plan, uint64_t nq, bool filtered) {
+// A launch of more than one round of the merged-beam kernel's resident slots (an exact tail needs a second round).
+inline bool multi_round_launch(const PlanInputs* ix, const LaunchPlan& plan, uint64_t nq) {
+  return nq > (uint64_t)plan.sbpc * (uint64_t)ix->num_cus;
+}
+// Once the variant is known: what follows from it (variant 0 is the two-heap kernel; 2-5 carry their own tail).
+inline void set_variant(KernelChoice& c, int variant) {
+  c.variant = variant;
+  c.sorted = variant != 0;
+  if (variant >= 2) c.tail_pct = kTailPct[variant];
+}
+// A pinned variant (fnv_tune's launches / "sorted_variant"): as asked when this launch can run it, else the merged-beam kernel.
+inline int pinned_variant(int pinned, bool multi_round, bool shadows_on) {
+  return variant_allowed(pinned, multi_round, true, shadows_on, true) ? pinned : 1;
+}
+// Before any measurement: the kernel the plan prefers, whether the launch is longer than one round, the tail the option asks
+// for -- or the variant that is pinned (`force_variant` >= 0: fnv_tune's launches; else "sorted_variant").
+inline KernelChoice default_choice(const PlanInputs* ix, const LaunchPlan& plan, uint64_t nq, bool filtered, int force_variant = -1) {
   // Adaptive choice ("sorted_beam" = 2): both kernels give the same answers; which one is faster depends on how often
   // equal keys force the merged-beam kernel to search a query twice (rarely on float data, often on integer-valued
   // data with wide beams) -- so it is measured: launches of at least 2048 queries are timed by the events that bracket
@@ -465,17 +484,15 @@ inline KernelChoice default_choice(const PlanInputs* ix, const LaunchPlan& plan,
   // "sorted_tail_exact_pct" = p the last p % of one round of queries skip the sorted pass (the exact search is slower but
   // never needs a second one): -15 % on the integer-valued SIFT stand-in at ef=52, +0-4 % on float data without ties --
   // so by default (-1) it is one more variant that the adaptive choice measures.
-  const uint64_t round_slots = (uint64_t)plan.sbpc * (uint64_t)ix->num_cus;
-  c.multi_round = c.sorted && nq > round_slots;
+  c.multi_round = c.sorted && multi_round_launch(ix, plan, nq);
   c.tail_pct = ix->sorted_tail_exact_pct < 0 ? 0 : ix->sorted_tail_exact_pct;
+  const int pinned = force_variant >= 0 ? force_variant : (int)ix->sorted_variant;
+  c.adaptive = c.sorted && pinned < 0 && ix->sorted_beam == 2;
+  if (c.sorted && pinned >= 0) set_variant(c, pinned_variant(pinned, c.multi_round, ix->shadow_exact != 0));
   return c;
 }
 // The adaptive choice ("sorted_beam" = 2) keeps, per tuner_key, the best time of each variant (Tuner); choose_kernel
-// (launch.hip) harvests the timings and asks the four rules below.
-// A pinned variant (fnv_tune's launches / "sorted_variant"): as asked when this launch can run it, else the merged-beam kernel.
-inline int pinned_variant(int pinned, bool multi_round, bool shadows_on) {
-  return variant_allowed(pinned, multi_round, true, shadows_on, true) ? pinned : 1;
-}
+// (launch.hip) harvests the timings of an `adaptive` choice, asks the three rules below and hands the answer to set_variant.
 // A hidden lane runs the fastest variant its owner has measured (-1: none measured); the lowest ordinal wins a tie.
 inline int lane_variant(const Tuner& t, bool multi_round, bool try_tail, bool shadows_on) {
   int best = -1;
@@ -560,6 +577,137 @@ inline LaunchShape launch_shape(const PlanInputs* ix, const LaunchPlan& plan, co
   s.n_scan = (uint32_t)((live + step - 1) / step);
   s.tail_exact = c.multi_round && sorted ? (uint32_t)std::min<uint64_t>((uint64_t)c.tail_pct * s.nslots / 100, nq) : 0u;
   return s;
+}
+
+// One graph-search launch, whole: its shape, the slots per CU and LDS bytes of the kernel `c` chose, whether it runs the DIRECT
+// form, the mode it reports -- and `p`, filled in place with that kernel's parameter block of the plan (the DIRECT layout
+// applied).  `filtered_bpc`: a filtered launch's resident slots per CU with the filtered kernel (0: the launch is not filtered).
+// The one function search_device_impl (launch.hip) and the CPU test's harness both shape a launch with.
+struct SearchLaunch : LaunchShape {
+  int bpc, mode;
+  uint32_t lds;
+  bool direct;
+};
+inline SearchLaunch shape_search(const PlanInputs* ix, const LaunchPlan& plan, const KernelChoice& c, int filtered_bpc, uint64_t nq,
+                                 int num_initializations, uint64_t live, SearchParams& p) {
+  SearchLaunch s;
+  s.bpc = c.sorted ? plan.sbpc : filtered_bpc ? filtered_bpc : plan.bpc;
+  s.lds = c.sorted ? plan.slds : plan.lds;
+  s.mode = c.sorted ? plan.mode : MODE_HEAPS;
+  static_cast<LaunchShape&>(s) = launch_shape(ix, plan, c, s.bpc, nq, num_initializations, live);
+  p = c.sorted ? plan.sorted : plan.heaps;
+  s.direct = c.sorted && s.small_launch && lay_out_direct(ix, p, &s.lds, s.bpc, s.nslots);
+  return s;
+}
+
+// K0 (entry_scan_kernel, kernels.hpp): the batch's shared entry-scan rows staged in LDS tiles of whole rows, the row stride
+// padded by 16 bytes against bank conflicts -- as many rows as 64 KB hold (at least one), behind the workgroup's staged
+// queries (SCAN_WAVES of them at a time) and its SCAN_QPB results; one workgroup per SCAN_QPB queries.
+struct EntryScanTile {
+  uint32_t stride, rows, lds, grid;
+};
+inline EntryScanTile entry_scan_tile(uint32_t row_bytes, uint32_t q_chunks, uint32_t n_scan, uint64_t nq) {
+  EntryScanTile t;
+  t.stride = row_bytes + 16;
+  t.rows = std::max<uint32_t>(1, std::min<uint32_t>(n_scan, (64u * 1024u) / t.stride));
+  t.lds = SCAN_WAVES * q_chunks * 16 + SCAN_QPB * 8 + t.rows * t.stride;
+  t.grid = (uint32_t)((nq + SCAN_QPB - 1) / SCAN_QPB);
+  return t;
+}
+
+// HBM per query slot of a launch on this index, in bytes: the visited set's bitmap, the list of ids whose bitmap words need
+// clearing, the candidates heap's spill area, the hand-over log of `log_entries` records (a plan's: log_entries_for its beam).
+struct SlotWorkspace {
+  uint64_t bitmap, ovf, spill, tielog;
+  uint64_t bytes() const { return bitmap + ovf + spill + tielog; }
+};
+inline SlotWorkspace slot_workspace(const PlanInputs* ix, uint64_t log_entries) {
+  return SlotWorkspace{(uint64_t)bitmap_words_of(ix) * 4, (uint64_t)ovf_cap_of(ix) * 4, (uint64_t)ix->spill_entries * 8, log_entries * 8};
+}
+
+// ---- exhaustive search (scan.hpp) and the scan stage of a routed filtered graph search ----------------------------
+// 32-bit words of a bitmap with one bit per node id, and the `rows` node bitmaps of a grouped launch (n_filters + 2 of them).
+inline uint64_t node_words(const PlanInputs* ix) { return (ix->capacity + 31) / 32; }
+inline size_t filter_rows_bytes(const PlanInputs* ix, uint64_t rows) { return (size_t)rows * (size_t)node_words(ix) * 4; }
+
+// How a launch of `nq` queries for K results is cut up: queries per tile (as many as a block's LDS budget holds next to their
+// result lists, at most 32), row segments (enough blocks to fill the device, at most 64 and at most what keeps the partial
+// lists within 256 MB; or what "scan_segment_rows" asks for).
+constexpr uint32_t kScanLdsBudget = 20u << 10;  // per block: eight blocks per CU = two wavefronts per SIMD
+constexpr uint32_t kScanMaxTile = 32, kScanMaxSegments = 64, kScanForcedSegments = 1024;
+constexpr uint64_t kScanPartialBudget = 256ull << 20;
+constexpr uint32_t kScanMaxLds = 160u << 10;  // one query and its list must fit a block's LDS
+struct ScanShape {
+  uint32_t tile, tiles, segments, lds;
+};
+// `filter_rows` != 0: a grouped launch over that many filter rows -- the id queue comes out of the block's LDS budget, and
+// `tiles` is the bound on the data-dependent tile count that the launch covers (scan_select.hpp, group_tile_bound).
+inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows = 0) {
+  ScanShape s;
+  const uint32_t per_query = g.q_chunks * 16u + (uint32_t)K * 8u;
+  const uint32_t queue = filter_rows ? SCAN_QUEUE_IDS * 4u : 0u;
+  s.tile = std::max(1u, std::min(kScanMaxTile, (kScanLdsBudget - queue) / per_query));
+  s.tile = (uint32_t)std::min<uint64_t>(s.tile, nq);
+  s.lds = s.tile * per_query + queue;
+  s.tiles = (uint32_t)(filter_rows ? group_tile_bound(nq, filter_rows, s.tile) : (nq + s.tile - 1) / s.tile);
+  uint64_t seg;
+  if (ix->scan_segment_rows > 0) {
+    seg = std::min<uint64_t>((live + (uint64_t)ix->scan_segment_rows - 1) / (uint64_t)ix->scan_segment_rows, kScanForcedSegments);
+  } else {
+    const uint64_t want_blocks = (uint64_t)std::max(1, ix->num_cus) * 8u;
+    seg = std::min<uint64_t>((want_blocks + s.tiles - 1) / s.tiles, std::max<uint64_t>(1, live / 1024));
+    seg = std::min<uint64_t>(seg, kScanMaxSegments);
+    seg = std::min<uint64_t>(seg, std::max<uint64_t>(1, kScanPartialBudget / (nq * (uint64_t)K * 8u)));
+  }
+  seg = std::min<uint64_t>(seg, 0x7FFFFFFFull / s.tiles);
+  s.segments = (uint32_t)std::max<uint64_t>(1, seg);
+  return s;
+}
+// The partial lists of a launch: one sorted list of K keys per (query, segment); the merge's LDS: three such lists.
+inline size_t scan_partial_bytes(uint64_t nq, const ScanShape& s, int K) { return (size_t)nq * s.segments * (size_t)K * 8; }
+inline uint32_t scan_merge_lds(uint32_t K) { return 3u * K * 8u; }
+
+// The grouping arrays of a grouped scan (scan.hpp's group_* kernels), as uint32 offsets into one buffer.
+// `routed` (the scan stage of a routed filtered graph search): nq route words and the overflow flag behind them as well.
+struct GroupArrays {
+  size_t query_row, perm, counts, cursor, row_count, slot_start, tile_start, tiles, route, bytes;
+  size_t cleared_bytes;  // counts | cursor | row_count: contiguous, zero before the launch's first kernel (one memset from `counts`)
+  GroupArrays(uint64_t nq, uint64_t rows, uint64_t tile_bound, bool routed = false) {
+    query_row = 0;
+    perm = query_row + nq;
+    counts = perm + nq;
+    cursor = counts + rows;
+    row_count = cursor + rows;
+    slot_start = row_count + rows;
+    cleared_bytes = (slot_start - counts) * 4;
+    tile_start = slot_start + rows + 1;
+    tiles = tile_start + rows + 1;
+    route = tiles + 3 * tile_bound;
+    bytes = (route + (routed ? nq + 1 : 0)) * 4;
+  }
+};
+
+// Filter routing of a filtered graph search ("filter_scan_max" / "filter_scan_on_overflow", scan_select.hpp): whether an
+// option asks for it at all ...
+inline bool filter_routing_on(const PlanInputs* ix) { return ix->filter_scan_max > 0 || ix->filter_scan_on_overflow != 0; }
+// ... whether this launch over `filter_rows` node bitmaps (0: the call has no filter) routes, and the shape of its scan stage.
+// Routing is not applied where the scan cannot take the call (K beyond its lists, rows too long for its LDS): an option
+// never makes a valid call invalid.
+struct ScanRouting {
+  bool on = false;
+  ScanShape shape{};
+};
+inline ScanRouting plan_scan_routing(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows) {
+  ScanRouting r;
+  if (filter_rows == 0 || !filter_routing_on(ix) || K > SCAN_MAX_K) return r;
+  r.shape = scan_shape(ix, g, nq, K, live, filter_rows);
+  r.on = r.shape.lds <= kScanMaxLds;
+  return r;
+}
+// HBM a routed launch takes on top of the search kernel's per-slot workspace: the node bitmaps, the grouping arrays with the
+// route words, the partial lists.
+inline size_t routed_scan_bytes(const PlanInputs* ix, uint64_t filter_rows, uint64_t nq, int K, const ScanShape& s) {
+  return filter_rows_bytes(ix, filter_rows) + GroupArrays(nq, filter_rows, s.tiles, true).bytes + scan_partial_bytes(nq, s, K);
 }
 
 // The layouts fnv_tune times for one beam width: [0] the rules' own, then its neighbours.  `base_*`: what the rules chose

@@ -30,9 +30,11 @@
 // sequential admission rule on the results.
 //
 // The launch planner -- row layout, visited-table geometry, a slot's LDS layout, table-size ladder, kernel family and variant,
-// launch shape: every decision that is arithmetic -- lives in launch_plan.hpp, free of HIP (tests/test_launch_plan.py runs
-// it on the CPU); these units own the HIP runtime around it: handles, buffers, streams and events, kernel lookup, the
-// occupancy queries and LDS limits the planner asks for, the launches and the C ABI.
+// the whole shape of a graph-search launch (shape_search), the exhaustive scan's tiles, segments, grouping arrays and routing,
+// K0's tile, the workspace's sizes: every decision that is arithmetic -- lives in launch_plan.hpp, free of HIP
+// (tests/test_launch_plan.py runs it on the CPU; tests/test_gpu_scan_shape.py holds launches against it); these units own the
+// HIP runtime around it: handles, buffers, streams and events, kernel lookup, the occupancy queries and LDS limits the planner
+// asks for, the measurements of the adaptive choice, the launches and the C ABI.
 //
 // Also theirs: incremental construction (fnv_index_write_nodes / write_links / insert_batch: Index::add,
 // include/flatnav/index/Index.h:353-378 with selectNeighbors :714-763 and connectNeighbors :765-834 as the
@@ -346,8 +348,6 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
 
 // The live nodes a launch on `ix` sees: a view (or hidden lane) follows its source's growth.
 inline uint64_t live_nodes(const fnv_index_s* ix) { return ix->parent ? ix->parent->n_nodes.load() : ix->n_nodes.load(); }
-// 32-bit words of a bitmap with one bit per node id.
-inline uint64_t node_words(const fnv_index_s* ix) { return (ix->capacity + 31) / 32; }
 // What every graph search checks of its sizes (Index.h:847-849).
 inline int check_search_sizes(int K, int ef_search, int num_initializations) {
   if (num_initializations <= 0) return fail(FNV_ERR_INVALID, "num_initializations must be greater than 0.");
@@ -366,7 +366,6 @@ wire_fn pick_connect_kernel(int dtype, int metric, int cfg, bool full);
 bool half_rows_possible(const fnv_index_s* ix);
 int check_status(int32_t st, const char* advice = "raise the spill_entries option");
 int check_device_status(fnv_index_s* ix, const char* advice = "raise the spill_entries option");
-size_t filter_rows_bytes(const fnv_index_s* ix, const SearchFilter& f);
 size_t routed_workspace_bytes(fnv_index_s* ix, const SearchFilter& f, uint64_t nq, int K);
 int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K, int ef_search, int num_initializations,
                        const SearchOutputs& out, void* hip_stream, const SearchOptions& opt = SearchOptions());

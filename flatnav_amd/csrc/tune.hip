@@ -210,7 +210,7 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
     float t1 = -1.f, t4 = -1.f;
     int r = time_variant(1, 4, &t1);
     if (r) return r;
-    const bool multi = nq > (uint64_t)ix->plan.sbpc * (uint64_t)ix->num_cus;
+    const bool multi = multi_round_launch(ix, ix->plan, nq);
     if (multi && ix->sorted_tail_exact_pct < 0 && (r = time_variant(3, 4, &t4)) != FNV_OK) return r;
     *out = (t4 > 0.f && t4 < t1) ? t4 : t1;
     if (tune_log)
@@ -284,7 +284,7 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
   HIP_TRY(hipStreamSynchronize(ix->stream));
 
   // ---- 2. the kernel variant on that layout --------------------------------------------------------------------------
-  const bool multi_round = nq > (uint64_t)ix->plan.sbpc * (uint64_t)ix->num_cus;
+  const bool multi_round = multi_round_launch(ix, ix->plan, nq);
   Tuner t;
   for (int v = 0; v < kNumVariants; v++) {
     if (!variant_allowed(v, multi_round, ix->sorted_tail_exact_pct < 0, ix->shadow_exact != 0)) continue;

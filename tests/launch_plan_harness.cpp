@@ -47,7 +47,8 @@ const char* lph_option_columns() { return LPH_OPTIONS(LPH_NAME); }
 const char* lph_param_columns() { return LPH_PARAMS(LPH_NAME); }
 #undef LPH_NAME
 // (the heaps block, then the sorted block, follow these)
-const char* lph_plan_columns() { return "rc,mode,cfg,full,row_bytes,tail_bytes,lds,bpc,slds,sbpc,"; }
+// (ws_*: slot_workspace for the plan's beam -- bytes per query slot, by part and in all)
+const char* lph_plan_columns() { return "rc,mode,cfg,full,row_bytes,tail_bytes,lds,bpc,slds,sbpc,ws_bitmap,ws_ovf,ws_spill,ws_tielog,ws_bytes,"; }
 // (the launch's parameter block follows these)
 const char* lph_shape_columns() {
   return "sorted,variant,multi_round,small_launch,shadow,nslots,tail_shadows,max_slots,tail_exact,scan_step,n_scan,direct,lds,bpc,mode,";
@@ -75,8 +76,10 @@ void* lph_plan(int dtype, uint32_t dim, uint32_t M, uint64_t capacity, uint64_t 
   std::string err;
   h->rc = plan_launch(&ix, B, K, LayoutChoice(), rt, err, h->plan);
   const LaunchPlan& p = h->plan;
+  const SlotWorkspace ws = slot_workspace(&ix, log_entries_for(&ix, B));
   for (int64_t v : {(int64_t)h->rc, (int64_t)p.mode, (int64_t)p.cfg, (int64_t)p.full, (int64_t)ix.row_bytes, (int64_t)ix.tail_bytes,
-                    (int64_t)p.lds, (int64_t)p.bpc, (int64_t)p.slds, (int64_t)p.sbpc})
+                    (int64_t)p.lds, (int64_t)p.bpc, (int64_t)p.slds, (int64_t)p.sbpc, (int64_t)ws.bitmap, (int64_t)ws.ovf,
+                    (int64_t)ws.spill, (int64_t)ws.tielog, (int64_t)ws.bytes()})
     *out++ = v;
   out = put_params(out, p.heaps);
   put_params(out, p.sorted);
@@ -84,28 +87,17 @@ void* lph_plan(int dtype, uint32_t dim, uint32_t M, uint64_t capacity, uint64_t 
 }
 void lph_free(void* plan) { delete (Plan*)plan; }
 
-// One unfiltered launch of `nq` queries over `live` nodes on that plan, the way search_device_impl shapes it: the plan's
-// default kernel choice, or `pinned` (>= 0: a variant, as "sorted_variant" pins it).  Fills `out` (lph_shape_columns).
-// The lines between the planner's calls are a TWIN of glue that stays in flatnav_amd/csrc/launch.hip -- choose_kernel's
-// pinned branch with its follow-up (sorted, tail_pct), and search_device_impl's choice of bpc / LDS bytes and its DIRECT
-// condition: what this returns is the planner under this copy, and an edit of either side belongs in the other.
+// One unfiltered launch of `nq` queries over `live` nodes on that plan, shaped by the two planner calls search_device_impl
+// shapes it with: the plan's default kernel choice, or `pinned` (>= 0: a variant, as fnv_tune pins it).  Fills `out`
+// (lph_shape_columns).
 void lph_launch(const void* plan, uint64_t nq, int num_initializations, uint64_t live, int pinned, int64_t* out) {
   const Plan* h = (const Plan*)plan;
-  const PlanInputs* ix = &h->ix;
-  KernelChoice c = default_choice(ix, h->plan, nq, false);
-  if (c.sorted && pinned >= 0) {
-    c.variant = pinned_variant(pinned, c.multi_round, ix->shadow_exact != 0);
-    c.sorted = c.variant != 0;
-    if (c.variant >= 2) c.tail_pct = kTailPct[c.variant];
-  }
-  const int bpc = c.sorted ? h->plan.sbpc : h->plan.bpc;
-  uint32_t lds = c.sorted ? h->plan.slds : h->plan.lds;
-  const LaunchShape s = launch_shape(ix, h->plan, c, bpc, nq, num_initializations, live);
-  SearchParams p = c.sorted ? h->plan.sorted : h->plan.heaps;
-  const bool direct = c.sorted && s.small_launch && lay_out_direct(ix, p, &lds, bpc, s.nslots);
+  const KernelChoice c = default_choice(&h->ix, h->plan, nq, false, pinned);
+  SearchParams p;
+  const SearchLaunch s = shape_search(&h->ix, h->plan, c, 0, nq, num_initializations, live, p);
   for (int64_t v : {(int64_t)c.sorted, (int64_t)c.variant, (int64_t)c.multi_round, (int64_t)s.small_launch, (int64_t)s.shadow,
                     (int64_t)s.nslots, (int64_t)s.tail_shadows, (int64_t)s.max_slots, (int64_t)s.tail_exact, (int64_t)s.scan_step,
-                    (int64_t)s.n_scan, (int64_t)direct, (int64_t)lds, (int64_t)bpc, (int64_t)(c.sorted ? h->plan.mode : MODE_HEAPS)})
+                    (int64_t)s.n_scan, (int64_t)s.direct, (int64_t)s.lds, (int64_t)s.bpc, (int64_t)s.mode})
     *out++ = v;
   put_params(out, p);
 }
@@ -126,6 +118,39 @@ void lph_sweep(const int64_t* cases, int64_t n, int64_t case_width, const int64_
     }
     lph_free(h);
   }
+}
+
+// The exhaustive scan's shape and the routing decision.  Rows of `cases`: dtype, dim, capacity, num_cus, scan_segment_rows,
+// filter_scan_max, filter_scan_on_overflow, nq, K, live, filter_rows; rows of `out` (lph_scan_columns): scan_shape's fields for
+// that call, the row's q_chunks, the partial lists' bytes, the merge's LDS, and whether plan_scan_routing routes it.
+const char* lph_scan_columns() { return "tile,tiles,segments,lds,q_chunks,partial_bytes,merge_lds,routed,"; }
+void lph_scan_sweep(const int64_t* cases, int64_t n, int64_t* out) {
+  for (int64_t i = 0; i < n; i++, cases += 11) {
+    PlanInputs ix;
+    ix.dtype = (int)cases[0], ix.dim = (uint32_t)cases[1], ix.capacity = (uint64_t)cases[2], ix.num_cus = (int)cases[3];
+    ix.scan_segment_rows = cases[4], ix.filter_scan_max = cases[5], ix.filter_scan_on_overflow = cases[6];
+    const RowLayout lay = row_layout(ix.dim, ix.dtype, ix.capacity);
+    ix.row_bytes = lay.row_bytes, ix.tail_bytes = lay.tail_bytes;
+    const RowGeometry g = row_geometry(&ix);
+    const uint64_t nq = (uint64_t)cases[7], live = (uint64_t)cases[9], rows = (uint64_t)cases[10];
+    const ScanShape s = scan_shape(&ix, g, nq, (int)cases[8], live, rows);
+    for (int64_t v : {(int64_t)s.tile, (int64_t)s.tiles, (int64_t)s.segments, (int64_t)s.lds, (int64_t)g.q_chunks,
+                      (int64_t)scan_partial_bytes(nq, s, (int)cases[8]), (int64_t)scan_merge_lds((uint32_t)cases[8]),
+                      (int64_t)plan_scan_routing(&ix, g, nq, (int)cases[8], live, rows).on})
+      *out++ = v;
+  }
+}
+// GroupArrays(nq, rows, tile_bound, routed): its ten offsets in declaration order, then cleared_bytes.
+void lph_group_arrays(uint64_t nq, uint64_t rows, uint64_t tile_bound, int routed, int64_t* out) {
+  const GroupArrays ga(nq, rows, tile_bound, routed != 0);
+  for (size_t v : {ga.query_row, ga.perm, ga.counts, ga.cursor, ga.row_count, ga.slot_start, ga.tile_start, ga.tiles, ga.route, ga.bytes,
+                   ga.cleared_bytes})
+    *out++ = (int64_t)v;
+}
+// K0's tile (entry_scan_tile): stride, rows, lds, grid.
+void lph_entry_scan_tile(uint32_t row_bytes, uint32_t q_chunks, uint32_t n_scan, uint64_t nq, int64_t* out) {
+  const EntryScanTile t = entry_scan_tile(row_bytes, q_chunks, n_scan, nq);
+  for (int64_t v : {(int64_t)t.stride, (int64_t)t.rows, (int64_t)t.lds, (int64_t)t.grid}) *out++ = v;
 }
 
 // The variant rules.  which: 0 pinned_variant(pinned), 1 lane_variant, 2 owner_next_sample, 3 owner_final_variant.

@@ -27,6 +27,7 @@ SRC = os.path.join(ROOT, "tests", "launch_plan_harness.cpp")
 F32, U8, F16 = 9, 0, 8  # FNV_DTYPE_* (include/flatnav_hip.h)
 FNV_ERR_INVALID = 1
 WAVE, OVF_LIST, STASH = 64, 30, 64
+SCAN_WAVES, SCAN_QPB, SCAN_QUEUE_IDS = 4, 32, 256  # (csrc/search_types.h, csrc/scan_select.hpp)
 MODE_HEAPS, MODE_MERGED_REGS, MODE_MERGED_LDS = 0, 1, 2
 LDS_PER_CU, GRANULE = 163840, 1280
 NUM_CUS, M, K, N_INIT = 256, 16, 10, 100
@@ -68,6 +69,10 @@ def lib() -> C.CDLL:
         L.lph_variant.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.lph_slots_per_cu.argtypes = [C.c_uint32]
         L.lph_tune_candidates.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_int]
+        L.lph_scan_columns.restype = C.c_char_p
+        L.lph_scan_sweep.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.lph_group_arrays.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+        L.lph_entry_scan_tile.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -320,6 +325,117 @@ def test_exact_tails_and_tail_shadows_of_pinned_variants():
                 assert s["sorted"] == (s["variant"] != 0)
         finally:
             L.lph_free(h)
+
+
+SCAN_CASE = ("dtype", "dim", "capacity", "num_cus", "scan_segment_rows", "filter_scan_max", "filter_scan_on_overflow", "nq", "K", "live",
+             "filter_rows")
+
+
+def scan_shapes(cases) -> Table:
+    """Rows of SCAN_CASE -> the exhaustive scan's shape and the routing decision for each (lph_scan_columns), the case's own
+    fields next to them."""
+    cases = np.ascontiguousarray(cases, np.int64).reshape(-1, len(SCAN_CASE))
+    cols = _names(lib().lph_scan_columns())
+    out = np.empty((len(cases), len(cols)), np.int64)
+    lib().lph_scan_sweep(cases.ctypes.data, len(cases), out.ctypes.data)
+    return Table(out, cols, {n: cases[:, i] for i, n in enumerate(SCAN_CASE)})
+
+
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def group_tile_bound(nq, rows, tile):
+    """scan_select.hpp's bound on a grouped scan's tiles: ceil(nq / tile) + min(rows, nq), and never more than nq."""
+    return np.minimum(ceil_div(nq, tile) + np.minimum(rows, nq), nq)
+
+
+def test_scan_shape_and_routing():
+    # scan_shape's own comment: queries per tile as the block's LDS budget (20 KB, less the grouped scan's id queue) holds them,
+    # at most 32; segments to fill the device, at most 64, at most live / 1024, partial lists within 256 MB -- or what
+    # "scan_segment_rows" asks for, at most 1024; plan_scan_routing: not where the scan cannot take the call
+    grid = itertools.product(ROWS + [(F32, 40000)], (1, 31, 32, 33, 1000, 100000, 2**31 - 1), (1, 10, 1024), (0, 1, 1023, 1024, 10**6, 2**31 - 1),
+                             (0, 2, 3, 1002, 2**31 + 1), (0, 1, 4096), ((0, 0), (5, 0), (0, 1)))
+    s = scan_shapes([[dt, dim, max(live, 1), NUM_CUS, seg_rows, scan_max, on_ovf, nq, K_, live, frows]
+                     for (dt, dim), nq, K_, live, frows, seg_rows, (scan_max, on_ovf) in grid])
+    assert len(s) == 13 * 7 * 3 * 6 * 5 * 3 * 3
+    nq, K_, live, frows, seg_rows = s["nq"], s["K"], s["live"], s["filter_rows"], s["scan_segment_rows"]
+    tile, tiles, segments, lds = s["tile"], s["tiles"], s["segments"], s["lds"]
+    grouped = frows > 0
+    assert ((1 <= tile) & (tile <= np.minimum(32, nq))).all()
+    assert (lds == tile * (s["q_chunks"] * 16 + K_ * 8) + np.where(grouped, SCAN_QUEUE_IDS * 4, 0)).all()
+    assert (lds[tile > 1] <= 20 << 10).all()
+    assert (tiles == np.where(grouped, group_tile_bound(nq, frows, tile), ceil_div(nq, tile))).all()
+    assert (segments >= 1).all() and (tiles * segments <= 2**31 - 1).all()
+    auto = seg_rows == 0
+    assert (segments[auto] <= 64).all() and (segments[auto] <= np.maximum(1, live[auto] // 1024)).all()
+    assert ((segments == 1) | (nq * segments * K_ * 8 <= 256 << 20))[auto].all()
+    forced = ~auto
+    assert (segments[forced] <= 1024).all() and (segments[forced] <= np.maximum(1, ceil_div(live[forced], seg_rows[forced]))).all()
+    assert (auto & (segments > 1)).any() and (forced & (segments > 1)).any()
+    assert (s["partial_bytes"] == nq * segments * K_ * 8).all() and (s["merge_lds"] == 3 * K_ * 8).all()
+    # routing is off exactly when both options are off, or K > 1024, or the scan's LDS exceeds a block's 160 KB (and without a filter)
+    options_off = (s["filter_scan_max"] <= 0) & (s["filter_scan_on_overflow"] == 0)
+    too_long = lds > 160 << 10
+    assert too_long.any() and (~too_long).any()  # the refusal is reached
+    assert ((s["routed"] == 0) == (options_off | too_long | ~grouped)).all()
+    wide = scan_shapes([[F32, 128, 4096, NUM_CUS, 0, 5, 1, 100, K_, 4096, 3] for K_ in (1024, 1025)])
+    assert wide["routed"].tolist() == [1, 0]
+
+
+def test_group_arrays():
+    # GroupArrays' own comment: query_row | perm | counts | cursor | row_count | slot_start | tile_start | tiles [| route], as
+    # uint32 offsets; counts | cursor | row_count are the prefix one memset clears
+    names = ("query_row", "perm", "counts", "cursor", "row_count", "slot_start", "tile_start", "tiles", "route", "bytes", "cleared_bytes")
+    out = np.empty(len(names), np.int64)
+    for nq, rows, routed in itertools.product((1, 33, 100000), (0, 3, 1002), (0, 1)):
+        bound = int(group_tile_bound(nq, rows, 32))
+        lib().lph_group_arrays(nq, rows, bound, routed, out.ctypes.data)
+        ga = dict(zip(names, out.tolist()))
+        sizes = [nq, nq, rows, rows, rows, rows + 1, rows + 1, 3 * bound] + ([nq + 1] if routed else [])
+        starts = [ga[n] for n in names[:9]]
+        end = 0
+        for start, size in zip(starts, sizes):  # in the documented order, each where the one before ends: disjoint
+            assert start == end
+            end = start + size
+        assert starts[8] == ga["tiles"] + 3 * bound  # (unrouted: the route words' offset is the end)
+        assert ga["bytes"] == 4 * end
+        assert ga["cursor"] == ga["counts"] + rows and ga["row_count"] == ga["cursor"] + rows and ga["slot_start"] == ga["row_count"] + rows
+        assert ga["cleared_bytes"] == 4 * (ga["slot_start"] - ga["counts"]) == 4 * 3 * rows
+
+
+def test_entry_scan_tile():
+    # entry_scan_tile's own comment: whole rows 16 bytes apart, as many as 64 KB hold (at least one), behind SCAN_WAVES staged
+    # queries and SCAN_QPB results of 8 bytes
+    L = lib()
+    _, plan_cols, _ = columns()
+    opts = np.array(option_row({}), np.int64)
+    out = np.empty(4, np.int64)
+    several = False
+    for dt, dim in ROWS + [(F32, 40000)]:
+        plan = np.empty(len(plan_cols), np.int64)
+        L.lph_free(L.lph_plan(dt, dim, M, 4096, 0, NUM_CUS, opts.ctypes.data, 52, K, 16, plan.ctypes.data))
+        p = dict(zip(plan_cols, plan.tolist()))
+        row_bytes, q_chunks = p["row_bytes"], p["heaps.q_chunks"]
+        for n_scan, nq in itertools.product((1, 2, 100, 4096, 2**31 - 1), (1, 32, 33, 100000)):
+            L.lph_entry_scan_tile(row_bytes, q_chunks, n_scan, nq, out.ctypes.data)
+            stride, rows, lds, grid = out.tolist()
+            assert stride == row_bytes + 16 and 1 <= rows <= n_scan
+            assert rows * stride <= 64 << 10 or rows == 1
+            assert lds == SCAN_WAVES * q_chunks * 16 + SCAN_QPB * 8 + rows * stride
+            assert grid == ceil_div(nq, SCAN_QPB)
+            several |= 1 < rows < n_scan
+    assert several
+
+
+def test_slot_workspace(sweep):
+    # slot_workspace: per query slot, what the plan's parameter blocks tell the kernels about each area
+    _, plan, _ = sweep
+    assert (plan["ws_bitmap"] == plan["heaps.bitmap_words"] * 4).all() and (plan["ws_ovf"] == plan["heaps.ovf_cap"] * 4).all()
+    assert (plan["ws_spill"] == plan["heaps.spill_entries"] * 8).all() and (plan["ws_tielog"] == plan["heaps.log_entries"] * 8).all()
+    merged = plan["mode"] != MODE_HEAPS
+    assert (plan["sorted.log_entries"][merged] == plan["heaps.log_entries"][merged]).all()
+    assert (plan["ws_bytes"] == plan["ws_bitmap"] + plan["ws_ovf"] + plan["ws_spill"] + plan["ws_tielog"]).all()
 
 
 def test_row_layouts_the_comments_state():
