@@ -126,13 +126,16 @@ struct Dist<f32h, METRIC> {
 // path's f32 arithmetic on the widened values -- nothing is ever rounded to f16.  L2: one v_fma_mix_f32 per element gives
 // fma(x, 1.0, -y) = the f32 difference of the widened operands (one rounding, as v_sub_f32 of the converted values), then
 // v_pk_fma_f32 squares and accumulates: 8 + 4 VALU per chunk instead of 16 conversions + 4 v_pk_add_f32 + 4 v_pk_fma_f32
-// (hipcc does not form the mixed instruction from fpext + fsub by itself).  IP: v_dot2_f32_f16 (products of two binary16
-// values are exact in f32), 4 per chunk into two accumulators.
+// (hipcc does not form the mixed instruction from fpext + fsub by itself).  IP: one v_fma_mix_f32 per element, both operands
+// widened in the instruction: fma(x, y, acc), even elements into acc.x and odd ones into acc.y, 8 VALU per chunk.
+// NOT v_dot2_f32_f16, which this path used at first (4 per chunk).  Read off an MI355X (profiles/distance_bits.md), that
+// instruction keeps binary16 subnormals but is neither the correctly rounded a0*b0 + a1*b1 + c nor any chain of fused
+// multiply-adds: normal operands miss the exact sum by one to four ulps, and rows with subnormal elements left the forward
+// error bound of f32 arithmetic by up to 2.7 x.  The per-element form is the arithmetic tests/distance_model_harness.cpp states.
 template <int METRIC>
 struct Dist<_Float16, METRIC> {
   typedef f32x2 acc_t;
   typedef int qacc_t;  // unused for float rows
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   static __device__ __forceinline__ f32x2 zero() { return f32x2{0.f, 0.f}; }
   static __device__ __forceinline__ int qzero() { return 0; }
   static __device__ __forceinline__ int qchunk(int q, const uint4&) { return q; }
@@ -143,8 +146,12 @@ struct Dist<_Float16, METRIC> {
     asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(t.y) : "v"(x), "v"(y));
     return t;
   }
-  static __device__ __forceinline__ float dot(uint32_t x, uint32_t y, float c) {
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, x), __builtin_bit_cast(h2, y), c, false);
+  // {fma(lo(x), lo(y), acc.x), fma(hi(x), hi(y), acc.y)} from two packed pairs
+  static __device__ __forceinline__ f32x2 mul_add(uint32_t x, uint32_t y, f32x2 acc) {
+    f32x2 r;
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,1,0]" : "=v"(r.x) : "v"(x), "v"(y), "v"(acc.x));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "=v"(r.y) : "v"(x), "v"(y), "v"(acc.y));
+    return r;
   }
   static __device__ __forceinline__ f32x2 chunk(f32x2 acc, const uint4& x, const uint4& y) {
     if (METRIC == FNV_METRIC_L2) {
@@ -154,10 +161,10 @@ struct Dist<_Float16, METRIC> {
       acc = __builtin_elementwise_fma(t2, t2, acc);
       acc = __builtin_elementwise_fma(t3, t3, acc);
     } else {
-      acc.x = dot(x.x, y.x, acc.x);
-      acc.y = dot(x.y, y.y, acc.y);
-      acc.x = dot(x.z, y.z, acc.x);
-      acc.y = dot(x.w, y.w, acc.y);
+      acc = mul_add(x.x, y.x, acc);
+      acc = mul_add(x.y, y.y, acc);
+      acc = mul_add(x.z, y.z, acc);
+      acc = mul_add(x.w, y.w, acc);
     }
     return acc;
   }

@@ -1,10 +1,10 @@
 // half_rows_harness.cpp -- the half-width mirror's rules (flatnav_amd/csrc/half_rows.hpp) on the CPU, for tests/test_half_rows.py:
 // compiled with g++ as a shared library (ctypes), and once as a stand-alone program (-DHRH_MAIN, with the host sanitizers).
 //
-// Besides thin wrappers of the header it holds a plain-C++ EMULATION of what the 64 lanes of a wave compute for one vector
-// (csrc/distance.hpp): the float32 FULL path of batch_dists with Dist<float>, and the mirror path with Dist<f32h> reading
-// 16-byte units -- each lane's chunks in its order, std::fmaf where the kernels use fused multiply-adds, then the pairing of
-// group_sum.  Compile with -ffp-contract=off: nothing but the written fmaf may fuse.
+// Besides thin wrappers of the header it exports the plain-C++ EMULATION of what the 64 lanes of a wave compute for one vector
+// (csrc/distance.hpp), which lives in tests/distance_model_harness.cpp: the float32 FULL path of batch_dists with Dist<float>,
+// and the mirror path with Dist<f32h> reading 16-byte units -- each lane's chunks in its order, std::fmaf where the kernels use
+// fused multiply-adds, then the pairing of group_sum.  Compile with -ffp-contract=off: nothing but the written fmaf may fuse.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -16,55 +16,11 @@
 
 #include "../flatnav_amd/csrc/half_rows.hpp"
 #include "../flatnav_amd/csrc/launch_plan.hpp"
+#include "distance_model_harness.cpp"  // hrh_dist_f32, hrh_dist_half: the lane-by-lane emulations
 
 using namespace fnv_dev;
 
-namespace {
-
-float as_float(uint32_t b) {
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
-
-struct Acc {
-  float x = 0.f, y = 0.f;
-};
-// Dist<float>::chunk / Dist<f32h>::half_chunk on widened values: x = one query chunk, y = one row chunk
-void chunk(Acc& a, const float* x, const float* y, int metric) {
-  if (metric == FNV_METRIC_L2) {
-    const float t0x = x[0] - y[0], t0y = x[1] - y[1], t1x = x[2] - y[2], t1y = x[3] - y[3];
-    a.x = std::fmaf(t0x, t0x, a.x);
-    a.y = std::fmaf(t0y, t0y, a.y);
-    a.x = std::fmaf(t1x, t1x, a.x);
-    a.y = std::fmaf(t1y, t1y, a.y);
-  } else {
-    a.x = std::fmaf(x[0], y[0], a.x);
-    a.y = std::fmaf(x[1], y[1], a.y);
-    a.x = std::fmaf(x[2], y[2], a.x);
-    a.y = std::fmaf(x[3], y[3], a.y);
-  }
-}
-// group_sum<G>: every step adds the partner's value of the step before
-float group_sum(std::vector<float> v, int G) {
-  auto step = [&](auto partner) {
-    std::vector<float> w(v.size());
-    for (int i = 0; i < G; i++) w[i] = v[i] + v[partner(i)];
-    v = w;
-  };
-  step([](int i) { return i ^ 1; });
-  step([](int i) { return i ^ 2; });
-  if (G >= 8) step([](int i) { return (i & ~7) | (7 - (i & 7)); });
-  if (G >= 16) step([](int i) { return (i & ~15) | (15 - (i & 15)); });
-  if (G >= 32) step([](int i) { return i ^ 16; });
-  if (G >= 64) step([](int i) { return i ^ 32; });
-  for (int i = 1; i < G; i++)
-    if (memcmp(&v[i], &v[0], 4) != 0) return NAN;  // (all lanes of a group end with the same bits)
-  return v[0];
-}
-float finish(float s, int metric) { return metric == FNV_METRIC_L2 ? s : 1.0f - s; }
-
-}  // namespace
+using dm::as_float;
 
 extern "C" {
 
@@ -100,39 +56,6 @@ void hrh_round_trip(const uint32_t* bits, uint64_t n, uint32_t* back, uint8_t* l
 }
 int hrh_convert_row(const uint32_t* row, uint16_t* mirror, uint32_t nchunks, uint32_t G, uint32_t CU) {
   return half_convert_row(row, mirror, nchunks, G, CU) ? 1 : 0;
-}
-
-// The float32 kernel: lane g takes chunks c0 + cu * G + g in the order of cu, span after span.
-float hrh_dist_f32(const float* q, const float* row, uint32_t nchunks, int G, int CU, int metric) {
-  std::vector<float> lane(G);
-  for (int g = 0; g < G; g++) {
-    Acc a;
-    for (uint32_t c0 = 0; c0 < nchunks; c0 += G * CU)
-      for (int cu = 0; cu < CU; cu++) {
-        const uint32_t c = c0 + cu * G + g;
-        chunk(a, q + 4 * c, row + 4 * c, metric);
-      }
-    lane[g] = a.x + a.y;
-  }
-  return finish(group_sum(lane, G), metric);
-}
-// The mirror kernel: lane g loads units c0 / 2 + j * G + g and multiplies the first four values with query chunk
-// c0 + (2j) * G + g, the last four with chunk c0 + (2j + 1) * G + g.  `swap`: the two halves of every unit change places.
-float hrh_dist_half(const float* q, const uint16_t* mirror, uint32_t nchunks, int G, int CU, int metric, int swap) {
-  std::vector<float> lane(G);
-  for (int g = 0; g < G; g++) {
-    Acc a;
-    for (uint32_t c0 = 0; c0 < nchunks; c0 += G * CU)
-      for (int j = 0; j < CU / 2; j++) {
-        const uint16_t* u = mirror + (size_t)(c0 / 2 + j * G + g) * 8;
-        float y[8];
-        for (int k = 0; k < 8; k++) y[k] = as_float(half_bits_widen(u[swap ? (k + 4) % 8 : k]));
-        chunk(a, q + 4 * (c0 + (2 * j) * G + g), y, metric);
-        chunk(a, q + 4 * (c0 + (2 * j + 1) * G + g), y + 4, metric);
-      }
-    lane[g] = a.x + a.y;
-  }
-  return finish(group_sum(lane, G), metric);
 }
 
 }  // extern "C"

@@ -55,8 +55,8 @@ def name_of(G, CU, full, tail_chunks, multi_span):
     return "%dx%d-%s%s" % (G, CU, form, "-spans" if multi_span else "")
 
 
-def geometry(dtype: str, dims, capacity: int = N_ROWS):
-    """Per dim: (cfg, full, row_bytes, tail_bytes) as the planner's harness returns them, at the default layout."""
+def _plans(dtype: str, dims, capacity: int):
+    """The planner harness's plan table over `dims`, at the default layout."""
     _, plan_cols, shape_cols = tlp.columns()
     dims = np.asarray(dims, np.int64).reshape(-1)
     opts = tlp.option_row({})
@@ -70,7 +70,26 @@ def geometry(dtype: str, dims, capacity: int = N_ROWS):
                             none.ctypes.data, len(shape_cols))
     t = tlp.Table(plans, plan_cols)
     assert (t["rc"] == 0).all(), "the planner refuses a row width"
+    return t
+
+
+def geometry(dtype: str, dims, capacity: int = N_ROWS):
+    """Per dim: (cfg, full, row_bytes, tail_bytes) as the planner's harness returns them, at the default layout."""
+    t = _plans(dtype, dims, capacity)
     return t["cfg"], t["full"], t["row_bytes"], t["tail_bytes"]
+
+
+def walk_of_row(dtype: str, dim: int, capacity: int = N_ROWS):
+    """How the kernels walk a row of this dim, in the planner's words (row_geometry, csrc/launch_plan.hpp): a dict of cfg, G, CU,
+    full, tail_chunks, nchunks (of the main table's row) and q_chunks (of the staged query).  tests/distance_model.py takes its
+    geometry from here and restates no layout rule."""
+    t = _plans(dtype, [dim], capacity)
+    cfg = int(t["cfg"][0])
+    G, CU = cfgs()[cfg]
+    out = dict(cfg=cfg, G=G, CU=CU, full=bool(t["full"][0]), tail_chunks=int(t["heaps.tail_chunks"][0]), nchunks=int(t["heaps.nchunks"][0]),
+               q_chunks=int(t["heaps.q_chunks"][0]))
+    assert out["nchunks"] * 16 == t["row_bytes"][0] and out["tail_chunks"] * 16 == t["tail_bytes"][0], (dtype, dim)
+    return out
 
 
 def keys_of(dtype: str, dims, capacity: int = N_ROWS):
