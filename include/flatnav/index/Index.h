@@ -9,7 +9,9 @@
 //   * search() and searchBatch() never run on the CPU.  The node store is mirrored to one GPU's
 //     HBM through the C ABI (flatnav_hip.h: fnv_index_upload) and every query is answered by the
 //     gfx950 beam-search kernel (fnv_search_batch).  If the device library or a GPU is missing the
-//     call throws -- there is no CPU fallback.
+//     call throws -- there is no CPU fallback.  The mirror -- what is shipped when, recovery from a
+//     failed write, replicas on further GPUs -- is flatnav/index/DeviceMirror.h; this header tells it
+//     what the host changed and asks it for a sync before each search.
 //   * Batched search is a first-class call (searchBatch): the reference loops Index::search over
 //     query rows with executeInParallel (bindings.cpp:198-211); here the batch is one kernel launch.
 //   * Index construction (add) stays on the host in this round.  It uses flat-array binary heaps
@@ -22,8 +24,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -38,6 +38,7 @@
 #include <vector>
 
 #include <flatnav/distances/DistanceInterface.h>
+#include <flatnav/index/DeviceMirror.h>
 #include <flatnav/util/BinaryArchive.h>
 #include <flatnav/util/Datatype.h>
 #include <flatnav/util/Multithreading.h>
@@ -52,14 +53,6 @@ using flatnav::distances::MetricType;
 using flatnav::util::DataType;
 
 namespace detail {
-
-// Maps a C-ABI status to the exception the reference throws at the same point.
-inline void throwOnDeviceError(int rc) {
-  if (rc == FNV_OK) return;
-  std::string msg = fnv_last_error();
-  if (rc == FNV_ERR_INVALID) throw std::invalid_argument(msg);
-  throw std::runtime_error(msg);
-}
 
 // Growable array of heap entries with the get/set face StlExact.h expects.
 struct EntryArray {
@@ -113,38 +106,6 @@ struct NodeGuard {
   ~NodeGuard() { locks.unlock(node); }
 };
 
-// Which link rows the host builder has changed since the device mirror was last brought up to date (one byte
-// per node, set from any thread), so that the next search ships those rows instead of the whole index.
-class DirtyRows {
-  std::unique_ptr<std::atomic<uint8_t>[]> _flags;
-  std::atomic<uint64_t> _count{0};
-  size_t _n = 0;
-
- public:
-  void reset(size_t n) {
-    _flags.reset(new std::atomic<uint8_t>[n]);
-    for (size_t i = 0; i < n; ++i) _flags[i].store(0, std::memory_order_relaxed);
-    _count.store(0);
-    _n = n;
-  }
-  void mark(uint32_t node) {
-    if (!_flags[node].exchange(1, std::memory_order_relaxed)) _count.fetch_add(1, std::memory_order_relaxed);
-  }
-  uint64_t count() const { return _count.load(); }
-  // ids < limit that are marked, ascending; clears every mark
-  std::vector<uint32_t> drain(size_t limit) {
-    std::vector<uint32_t> ids;
-    if (_count.load() != 0)
-      for (size_t i = 0; i < _n; ++i)
-        if (_flags[i].load(std::memory_order_relaxed)) {
-          _flags[i].store(0, std::memory_order_relaxed);
-          if (i < limit) ids.push_back(static_cast<uint32_t>(i));
-        }
-    _count.store(0);
-    return ids;
-  }
-};
-
 // Per-thread working memory of the host builder.
 struct BuildScratch {
   std::vector<uint32_t> stamp;  // visited epoch per node
@@ -179,12 +140,12 @@ class Index {
   size_t _node_size_bytes = 0;  // [data][M links][label], as in the reference (Index.h:61-63, 176)
   size_t _max_node_count = 0;
   size_t _cur_num_nodes = 0;
-  std::unique_ptr<DistanceInterface<dist_t>> _distance;
+  std::unique_ptr<dist_t> _distance;  // (held as what it is: DistanceInterface has no virtual destructor to delete it through)
   uint32_t _num_threads = 1;
   bool _collect_stats = false;
   DataType _data_type = DataType::float32;
-  mutable std::atomic<uint64_t> _distance_computations{0};
-  mutable std::atomic<uint64_t> _metric_hops{0};
+  std::atomic<uint64_t> _distance_computations{0};
+  std::atomic<uint64_t> _metric_hops{0};
 
   // host builder state
   std::mutex _index_data_guard;
@@ -192,23 +153,8 @@ class Index {
   std::mutex _scratch_guard;
   std::vector<std::unique_ptr<detail::BuildScratch>> _scratch_pool;
 
-  // device mirror
-  mutable std::mutex _device_guard;
-  mutable fnv_index_t _device_index = nullptr;
-  mutable bool _device_stale = true;       // the mirror misses host-side changes (new nodes and / or dirty link rows)
-  mutable bool _device_rebuild = true;     // ... and they are not tracked: the whole store must be shipped again
-  mutable size_t _device_capacity = 0;     // rows allocated on the device
-  int64_t _filter_scan_max = 0;            // setFilterRouting: re-applied whenever the mirror is created anew
-  bool _filter_scan_on_overflow = false;
-  mutable size_t _device_synced_nodes = 0; // nodes [0, this) have their records on the device
-  mutable detail::DirtyRows _dirty_rows;   // link rows of synced nodes that changed since
-  int _device_ordinal = 0;
-  // several GPUs: the mirror on _device_ordinal is the primary; replicas of it live on the other devices of
-  // _device_list (filled by peer copies, refreshed whenever the primary changes); batches are sharded over all of them
-  mutable std::vector<int> _device_list;   // empty: not decided yet (FLATNAV_DEVICES, else the primary GPU alone)
-  mutable bool _device_list_defaulted = false;  // FLATNAV_DEVICES=all: "every visible GPU", whatever that turns out to be
-  mutable std::vector<fnv_index_t> _replicas;
-  mutable bool _replicas_stale = true;
+  // the copy in HBM and its lock (devices() const decides the device list on first use, hence the qualifier)
+  mutable detail::DeviceMirror _mirror;
 
   Index() = default;
   Index(const Index&) = delete;
@@ -225,7 +171,12 @@ class Index {
   void allocateStore() {
     _index_memory.reset(new char[storeBytes()]());  // zero-filled: saved files are deterministic
     _node_locks.reset(_max_node_count);
-    _dirty_rows.reset(_max_node_count);
+    _mirror.resetRows(_max_node_count);
+  }
+
+  detail::StoreView storeView() {
+    return {_index_memory.get(), _node_size_bytes, _data_size_bytes, _M, _cur_num_nodes, _max_node_count, static_cast<int>(_data_type),
+            _distance->metricType() == MetricType::L2 ? FNV_METRIC_L2 : FNV_METRIC_IP, static_cast<uint32_t>(_distance->dimension())};
   }
 
   template <typename Archive>
@@ -342,12 +293,12 @@ class Index {
                      const node_id_t* pop_order = nullptr) {
     detail::NodeGuard own(_node_locks, new_id);
     node_id_t* new_links = nodeLinks(new_id);
-    _dirty_rows.mark(new_id);
+    _mirror.markRow(new_id);
     size_t slot = 0;
     while (!selected.empty()) {
       const node_id_t nb = pop_order ? pop_order[slot] : selected.top().val;
       new_links[slot++] = nb;
-      _dirty_rows.mark(nb);
+      _mirror.markRow(nb);
       {
         detail::NodeGuard theirs(_node_locks, nb);
         node_id_t* nb_links = nodeLinks(nb);
@@ -378,163 +329,18 @@ class Index {
     }
   }
 
-  void markDeviceStale() { _device_stale = true; }             // appended nodes / dirty rows: tracked
-  void markDeviceRebuild() { _device_stale = _device_rebuild = true; }  // anything else (reorder, graph import)
-
-  // Brings the device mirror up to date.  A mirror that already holds a prefix of the nodes receives only what
-  // changed -- the appended node records (fnv_index_write_nodes) and the link rows the builder touched
-  // (fnv_index_write_links) -- unless that is most of the index anyway; otherwise the store is shipped whole.
-  void ensureDevice() const {
-    if (_device_index && !_device_stale) return;
-    resolveDeviceList();
-    Index* self = const_cast<Index*>(this);
-    const int metric = self->deviceMetric();
-    const uint32_t dim = static_cast<uint32_t>(self->_distance->dimension());
-    const bool incremental = _device_index && !_device_rebuild && _device_capacity >= _cur_num_nodes &&
-                             _device_synced_nodes > 0 && _device_synced_nodes <= _cur_num_nodes &&
-                             _dirty_rows.count() <= _cur_num_nodes / 4;
-    if (incremental) {
-      // The marks are drained before the writes: if a write fails they are gone, so the mirror is declared untracked
-      // (next call ships the whole store) before the error goes up -- never a silently diverged device graph.
-      std::vector<node_id_t> ids = _dirty_rows.drain(_device_synced_nodes);
-      try {
-        if (_cur_num_nodes > _device_synced_nodes)
-          detail::throwOnDeviceError(fnv_index_write_nodes(_device_index, _device_synced_nodes,
-                                                           _cur_num_nodes - _device_synced_nodes,
-                                                           nodeData(static_cast<node_id_t>(_device_synced_nodes)),
-                                                           _node_size_bytes, _data_size_bytes));
-        if (!ids.empty()) {
-          std::vector<node_id_t> rows(ids.size() * _M);
-          for (size_t t = 0; t < ids.size(); ++t) std::memcpy(rows.data() + t * _M, nodeLinks(ids[t]), _M * sizeof(node_id_t));
-          detail::throwOnDeviceError(fnv_index_write_links(_device_index, ids.data(), rows.data(), ids.size()));
-        }
-        detail::throwOnDeviceError(fnv_index_set_live_nodes(_device_index, _cur_num_nodes));
-      } catch (...) {
-        const_cast<Index*>(this)->markDeviceRebuild();
-        throw;
-      }
-    } else {
-      if (_device_index) {
-        fnv_index_free(_device_index);
-        _device_index = nullptr;
-        dropReplicas();
-      }
-      if (_cur_num_nodes == _max_node_count) {  // complete: exactly as many rows as nodes
-        detail::throwOnDeviceError(fnv_index_upload(_index_memory.get(), _node_size_bytes, _data_size_bytes,
-                                                    static_cast<uint32_t>(_M), _cur_num_nodes,
-                                                    static_cast<int>(_data_type), metric, dim, _device_ordinal,
-                                                    &_device_index));
-        _device_capacity = _cur_num_nodes;
-      } else {  // still growing: room for every node the store can hold, so that later additions are appended
-        detail::throwOnDeviceError(fnv_index_alloc(static_cast<uint32_t>(_M), _max_node_count,
-                                                   static_cast<int>(_data_type), metric, dim, _device_ordinal,
-                                                   &_device_index));
-        _device_capacity = _max_node_count;
-        detail::throwOnDeviceError(fnv_index_write_nodes(_device_index, 0, _cur_num_nodes, _index_memory.get(),
-                                                         _node_size_bytes, _data_size_bytes));
-        detail::throwOnDeviceError(fnv_index_set_live_nodes(_device_index, _cur_num_nodes));
-      }
-      _dirty_rows.drain(0);
-      applyFilterRouting();  // (a new handle starts with the library's defaults)
-    }
-    _device_synced_nodes = _cur_num_nodes;
-    _device_stale = _device_rebuild = false;
-    _replicas_stale = true;
-  }
-
-  void applyFilterRouting() const {
-    if (!_device_index || (_filter_scan_max == 0 && !_filter_scan_on_overflow)) return;
-    detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_max", _filter_scan_max));
-    detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_on_overflow", _filter_scan_on_overflow ? 1 : 0));
-  }
-
-  void dropReplicas() const {
-    for (fnv_index_t r : _replicas) fnv_index_free(r);
-    _replicas.clear();
-    _replicas_stale = true;
-  }
-
-  // The GPUs this index spreads its batches over: setDevices(), else the FLATNAV_DEVICES environment variable
-  // ("0,1,2,3" -- an ordinal may repeat: tests put two replicas on one GPU -- or "all" = every visible device), else
-  // the primary GPU alone: a library must not allocate a full index copy on every GPU of the node, nor move work to
-  // devices the caller did not name, unasked.
-  void resolveDeviceList() const {
-    if (!_device_list.empty()) return;
-    if (const char* env = std::getenv("FLATNAV_DEVICES")) {
-      if (std::string(env) == "all") {  // the primary first, then every other visible GPU
-        int count = 1;
-        if (fnv_device_count(&count) != FNV_OK || count < 1) count = 1;
-        _device_list.push_back(_device_ordinal);
-        for (int d = 0; d < count; ++d)
-          if (d != _device_ordinal) _device_list.push_back(d);
-        _device_list_defaulted = true;  // a replication failure falls back to the primary with a warning
-      } else {
-        std::stringstream ss(env);
-        for (std::string tok; std::getline(ss, tok, ',');)
-          if (!tok.empty()) _device_list.push_back(std::stoi(tok));
-      }
-    }
-    if (_device_list.empty()) _device_list.push_back(_device_ordinal);  // nobody asked for more: the primary GPU only
-    const_cast<Index*>(this)->_device_ordinal = _device_list[0];
-  }
-
-  // Brings the replicas in line with the (up-to-date) primary mirror.
-  void ensureReplicas() const {
-    resolveDeviceList();
-    if (_device_list.size() <= 1) return;
-    if (!_replicas_stale && _replicas.size() + 1 == _device_list.size()) return;
-    if (_replicas.size() + 1 != _device_list.size()) {
-      dropReplicas();
-      _replicas.resize(_device_list.size() - 1, nullptr);
-      const int rc = fnv_replicate(_device_index, static_cast<int>(_replicas.size()), _device_list.data() + 1, _replicas.data());
-      if (rc != FNV_OK) {
-        _replicas.clear();
-        if (_device_list_defaulted) {  // nobody asked for the other GPUs: serve from the primary alone, say so once
-          std::fprintf(stderr, "flatnav: replicating the index over %zu visible GPUs failed (%s); searching on device %d only\n",
-                       _device_list.size(), fnv_last_error(), _device_ordinal);
-          _device_list.assign(1, _device_ordinal);
-          _replicas_stale = false;
-          return;
-        }
-        detail::throwOnDeviceError(rc);
-      }
-    } else {
-      const int rc = fnv_replica_refresh(_device_index, static_cast<int>(_replicas.size()), _replicas.data());
-      if (rc != FNV_OK) {  // e.g. the primary was re-created with another capacity: start over
-        dropReplicas();
-        return ensureReplicas();
-      }
-    }
-    _replicas_stale = false;
-  }
-
-  int deviceMetric() { return _distance->metricType() == MetricType::L2 ? FNV_METRIC_L2 : FNV_METRIC_IP; }
-
-  // Device index with room for every node the store can hold, holding nodes [0, _cur_num_nodes): what the
-  // device-assisted builder appends to.
-  void ensureDeviceAtCapacity() {
-    if (_device_index && _device_capacity != _max_node_count) markDeviceRebuild();
-    if (_cur_num_nodes == _max_node_count) return ensureDevice();
-    ensureDevice();  // allocates at full capacity while the store is not full
-  }
-
  public:
   // Reference constructor (Index.h:159-179).
   Index(std::unique_ptr<DistanceInterface<dist_t>> dist, int dataset_size, int max_edges_per_node,
         bool collect_stats = false, DataType data_type = DataType::float32)
       : _M(static_cast<size_t>(max_edges_per_node)),
         _max_node_count(static_cast<size_t>(dataset_size)),
-        _distance(std::move(dist)),
+        _distance(static_cast<dist_t*>(dist.release())),
         _collect_stats(collect_stats),
         _data_type(data_type) {
     _data_size_bytes = _distance->dataSize();
     _node_size_bytes = _data_size_bytes + sizeof(node_id_t) * _M + sizeof(label_t);
     allocateStore();
-  }
-
-  ~Index() {
-    dropReplicas();
-    if (_device_index) fnv_index_free(_device_index);
   }
 
   // ---- GPU placement (new) ------------------------------------------------------------------
@@ -544,25 +350,16 @@ class Index {
   // (bindings.cpp:198-211).  Default: FLATNAV_DEVICES ("all" = every visible GPU), else the primary GPU only.
   void setDevices(const std::vector<int>& ordinals) {
     if (ordinals.empty()) throw std::invalid_argument("setDevices: at least one device ordinal is required");
-    std::lock_guard<std::mutex> g(_device_guard);
-    _device_list_defaulted = false;
-    if (ordinals == _device_list) return;
-    dropReplicas();
-    if (ordinals[0] != _device_ordinal || _device_list.empty()) markDeviceRebuild();
-    _device_list = ordinals;
-    _device_ordinal = ordinals[0];
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    _mirror.setDevices(ordinals);
   }
   std::vector<int> devices() const {
-    std::lock_guard<std::mutex> g(_device_guard);
-    resolveDeviceList();
-    return _device_list;
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    return _mirror.devices();
   }
-  int device() const { return _device_ordinal; }
+  int device() const { return _mirror.ordinal(); }
   // Push pending host-side changes to HBM now (otherwise done lazily by the next search).
-  void syncDevice() {
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-  }
+  void syncDevice() { deviceHandle(); }
   // Filter routing (flatnav_hip.h, options "filter_scan_max" / "filter_scan_on_overflow"): in searchBatchFiltered and
   // searchBatchFilteredGrouped a query whose filter allows at most scan_max_allowed live nodes (0: off) -- and, with
   // scan_on_overflow, one whose candidates heap outgrows its room, instead of the call failing -- is answered by the exhaustive
@@ -570,20 +367,15 @@ class Index {
   // and to every mirror made later.
   void setFilterRouting(int64_t scan_max_allowed, bool scan_on_overflow) {
     if (scan_max_allowed < 0) throw std::invalid_argument("setFilterRouting: scan_max_allowed must not be negative");
-    std::lock_guard<std::mutex> g(_device_guard);
-    _filter_scan_max = scan_max_allowed;
-    _filter_scan_on_overflow = scan_on_overflow;
-    if (_device_index) {
-      detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_max", _filter_scan_max));
-      detail::throwOnDeviceError(fnv_set_option(_device_index, "filter_scan_on_overflow", _filter_scan_on_overflow ? 1 : 0));
-    }
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    _mirror.setFilterRouting(scan_max_allowed, scan_on_overflow);
   }
   // The C-ABI handle of the device mirror (valid until the next mutation); for callers that drive
   // fnv_search_batch_device on their own buffers / streams.
   fnv_index_t deviceHandle() {
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-    return _device_index;
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    _mirror.sync(storeView());
+    return _mirror.handle();
   }
 
   // ---- graph import (reference Index.h:187-251) ----------------------------------------------
@@ -611,7 +403,7 @@ class Index {
           break;
         }
     }
-    markDeviceRebuild();
+    _mirror.markRebuild();
   }
 
   std::vector<std::vector<uint32_t>> getGraphOutdegreeTable() {
@@ -631,7 +423,7 @@ class Index {
     *nodeLabel(new_node_id) = label;
     std::fill_n(nodeLinks(new_node_id), _M, new_node_id);  // self-loop == empty slot
     ++_cur_num_nodes;
-    markDeviceStale();
+    _mirror.markStale();
   }
 
   template <typename data_type>
@@ -693,24 +485,12 @@ class Index {
     }
     if (row == total) return;
 
-    std::lock_guard<std::mutex> dev_lock(_device_guard);
-    ensureDeviceAtCapacity();
-    detail::throwOnDeviceError(fnv_set_option(_device_index, "output_node_ids", 1));
-    struct RestoreLabels {
-      fnv_index_t ix;
-      ~RestoreLabels() { fnv_set_option(ix, "output_node_ids", 0); }
-    } restore{_device_index};
-
-    // A device call that throws mid-batch leaves host store and mirror out of step in ways nothing tracks: the mirror
-    // is rebuilt from the host store by the next ensureDevice().
-    struct RebuildOnError {
-      Index* self;
-      bool armed = true;
-      ~RebuildOnError() { if (armed) self->markDeviceRebuild(); }
-    } rebuild_guard{this};
+    std::lock_guard<std::mutex> dev_lock(_mirror.mutex());
+    _mirror.syncAtCapacity(storeView());
+    detail::DeviceMirror::BuildScope build_scope(_mirror);  // (left by an exception: the next search ships the whole store)
+    const fnv_index_t device = _mirror.handle();
 
     const bool device_wiring = opt.wire_on_device && _M <= 64;
-    const uint64_t first_device_node = _cur_num_nodes;
     const int width = ef_construction;
     const int keep = std::max(static_cast<int>(_M / 2), 1);
     std::vector<float> beam_dist;
@@ -732,13 +512,12 @@ class Index {
       };
       for (uint32_t i = 0; i < batch; ++i) storeNode(i);  // a plain copy loop: measured faster than fanning out
       _cur_num_nodes += batch;
-      markDeviceStale();
-      detail::throwOnDeviceError(fnv_index_write_nodes(_device_index, cur, batch, nodeData(static_cast<node_id_t>(cur)),
-                                                       _node_size_bytes, _data_size_bytes));
+      _mirror.markStale();
+      detail::throwOnDeviceError(
+          fnv_index_write_nodes(device, cur, batch, nodeData(static_cast<node_id_t>(cur)), _node_size_bytes, _data_size_bytes));
       if (device_wiring) {  // search + prune + wire in HBM; the host rows are refreshed once at the end
         uint64_t evals = 0;
-        detail::throwOnDeviceError(
-            fnv_index_insert_batch(_device_index, cur, batch, width, num_initializations, &evals));
+        detail::throwOnDeviceError(fnv_index_insert_batch(device, cur, batch, width, num_initializations, &evals));
         if (_collect_stats) _distance_computations.fetch_add(evals + batch * static_cast<uint64_t>(num_initializations));
         row += batch;
         continue;
@@ -748,8 +527,7 @@ class Index {
       beam_ids.resize(batch * width);
       beam_count.resize(batch);
       beam_evals.resize(batch);
-      detail::throwOnDeviceError(fnv_search_batch(_device_index, rowPtr(row),
-                                                  batch, width, width, num_initializations, beam_dist.data(),
+      detail::throwOnDeviceError(fnv_search_batch(device, rowPtr(row), batch, width, width, num_initializations, beam_dist.data(),
                                                   beam_ids.data(), beam_count.data(), beam_evals.data(), nullptr));
       // 3. prune + wire on the host threads
       touched.clear();
@@ -790,24 +568,18 @@ class Index {
       auto packRow = [&](uint32_t t) { std::memcpy(link_rows.data() + static_cast<uint64_t>(t) * _M, nodeLinks(touched[t]), _M * sizeof(node_id_t)); };
       if (_num_threads == 1) for (uint32_t t = 0; t < touched.size(); ++t) packRow(t);
       else flatnav::executeInParallel(0, static_cast<uint32_t>(touched.size()), _num_threads, packRow);
-      detail::throwOnDeviceError(fnv_index_write_links(_device_index, touched.data(), link_rows.data(), touched.size()));
-      detail::throwOnDeviceError(fnv_index_set_live_nodes(_device_index, cur + batch));
+      detail::throwOnDeviceError(fnv_index_write_links(device, touched.data(), link_rows.data(), touched.size()));
+      detail::throwOnDeviceError(fnv_index_set_live_nodes(device, cur + batch));
       row += batch;
     }
     if (device_wiring) {  // bring every link row home (old nodes gained back-links too)
-      (void)first_device_node;
       link_rows.resize(_cur_num_nodes * _M);
-      detail::throwOnDeviceError(fnv_index_read_links(_device_index, 0, _cur_num_nodes, link_rows.data()));
+      detail::throwOnDeviceError(fnv_index_read_links(device, 0, _cur_num_nodes, link_rows.data()));
       auto unpackRow = [&](uint32_t n) { std::memcpy(nodeLinks(n), link_rows.data() + static_cast<uint64_t>(n) * _M, _M * sizeof(node_id_t)); };
       if (_num_threads == 1) for (uint32_t n = 0; n < _cur_num_nodes; ++n) unpackRow(n);
       else flatnav::executeInParallel(0, static_cast<uint32_t>(_cur_num_nodes), _num_threads, unpackRow);
     }
-    // the device copy was kept in step; replicas on other GPUs were not
-    _dirty_rows.drain(0);
-    _device_synced_nodes = _cur_num_nodes;
-    _device_stale = _device_rebuild = false;
-    _replicas_stale = true;
-    rebuild_guard.armed = false;
+    build_scope.complete(_cur_num_nodes);
   }
 
   void add(void* data, label_t& label, int ef_construction, int num_initializations) {
@@ -835,44 +607,25 @@ class Index {
   // with fewer than K reachable results are padded with (+inf, -1) and flagged in out_count.
   void searchBatch(const void* queries, uint64_t nq, int K, int ef_search, int num_initializations, float* out_dist,
                    label_t* out_labels, int32_t* out_count = nullptr) {
-    if (num_initializations <= 0) throw std::invalid_argument("num_initializations must be greater than 0.");
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-    std::vector<uint64_t> ndist;
-    if (_collect_stats) ndist.resize(nq);
-    // small batches stay on the primary GPU; larger ones are sharded over every replica
-    const bool spread = _device_list.size() > 1 && nq >= 64 * _device_list.size();
-    if (spread) ensureReplicas();
-    if (spread && !_replicas.empty()) {
-      std::vector<fnv_index_t> all{_device_index};
-      all.insert(all.end(), _replicas.begin(), _replicas.end());
-      detail::throwOnDeviceError(fnv_search_batch_multi(all.data(), static_cast<int>(all.size()), queries, nq, K, ef_search,
-                                                        num_initializations, out_dist, reinterpret_cast<int32_t*>(out_labels),
-                                                        out_count, _collect_stats ? ndist.data() : nullptr, nullptr));
-    } else {
-      detail::throwOnDeviceError(fnv_search_batch(_device_index, queries, nq, K, ef_search, num_initializations, out_dist,
-                                                  reinterpret_cast<int32_t*>(out_labels), out_count,
-                                                  _collect_stats ? ndist.data() : nullptr, nullptr));
-    }
-    if (_collect_stats) {
-      // reference accounting: + num_initializations per query (Index.h:857-859), + 1 per neighbour
-      // evaluation (Index.h:689-691)
-      uint64_t total = static_cast<uint64_t>(num_initializations) * nq;
-      for (uint64_t v : ndist) total += v;
-      _distance_computations.fetch_add(total);
-    }
+    runSearch(nq, num_initializations, true, [&](fnv_index_t primary, uint64_t* ndist) {
+      // small batches stay on the primary GPU; larger ones are sharded over every replica
+      const size_t n_devices = _mirror.devices().size();
+      if (n_devices > 1 && nq >= 64 * n_devices && !_mirror.replicas().empty()) {
+        std::vector<fnv_index_t> all{primary};
+        all.insert(all.end(), _mirror.replicas().begin(), _mirror.replicas().end());
+        return fnv_search_batch_multi(all.data(), static_cast<int>(all.size()), queries, nq, K, ef_search, num_initializations,
+                                      out_dist, reinterpret_cast<int32_t*>(out_labels), out_count, ndist, nullptr);
+      }
+      return fnv_search_batch(primary, queries, nq, K, ef_search, num_initializations, out_dist,
+                              reinterpret_cast<int32_t*>(out_labels), out_count, ndist, nullptr);
+    });
   }
 
   // Reference Index::search (Index.h:387-409): up to K (distance, label) pairs, ascending.
   std::vector<dist_label_t> search(const void* query, const int K, int ef_search, int num_initializations = 100) {
-    std::vector<float> dist(static_cast<size_t>(std::max(K, 0)));
-    std::vector<label_t> labels(static_cast<size_t>(std::max(K, 0)));
-    int32_t count = 0;
-    searchBatch(query, 1, K, ef_search, num_initializations, dist.data(), labels.data(), &count);
-    std::vector<dist_label_t> results;
-    results.reserve(static_cast<size_t>(count));
-    for (int i = 0; i < count; ++i) results.emplace_back(dist[static_cast<size_t>(i)], labels[static_cast<size_t>(i)]);
-    return results;
+    return oneQuery(K, [&](float* dist, label_t* labels, int32_t* count) {
+      searchBatch(query, 1, K, ef_search, num_initializations, dist, labels, count);
+    });
   }
 
   // Filtered search (flatnav_hip.h, fnv_search_batch_filtered): the K nearest neighbours among the nodes whose label L is set
@@ -882,32 +635,18 @@ class Index {
   void searchBatchFiltered(const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
                            const uint8_t* allowed_bits, uint64_t n_bits, float* out_dist, label_t* out_labels,
                            int32_t* out_count = nullptr) {
-    if (num_initializations <= 0) throw std::invalid_argument("num_initializations must be greater than 0.");
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-    std::vector<uint64_t> ndist;
-    if (_collect_stats) ndist.resize(nq);
-    detail::throwOnDeviceError(fnv_search_batch_filtered(_device_index, queries, nq, K, ef_search, num_initializations, allowed_bits,
-                                                         n_bits, out_dist, reinterpret_cast<int32_t*>(out_labels), out_count,
-                                                         _collect_stats ? ndist.data() : nullptr, nullptr));
-    if (_collect_stats) {  // same accounting as searchBatch
-      uint64_t total = static_cast<uint64_t>(num_initializations) * nq;
-      for (uint64_t v : ndist) total += v;
-      _distance_computations.fetch_add(total);
-    }
+    runSearch(nq, num_initializations, true, [&](fnv_index_t primary, uint64_t* ndist) {
+      return fnv_search_batch_filtered(primary, queries, nq, K, ef_search, num_initializations, allowed_bits, n_bits, out_dist,
+                                       reinterpret_cast<int32_t*>(out_labels), out_count, ndist, nullptr);
+    });
   }
 
   // One query: up to K (distance, label) pairs among the allowed labels, ascending (fewer when fewer are reachable).
   std::vector<dist_label_t> searchFiltered(const void* query, const int K, int ef_search, const uint8_t* allowed_bits,
                                            uint64_t n_bits, int num_initializations = 100) {
-    std::vector<float> dist(static_cast<size_t>(std::max(K, 0)));
-    std::vector<label_t> labels(static_cast<size_t>(std::max(K, 0)));
-    int32_t count = 0;
-    searchBatchFiltered(query, 1, K, ef_search, num_initializations, allowed_bits, n_bits, dist.data(), labels.data(), &count);
-    std::vector<dist_label_t> results;
-    results.reserve(static_cast<size_t>(count));
-    for (int i = 0; i < count; ++i) results.emplace_back(dist[static_cast<size_t>(i)], labels[static_cast<size_t>(i)]);
-    return results;
+    return oneQuery(K, [&](float* dist, label_t* labels, int32_t* count) {
+      searchBatchFiltered(query, 1, K, ef_search, num_initializations, allowed_bits, n_bits, dist, labels, count);
+    });
   }
 
   // Exhaustive search (flatnav_hip.h, fnv_search_batch_exhaustive): the EXACT K nearest neighbours among the live nodes, or
@@ -917,31 +656,18 @@ class Index {
   // primary GPU.  (No reference counterpart: the reference has no brute-force search.)
   void searchBatchExhaustive(const void* queries, uint64_t nq, int K, const uint8_t* allowed_bits, uint64_t n_bits, bool use_filter,
                              float* out_dist, label_t* out_labels, int32_t* out_count = nullptr) {
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-    std::vector<uint64_t> ndist;
-    if (_collect_stats) ndist.resize(nq);
-    detail::throwOnDeviceError(fnv_search_batch_exhaustive(_device_index, queries, nq, K, use_filter ? 1 : 0, allowed_bits, n_bits,
-                                                           out_dist, reinterpret_cast<int32_t*>(out_labels), out_count,
-                                                           _collect_stats ? ndist.data() : nullptr));
-    if (_collect_stats) {  // one evaluation per candidate row and query
-      uint64_t total = 0;
-      for (uint64_t v : ndist) total += v;
-      _distance_computations.fetch_add(total);
-    }
+    runSearch(nq, 0, false, [&](fnv_index_t primary, uint64_t* ndist) {
+      return fnv_search_batch_exhaustive(primary, queries, nq, K, use_filter ? 1 : 0, allowed_bits, n_bits, out_dist,
+                                         reinterpret_cast<int32_t*>(out_labels), out_count, ndist);
+    });
   }
 
   // One query: up to K (distance, label) pairs, ascending by (distance, node id) (fewer when there are fewer candidates).
   std::vector<dist_label_t> searchExhaustive(const void* query, const int K, const uint8_t* allowed_bits = nullptr,
                                              uint64_t n_bits = 0, bool use_filter = false) {
-    std::vector<float> dist(static_cast<size_t>(std::max(K, 0)));
-    std::vector<label_t> labels(static_cast<size_t>(std::max(K, 0)));
-    int32_t count = 0;
-    searchBatchExhaustive(query, 1, K, allowed_bits, n_bits, use_filter, dist.data(), labels.data(), &count);
-    std::vector<dist_label_t> results;
-    results.reserve(static_cast<size_t>(count));
-    for (int i = 0; i < count; ++i) results.emplace_back(dist[static_cast<size_t>(i)], labels[static_cast<size_t>(i)]);
-    return results;
+    return oneQuery(K, [&](float* dist, label_t* labels, int32_t* count) {
+      searchBatchExhaustive(query, 1, K, allowed_bits, n_bits, use_filter, dist, labels, count);
+    });
   }
 
   // Grouped filters (flatnav_hip.h, fnv_search_batch_*_grouped): searchBatchFiltered / searchBatchExhaustive with one allowed set
@@ -951,36 +677,19 @@ class Index {
   void searchBatchFilteredGrouped(const void* queries, uint64_t nq, int K, int ef_search, int num_initializations,
                                   const uint8_t* filters, uint64_t n_filters, uint64_t stride_bytes, uint64_t n_bits,
                                   const int32_t* query_filter, float* out_dist, label_t* out_labels, int32_t* out_count = nullptr) {
-    if (num_initializations <= 0) throw std::invalid_argument("num_initializations must be greater than 0.");
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-    std::vector<uint64_t> ndist;
-    if (_collect_stats) ndist.resize(nq);
-    detail::throwOnDeviceError(fnv_search_batch_filtered_grouped(_device_index, queries, nq, K, ef_search, num_initializations, filters,
-                                                                 n_filters, stride_bytes, n_bits, query_filter, out_dist,
-                                                                 reinterpret_cast<int32_t*>(out_labels), out_count,
-                                                                 _collect_stats ? ndist.data() : nullptr, nullptr));
-    if (_collect_stats) {  // same accounting as searchBatchFiltered
-      uint64_t total = static_cast<uint64_t>(num_initializations) * nq;
-      for (uint64_t v : ndist) total += v;
-      _distance_computations.fetch_add(total);
-    }
+    runSearch(nq, num_initializations, true, [&](fnv_index_t primary, uint64_t* ndist) {
+      return fnv_search_batch_filtered_grouped(primary, queries, nq, K, ef_search, num_initializations, filters, n_filters, stride_bytes,
+                                               n_bits, query_filter, out_dist, reinterpret_cast<int32_t*>(out_labels), out_count,
+                                               ndist, nullptr);
+    });
   }
   void searchBatchExhaustiveGrouped(const void* queries, uint64_t nq, int K, const uint8_t* filters, uint64_t n_filters,
                                     uint64_t stride_bytes, uint64_t n_bits, const int32_t* query_filter, float* out_dist,
                                     label_t* out_labels, int32_t* out_count = nullptr) {
-    std::lock_guard<std::mutex> g(_device_guard);
-    ensureDevice();
-    std::vector<uint64_t> ndist;
-    if (_collect_stats) ndist.resize(nq);
-    detail::throwOnDeviceError(fnv_search_batch_exhaustive_grouped(_device_index, queries, nq, K, filters, n_filters, stride_bytes, n_bits,
-                                                                   query_filter, out_dist, reinterpret_cast<int32_t*>(out_labels),
-                                                                   out_count, _collect_stats ? ndist.data() : nullptr));
-    if (_collect_stats) {  // same accounting as searchBatchExhaustive
-      uint64_t total = 0;
-      for (uint64_t v : ndist) total += v;
-      _distance_computations.fetch_add(total);
-    }
+    runSearch(nq, 0, false, [&](fnv_index_t primary, uint64_t* ndist) {
+      return fnv_search_batch_exhaustive_grouped(primary, queries, nq, K, filters, n_filters, stride_bytes, n_bits, query_filter,
+                                                 out_dist, reinterpret_cast<int32_t*>(out_labels), out_count, ndist);
+    });
   }
 
   // ---- reordering (reference Index.h:412-440, 872-926) ---------------------------------------
@@ -1009,7 +718,7 @@ class Index {
     if (!stream.is_open()) throw std::runtime_error("Unable to open file for reading: " + filename);
     flatnav::util::BinaryReader archive(stream);
     std::unique_ptr<Index<dist_t, label_t>> index(new Index<dist_t, label_t>());
-    std::unique_ptr<DistanceInterface<dist_t>> dist = std::make_unique<dist_t>();
+    auto dist = std::make_unique<dist_t>();
     archive(index->_data_type, index->_M, index->_data_size_bytes, index->_node_size_bytes, index->_max_node_count,
             index->_cur_num_nodes, *dist);
     if (index->_node_size_bytes != index->_data_size_bytes + sizeof(node_id_t) * index->_M + sizeof(label_t) ||
@@ -1069,6 +778,39 @@ class Index {
   }
 
  private:
+  // The frame of every batched search: under the mirror's lock, bring the mirror up to date, make the one C-ABI call
+  // (`call(primary handle, per-query evaluation counts or null)` -> status), account for it.  The graph searches
+  // (`searches_graph`) need num_initializations > 0 and pay that many evaluations per query for their entry point (reference
+  // Index.h:857-859) on top of one per neighbour evaluation (Index.h:689-691), which is what the device counts; a scan pays
+  // one per candidate row, all counted by the device.
+  template <typename Call>
+  void runSearch(uint64_t nq, int num_initializations, bool searches_graph, Call&& call) {
+    if (searches_graph && num_initializations <= 0) throw std::invalid_argument("num_initializations must be greater than 0.");
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    _mirror.sync(storeView());
+    std::vector<uint64_t> ndist;
+    if (_collect_stats) ndist.resize(nq);
+    detail::throwOnDeviceError(call(_mirror.handle(), _collect_stats ? ndist.data() : nullptr));
+    if (_collect_stats) {
+      uint64_t total = static_cast<uint64_t>(num_initializations) * nq;
+      for (uint64_t v : ndist) total += v;
+      _distance_computations.fetch_add(total);
+    }
+  }
+
+  // The single-query forms: `batched(dist, labels, count)` answers one query with K slots; the real ones become pairs.
+  template <typename Batched>
+  std::vector<dist_label_t> oneQuery(int K, Batched&& batched) {
+    std::vector<float> dist(static_cast<size_t>(std::max(K, 0)));
+    std::vector<label_t> labels(static_cast<size_t>(std::max(K, 0)));
+    int32_t count = 0;
+    batched(dist.data(), labels.data(), &count);
+    std::vector<dist_label_t> results;
+    results.reserve(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) results.emplace_back(dist[static_cast<size_t>(i)], labels[static_cast<size_t>(i)]);
+    return results;
+  }
+
   // Apply a permutation (perm[old] = new id): rewrite every link, then move the node records with
   // one gather into a fresh store (reference relabel(), Index.h:872-926, permutes in place).
   void relabel(const std::vector<node_id_t>& perm) {
@@ -1081,7 +823,7 @@ class Index {
     for (node_id_t n = 0; n < _cur_num_nodes; ++n)
       std::memcpy(fresh.get() + static_cast<uint64_t>(perm[n]) * _node_size_bytes, nodeData(n), _node_size_bytes);
     _index_memory = std::move(fresh);
-    markDeviceRebuild();
+    _mirror.markRebuild();
   }
 };
 
