@@ -20,12 +20,12 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
                                            "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "runtime.hpp",
-                                           "launch_plan.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp")] + [
+                                           "launch_plan.hpp", "measurements.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
-# The host units behind runtime.hpp, which brings launch_plan.hpp (kernel units include neither) and, through kernel_table.h,
+# The host units behind runtime.hpp, which brings launch_plan.hpp with measurements.hpp (kernel units include none) and, through kernel_table.h,
 # the device headers that say what a launch passes.  Each unit with the kernel headers it includes on top of those (launch.hip:
 # scan.hpp for its non-template kernels; the others in developer builds, where it instantiates the search kernels itself).
-HOST_HEADERS = ("runtime.hpp", "launch_plan.hpp")
+HOST_HEADERS = ("runtime.hpp", "launch_plan.hpp", "measurements.hpp")
 KERNEL_HEADERS = ("scan.hpp", "kernels.hpp", "merged_beam.hpp", "visited.hpp")
 HOST_UNITS = {"index.hip": (), "launch.hip": KERNEL_HEADERS, "host_search.hip": (), "multi.hip": (), "tune.hip": (),
               "device_build.hip": ()}
@@ -72,7 +72,7 @@ def _stale(obj, src):
     name = os.path.basename(src)
     if name in HOST_UNITS:
         deps = [h for h in HEADERS if os.path.basename(h) not in KERNEL_HEADERS or os.path.basename(h) in HOST_UNITS[name]]
-    else:  # runtime.hpp and launch_plan.hpp (the launch planner) are included by the host units only
+    else:  # runtime.hpp, launch_plan.hpp and measurements.hpp (the launch planner) are included by the host units only
         deps = [h for h in HEADERS if os.path.basename(h) not in HOST_HEADERS]
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 

@@ -241,14 +241,11 @@ static fnv_index_s* create_lane_locked(fnv_index_t ix, int which) {
 static void sync_lane(fnv_index_t ix, fnv_index_s* lane) {
   std::lock_guard<std::mutex> l1(ix->mu);
   std::lock_guard<std::mutex> l2(lane->mu);
-  if (lane->lane_epoch == ix->tune_epoch && lane->lane_options == ix->options_version) return;
+  if (lane->lane_epoch == ix->measured.epoch() && lane->lane_options == ix->options_version) return;
   static_cast<IndexOptions&>(*lane) = static_cast<const IndexOptions&>(*ix);
-  lane->layouts = ix->layouts;
-  lane->tuner = ix->tuner;
-  lane->sample_kernel = -1;
-  lane->options_version++;
-  lane->plan.valid = false;
-  lane->lane_epoch = ix->tune_epoch;
+  lane->measured.copy_from(ix->measured, true);
+  lane->options_version++;  // (the lane's plan is made again)
+  lane->lane_epoch = ix->measured.epoch();
   lane->lane_options = ix->options_version;
 }
 

@@ -566,7 +566,7 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   std::string n(name);
   if (value < 0 && !((n == "sorted_tail_exact_pct" || n == "sorted_variant") && value == -1))
     return fail(FNV_ERR_INVALID, "option values must be non-negative");
-  // Under the handle's mutex (round 5): a launch reads the options, the tuner and the layouts under it, and a concurrent
+  // Under the handle's mutex (round 5): a launch reads the options and the measurements under it, and a concurrent
   // caller's lane copies them under it (sync_lane) -- an option may change while other threads search; each launch sees the
   // options either before or after the change.
   std::lock_guard<std::mutex> lock(ix->mu);
@@ -616,14 +616,13 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   // nor the kernel choice: Index.h::addBatchDevice flips output_node_ids around every device build, and a tune costs
   // dozens of launches.  (output_node_ids is read per launch; shadow_exact per launch; tune_layout by fnv_tune itself.)
   const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows" ||
-                            n == "filter_scan_max" || n == "filter_scan_on_overflow" || n == "launch_timing";  // (filtered launches never touch the tuner)
-  if (!keeps_tuning) {
+                            n == "filter_scan_max" || n == "filter_scan_on_overflow" || n == "launch_timing";  // (filtered launches never touch the measurements)
+  // (either way the epoch goes up: the hidden lanes of the host entry point re-copy options and measurements)
+  if (keeps_tuning) ix->measured.touch();
+  else {
     ix->options_version++;
-    ix->tuner.clear();
-    ix->layouts.clear();
-    ix->sample_kernel = -1;
+    ix->measured.forget();
   }
-  ix->tune_epoch++;  // (the second lane of the host entry point re-copies options and measurements)
   return FNV_OK;
 }
 

@@ -244,12 +244,13 @@ static int ensure_plan(fnv_index_s* ix, int B, int K, bool half_rows) {
   PlannedLaunch& plan = ix->plan;
   // (a mirror that was dropped and built again is another allocation: the plan's kernels carry the table they read)
   const bool same_rows = plan.half_rows == half_rows && (!half_rows || plan.kern.rows == rows_source(ix)->half.rows.load());
-  if (plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity && plan.options_version == ix->options_version && same_rows)
+  if (plan.valid && plan.B == B && plan.K == K && plan.capacity == ix->capacity && plan.options_version == ix->options_version &&
+      plan.layouts_version == ix->measured.layouts_version() && same_rows)
     return FNV_OK;
   plan = PlannedLaunch();
   const PlanRuntime rt{ix, row_geometry(ix), B, half_rows};
   LayoutChoice lc;  // a layout that fnv_tune measured for this beam width overrides the planner's rules (heap home, table size)
-  if (auto it = ix->layouts.find(B); it != ix->layouts.end()) lc = it->second;
+  if (const LayoutChoice* measured = ix->measured.layout(B)) lc = *measured;
   std::string err;
   const int rc = plan_launch(ix, B, K, lc, rt, err, plan);
   if (rc) return fail(rc, err);
@@ -264,6 +265,7 @@ static int ensure_plan(fnv_index_s* ix, int B, int K, bool half_rows) {
   }
   plan.half_rows = half_rows;
   plan.options_version = ix->options_version;
+  plan.layouts_version = ix->measured.layouts_version();
   plan.valid = true;
   return FNV_OK;
 }
@@ -279,23 +281,18 @@ static KernelChoice choose_kernel(fnv_index_s* ix, int B, uint64_t nq, int force
   if (ix->is_lane) {
     // a hidden lane runs what its owner has measured (copied by sync_lane) and never explores or samples: a production
     // caller that happens to land on a lane must not pay for 3 x variants exploratory launches per lane
-    if (auto it = ix->tuner.find(tuner_key(B, multi_round)); nq >= 2048 && it != ix->tuner.end())
-      if (const int best = lane_variant(it->second, multi_round, try_tail, shadows_on); best >= 0) set_variant(c, best);
+    if (const Tuner* t = ix->measured.find(tuner_key(B, multi_round)); nq >= 2048 && t)
+      if (const int best = lane_variant(*t, multi_round, try_tail, shadows_on); best >= 0) set_variant(c, best);
     return c;
   }
-  if (ix->sample_kernel >= 0 && ix->launched && hipEventQuery(ix->ev1) == hipSuccess) {
+  if (ix->measured.has_pending() && ix->launched && hipEventQuery(ix->ev1) == hipSuccess) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) == hipSuccess && ms > 0.f) {
-      Tuner& t = ix->tuner[ix->sample_B];
-      const float per_q = ms / (float)ix->sample_nq;
-      if (t.samples[ix->sample_kernel] == 0 || per_q < t.best[ix->sample_kernel]) t.best[ix->sample_kernel] = per_q;
-      t.samples[ix->sample_kernel]++;
-      ix->tune_epoch++;  // (lanes re-copy the measurements)
-    }
-    ix->sample_kernel = -1;
+    if (hipEventElapsedTime(&ms, ix->ev0, ix->ev1) != hipSuccess) ms = 0.f;
+    ix->measured.harvest(ms);  // (a change: lanes re-copy the measurements)
   }
   if (nq >= 2048) {
-    Tuner& t = ix->tuner[tuner_key(B, multi_round)];
+    const Tuner* found = ix->measured.find(tuner_key(B, multi_round));
+    const Tuner t = found ? *found : Tuner();  // (nothing measured yet: every variant is still to be sampled)
     // three samples each (the first launch of a kernel is a cold one; the best of the rest decides), then the fastest
     // (fnv_tune takes all the samples in one call, so that no caller's launch is an exploratory one)
     int v = owner_next_sample(t, multi_round, try_tail, shadows_on);
@@ -539,7 +536,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   if (rc) return rc;
 
   // -- the scan and its merge
-  ix->sample_kernel = -1;  // ev0 / ev1 no longer bracket a graph-search launch: a pending sample of the adaptive choice is dropped
+  ix->measured.drop_pending();  // ev0 / ev1 no longer bracket a graph-search launch
   HIP_TRY(hipEventRecord(ix->ev0, stream));
   if (grouped) {
     rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full], gp, shape, nq, stream);
@@ -567,14 +564,7 @@ static int plan_search(fnv_index_s* ix, int B, int K, uint64_t live, bool filter
   // The half-width mirror (half_rows.hpp): its state is the source's, read at every launch.  Launches with and without it run
   // different kernels, so what was measured in the other mode (kernel variant, LDS layout) is discarded with the plan.
   const bool half_rows = half_rows_usable(ix, live);
-  if (ix->measured_half >= 0 && ix->measured_half != (int)half_rows) {
-    ix->tuner.clear();
-    ix->layouts.clear();
-    ix->sample_kernel = -1;
-    ix->tune_epoch++;
-    ix->plan.valid = false;
-  }
-  ix->measured_half = (int)half_rows;
+  (void)ix->measured.rows_changed(half_rows);  // (the layouts' version then makes ensure_plan plan again)
   const int rc = ensure_plan(ix, B, K, half_rows);
   if (rc) return rc;
   PlannedLaunch& plan = ix->plan;
@@ -749,9 +739,8 @@ int search_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, int K
   if (timed) HIP_TRY(hipEventRecord(ix->ev1, stream));
 
   // -- record: for the adaptive choice's next harvest, and for the fnv_last_* calls
-  ix->sample_kernel = c.sample ? c.variant : -1;  // (a sample is always timed)
-  ix->sample_B = tuner_key(B, c.multi_round);
-  ix->sample_nq = nq;
+  if (c.sample) ix->measured.expect(tuner_key(B, c.multi_round), c.variant, nq);  // (a sample is always timed)
+  else ix->measured.drop_pending();
   ix->last_variant = sorted ? std::max(c.variant, 1) : 0;
   ix->last_exploratory = c.exploratory;
   if (c.exploratory) ix->explored_launches++;

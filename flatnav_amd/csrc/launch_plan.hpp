@@ -3,7 +3,7 @@
 // LDS layout of a query slot, the table-size ladder and its occupancy trade, the choice of kernel family and variant, one
 // graph-search launch whole (shape_search: the function launch.hip launches by and the CPU test reports), K0's tile, the
 // per-slot workspace, the exhaustive scan's tiles, segments, grouping arrays, routing and byte counts, the layouts fnv_tune
-// tries.  It deals in counts and option values, never in pointers.  The host units (runtime.hpp) own the HIP runtime (kernel
+// tries -- and, in measurements.hpp (included below), what the adaptive choice has measured and how fnv_tune decides.  It deals in counts and option values, never in pointers.  The host units (runtime.hpp) own the HIP runtime (kernel
 // pointers, occupancy queries, LDS limits, events, buffers) and hand the planner what it needs of it as a `Runtime` object:
 //   int occupancy(int mode, uint32_t lds)                workgroups of MODE_*'s kernel one CU holds with `lds` bytes each (0: error)
 //   const char* raise_lds_limit(int mode, uint32_t lds)  that kernel may be launched with `lds` bytes: null, or the runtime's error
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/flatnav_hip.h"
+#include "measurements.hpp"
 #include "scan_select.hpp"
 #include "search_types.h"
 
@@ -61,34 +62,6 @@ struct PlanInputs : IndexOptions {
   uint64_t capacity = 0;  // rows the device buffers hold (>= n_nodes; grows never)
   uint64_t parent_capacity = 0;  // a view: its source's capacity (0: not a view)
   int num_cus = 0;
-};
-
-// Kernel variants of one launch: 0 the exact two-heap kernel, 1 the merged-beam kernel, 2-5 the merged-beam kernel with
-// the last 50 / 75 / 100 / 25 % of a round of queries sent straight to the exact search, 6 (round 4) the merged-beam kernel
-// for every query plus exact shadows of the last ones on the slots the drain leaves idle (search_types.h).
-constexpr int kNumVariants = 7;
-constexpr int kVariantTailShadows = 6;
-constexpr int kTailPct[kNumVariants] = {0, 0, 50, 75, 100, 25, 0};
-inline bool variant_allowed(int v, bool multi_round, bool try_tail, bool shadows_on, bool pinned_only = false) {
-  if (v < 2) return true;
-  // (tail shadows: measured in round 4 -- 0.5-3 % better than the merged-beam kernel alone, behind the best exact tail on every configuration:
-  //  a shadow can only start when a slot falls idle, which is too late for the ties that end a launch -- so the variant can
-  //  be pinned for A/B runs but is not part of the adaptive choice)
-  if (v == kVariantTailShadows) return shadows_on && pinned_only;
-  return multi_round && try_tail;  // an exact tail needs more than one round of queries
-}
-
-// adaptive kernel choice ("sorted_beam" = 2): per beam width, the best time per query seen for each variant
-struct Tuner {
-  // ms per query: [0] two-heap kernel, [1] merged-beam kernel, [2..5] merged-beam kernel whose last 50 / 75 / 100 / 25 %
-  // of a round of queries go straight to the exact search ("sorted_tail_exact_pct"; launches of more than one round)
-  float best[kNumVariants] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
-  int samples[kNumVariants] = {0, 0, 0, 0, 0, 0, 0};
-};
-// Per beam width: the LDS layout fnv_tune measured to be the fastest (absent: the rules of configure_launch).
-struct LayoutChoice {
-  int cand_lds = -1;       // where the exact search keeps its candidates heap: -1 = by rule, 0 = HBM, 1 = LDS
-  uint32_t vis_slots = 0;  // visited-table slots: 0 = by rule
 };
 
 // Row stride of the vector table.  Rows are 16-byte chunks; when rounding the stride up to whole 128-byte lines costs
@@ -344,16 +317,13 @@ inline RowGeometry row_geometry(const PlanInputs* ix) {
   return g;
 }
 
-// The adaptive choice keeps its measurements per (beam width, batch class: more than one round of queries or not).
-inline int tuner_key(int B, bool multi_round) { return 2 * B + (multi_round ? 1 : 0); }
-
 // What a search launch looks like for one (beam width, K) on one index: cached (launch.hip, which adds the kernels),
 // because working it out costs several occupancy queries and a single-query search should not pay for them every time.
 struct LaunchPlan {
   bool valid = false;
   int B = 0, K = 0, cfg = 0, mode = 0;
   bool full = false;
-  uint64_t capacity = 0, options_version = 0;
+  uint64_t capacity = 0, options_version = 0, layouts_version = 0;  // (made under these: launch.hip, ensure_plan)
   SearchParams heaps, sorted;                 // geometry + LDS layout for each (pointers and per-call fields unset)
   uint32_t lds = 0, slds = 0;
   int bpc = 0, sbpc = 0;
@@ -491,8 +461,9 @@ inline KernelChoice default_choice(const PlanInputs* ix, const LaunchPlan& plan,
   if (c.sorted && pinned >= 0) set_variant(c, pinned_variant(pinned, c.multi_round, ix->shadow_exact != 0));
   return c;
 }
-// The adaptive choice ("sorted_beam" = 2) keeps, per tuner_key, the best time of each variant (Tuner); choose_kernel
-// (launch.hip) harvests the timings of an `adaptive` choice, asks the three rules below and hands the answer to set_variant.
+// The adaptive choice ("sorted_beam" = 2) keeps, per tuner_key, the best time of each variant (Tuner, in the handle's
+// Measurements: measurements.hpp); choose_kernel (launch.hip) hands the timing of an `adaptive` choice's last sample to
+// Measurements::harvest, asks the three rules below and hands the answer to set_variant.
 // A hidden lane runs the fastest variant its owner has measured (-1: none measured); the lowest ordinal wins a tie.
 inline int lane_variant(const Tuner& t, bool multi_round, bool try_tail, bool shadows_on) {
   int best = -1;

@@ -8,17 +8,11 @@
 // Both handles' mutexes are held by the caller (source first).
 static void inherit_measurements(const fnv_index_s* src, fnv_index_s* r) {
   const bool same_model = r->num_cus == src->num_cus && r->gcn_arch == src->gcn_arch;
-  if (same_model) {
-    r->tuner = src->tuner;
-    r->layouts = src->layouts;
-  } else {
-    r->tuner.clear();
-    r->layouts.clear();  // measured under the old options (a stale table size could even change the kernel mode)
-  }
-  r->sample_kernel = -1;
-  r->measured_half = same_model ? src->measured_half : -1;  // (a replica without the source's mirror discards them at its first launch)
-  r->replica_epoch = src->tune_epoch;
-  r->tune_epoch++;  // (the replica's own lanes re-copy)
+  // (another model: what the replica held was measured under the old options -- a stale table size could even change the kernel
+  //  mode; the same model: a replica without the source's mirror discards the copy at its first launch.  The replica's plan is
+  //  made again and its own lanes re-copy: copy_from sees to both.)
+  r->measured.copy_from(src->measured, same_model);
+  r->replica_epoch = src->measured.epoch();
 }
 
 // Only the C ABI is exported (the library is built with -fvisibility=hidden).
@@ -81,7 +75,6 @@ int fnv_replica_refresh(fnv_index_t src, int n_replicas, fnv_index_t* replicas) 
     r->replica_of = src;
     r->replica_options = src->options_version;
     inherit_measurements(src, r);
-    r->plan.valid = false;
   }
   // Doubling tree of peer copies over xGMI: in every round each index that already holds the data feeds one that
   // does not (1 -> 2 -> 4 -> 8 holders: three rounds for eight GPUs, every link busy once per round).  The copies
@@ -157,10 +150,7 @@ int fnv_search_batch_multi(fnv_index_t* indexes, int n_indexes, const void* quer
     if (r == src || r->replica_of != src) continue;
     std::lock_guard<std::mutex> l1(src->mu);
     std::lock_guard<std::mutex> l2(r->mu);
-    if (r->replica_options == src->options_version && r->replica_epoch != src->tune_epoch) {
-      inherit_measurements(src, r);
-      r->plan.valid = false;  // (a layout choice changes the plan)
-    }
+    if (r->replica_options == src->options_version && r->replica_epoch != src->measured.epoch()) inherit_measurements(src, r);
   }
   const uint64_t per = (nq + (uint64_t)n_indexes - 1) / (uint64_t)n_indexes;
   const size_t qrow = (size_t)indexes[0]->dim * dtype_size(indexes[0]->dtype);

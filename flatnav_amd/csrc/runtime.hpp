@@ -32,9 +32,12 @@
 // The launch planner -- row layout, visited-table geometry, a slot's LDS layout, table-size ladder, kernel family and variant,
 // the whole shape of a graph-search launch (shape_search), the exhaustive scan's tiles, segments, grouping arrays and routing,
 // K0's tile, the workspace's sizes: every decision that is arithmetic -- lives in launch_plan.hpp, free of HIP
-// (tests/test_launch_plan.py runs it on the CPU; tests/test_gpu_scan_shape.py holds launches against it); these units own the
-// HIP runtime around it: handles, buffers, streams and events, kernel lookup, the occupancy queries and LDS limits the planner
-// asks for, the measurements of the adaptive choice, the launches and the C ABI.
+// (tests/test_launch_plan.py runs it on the CPU; tests/test_gpu_scan_shape.py holds launches against it).  So does the adaptive
+// choice (measurements.hpp, which the planner includes): what a handle has measured and every rule that changes it (the class
+// Measurements), and fnv_tune's tournament over a measuring object (tests/test_adaptive_choice.py runs both on the CPU;
+// tests/test_gpu_tune_replay.py replays a real tune's log through them).  These units own the HIP runtime around it: handles,
+// buffers, streams and events, kernel lookup, the occupancy queries and LDS limits the planner asks for, the timed launches
+// the adaptive choice is fed with, the launches and the C ABI.
 //
 // Also theirs: incremental construction (fnv_index_write_nodes / write_links / insert_batch: Index::add,
 // include/flatnav/index/Index.h:353-378 with selectNeighbors :714-763 and connectNeighbors :765-834 as the
@@ -207,7 +210,7 @@ struct DeviceBuf {
 };
 
 // THE LOCK ORDER of a handle: who may hold what (the comments at each site refer here).
-//   mu        launch configuration + workspace growth.  A launch reads the options, the tuner and the layouts under it, an option
+//   mu        launch configuration + workspace growth.  A launch reads the options and the measurements under it, an option
 //             changes under it, and a buffer that grows on demand grows under it.  Two handles' mu: the SOURCE first, then its
 //             replica or lane (sync_lane, fnv_replica_refresh, fnv_search_batch_multi).
 //   host_mu   one host-buffer caller per lane for the whole call: the lane's d_q / d_out, staging areas, stream and workspace are
@@ -240,19 +243,18 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
     std::atomic<size_t> bytes{0};
     bool off = false;                     // FLATNAV_HALF_ROWS=0 when the handle was made: never built
   } half;
-  int measured_half = -1;  // tuner / layouts hold measurements of launches with (1) / without (0) the mirror; -1: none yet
   bool last_half = false;  // the most recent launch read the mirror
   uint32_t* d_links = nullptr;
   int32_t* d_labels = nullptr;
   std::string gcn_arch;  // hipDeviceProp_t::gcnArchName: replicas on the same GPU model inherit the source's measurements
   uint64_t options_version = 0;
   PlannedLaunch plan;
-  // adaptive kernel choice ("sorted_beam" = 2) and the layouts fnv_tune measured, per beam width (launch_plan.hpp)
-  std::map<int, LayoutChoice> layouts;
-  std::map<int, Tuner> tuner;
-  int sample_B = 0, sample_kernel = -1;  // the launch between ev0 / ev1 is a sample for this entry (-1: it is not)
-  uint64_t sample_nq = 0;
-  int last_variant = 0;          // what the most recent launch ran: 0 two-heap kernel, 1 merged beam, 2-4 with exact tail
+  // The adaptive choice ("sorted_beam" = 2): the layouts fnv_tune measured, each variant's best time, the launch between
+  // ev0 / ev1 that is a sample still to be harvested, the row mode they were measured in, and the epoch by which lanes and
+  // replicas notice a change -- one object that keeps these consistent (measurements.hpp); the units only call it.  Whoever
+  // records ev0 / ev1 for anything but a graph search calls drop_pending().
+  Measurements measured;
+  int last_variant = 0;         // what the most recent launch ran: 0 two-heap kernel, 1 merged beam, 2-4 with exact tail
   bool last_exploratory = false;  // ... and whether the adaptive choice was still sampling (not its final pick)
   bool last_shadow = false;       // ... and whether every query had an exact shadow (small launches)
   // host-buffer searches: steady-clock time of launch / of completion (atomic: every lane's caller reports into the handle)
@@ -337,10 +339,10 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
   std::mutex lane_mu;            // (the lock order: above)
   std::atomic<fnv_index_s*> last_served{nullptr};  // the lane that ran the handle's most recent launch (null: the handle itself):
                                                    // fnv_last_kernel_ms / _replayed_queries / _handover_stats read ITS events and counters
-  uint64_t tune_epoch = 0;       // bumped whenever tuner / layouts change: a lane copies them when its own epoch lags
-  uint64_t lane_epoch = ~0ull, lane_options = ~0ull;  // (on a lane: what it last copied from its owner)
+  // (on a lane: its owner's measured.epoch() and options_version when it last copied them; it copies again when either lags)
+  uint64_t lane_epoch = ~0ull, lane_options = ~0ull;
   // (on a replica, round 6) the handle fnv_replica_refresh last copied options from, that handle's options_version then, and
-  // the tune_epoch whose measurements this replica holds: fnv_search_batch_multi hands newer measurements over (pointer
+  // its measured.epoch() whose measurements this replica holds: fnv_search_batch_multi hands newer measurements over (pointer
   // compared, never followed, outside calls that were given the source itself)
   const fnv_index_s* replica_of = nullptr;
   uint64_t replica_options = ~0ull, replica_epoch = ~0ull;

@@ -97,6 +97,80 @@ static fnv_index_s* last_launcher(fnv_index_t ix) {
   return lane ? lane : ix;
 }
 
+// What fnv_tune measures with: its launches on the handle's stream, their times, the candidate layouts, the log.  The
+// tournament itself -- which layout wins, then the variant pass on it -- is tune_layout / tune_variants (measurements.hpp)
+// over this object.
+struct TuneMeter {
+  fnv_index_s* ix;
+  // The batch twice in a row: a launch on rows [off, off + nq) searches the same queries in a rotated order.  Which
+  // queries tie -- and so which ones are stragglers of the last round -- is a property of the queries: timing several
+  // rotations and averaging measures a variant's EXPECTED time, not its luck with one order.
+  const uint8_t* dq2;
+  uint64_t nq;
+  int K, ef_search, num_initializations;
+  SearchOutputs scratch;  // distances | labels, nothing else
+  const int B = std::max(ef_search, K);
+  std::vector<LayoutChoice> cands{1};  // [0]: the rules' (fnv_tune adds their neighbours once the probing launch has planned)
+  const bool tune_log = getenv("FLATNAV_TUNE_LOG") != nullptr;  // developer aid: every measurement on stderr
+  int launch(int variant, uint64_t rotate = 0) {
+    SearchOptions opt;
+    opt.force_variant = variant;
+    opt.timed = true;  // (time reads ev0 / ev1)
+    const size_t qrow_bytes = (size_t)ix->dim * dtype_size(ix->dtype);
+    return search_device_impl(ix, dq2 + (rotate % nq) * qrow_bytes, nq, K, ef_search, num_initializations, scratch, ix->stream, opt);
+  }
+  // Every timed launch starts from cold caches: the SAME queries visit the same nodes launch after launch, so the index
+  // rows and -- above all -- the words of the per-slot HBM visited bitmaps they touch would sit in the 256 MiB Infinity
+  // Cache by the second launch, which flatters exactly the layouts that spill most (small visited tables); a caller's
+  // consecutive batches are different queries.  (Measured: without this the layout choice for 100-d rows at ef=200
+  // flipped between boxes to a 4096-slot table that is 10 % slower under the bench protocol.)
+  struct Flush {
+    void* p = nullptr;
+    size_t bytes = 768u << 20;
+    void open() {
+      const char* flush_env = getenv("FLATNAV_TUNE_FLUSH");  // developer knob: 0 = time warm launches
+      if (flush_env && flush_env[0] == '0') p = nullptr;
+      else if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr;  // (no room: tune warm, as before)
+      (void)hipGetLastError();
+    }
+    ~Flush() { if (p) (void)hipFree(p); }
+  } flush;
+  // mean of `reps` timed launches of one variant, each on another rotation of the batch (after a cold launch), ms per query
+  int time(int v, int reps, float* out) {
+    float sum = 0.f;
+    for (int rep = 0; rep <= reps; rep++) {
+      if (rep > 0 && flush.p) HIP_TRY(hipMemsetAsync(flush.p, rep, flush.bytes, ix->stream));
+      const int r = launch(v, rep == 0 ? 0 : (uint64_t)(rep - 1) * nq / (uint64_t)reps);
+      if (r) return r;
+      HIP_TRY(hipStreamSynchronize(ix->stream));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
+      if (rep > 0) sum += ms;  // the first launch of a kernel is a cold one
+    }
+    *out = sum / (float)reps / (float)nq;
+    return FNV_OK;
+  }
+  void use_layout(size_t li) {
+    std::lock_guard<std::mutex> lock(ix->mu);
+    ix->measured.set_layout(B, li == 0 ? nullptr : &cands[li]);
+  }
+  bool multi_round() const { return multi_round_launch(ix, ix->plan, nq); }
+  // (each line ends with the per-query values it compared as hex floats: a replay is exact, not rounded to four decimals)
+  void log_layout(size_t li, float t1, float t4) const {
+    if (tune_log)
+      fprintf(stderr, "fnv_tune B=%d layout %zu (heap in LDS %d, table %u): merged %.4f ms, 75%% tail exact %.4f ms -> %u slots, %d per CU [%a %a, %u heap entries]\n", B,
+              li, (int)cands[li].cand_lds, cands[li].vis_slots, t1 * (float)nq, t4 * (float)nq, (unsigned)ix->geom[4], (int)ix->geom[3], t1, t4, (unsigned)ix->geom[5]);
+  }
+  void log_duel(int rounds, size_t li, float sum_c, size_t holder, float sum_b, bool wins) const {
+    if (tune_log) fprintf(stderr, "fnv_tune B=%d duel (%d round%s): layout %zu %.4f ms against layout %zu %.4f ms -> %s [%a %a]\n", B, rounds, rounds == 1 ? "" : "s",
+                          li, sum_c / (float)rounds * (float)nq, holder, sum_b / (float)rounds * (float)nq,
+                          wins ? "challenger" : "holder", sum_c / (float)rounds, sum_b / (float)rounds);
+  }
+  void log_variant(int v, float t) const {
+    if (tune_log) fprintf(stderr, "fnv_tune B=%d variant %d: %.4f ms [%a]\n", B, v, t * (float)nq, t);
+  }
+};
+
 // Only the C ABI is exported (the library is built with -fvisibility=hidden).
 #pragma GCC visibility push(default)
 extern "C" {
@@ -120,104 +194,30 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
     if (!rc) rc = ix->d_out.grow(obytes);
     if (rc) return rc;
   }
-  // The batch twice in a row: a launch on rows [off, off + nq) searches the same queries in a rotated order.  Which
-  // queries tie -- and so which ones are stragglers of the last round -- is a property of the queries: timing several
-  // rotations and averaging measures a variant's EXPECTED time, not its luck with one order.
-  uint8_t* dq2 = ix->d_q.as<uint8_t>();
+  uint8_t* dq2 = ix->d_q.as<uint8_t>();  // (the batch twice in a row: TuneMeter)
   HIP_TRY(hipMemcpy(dq2, queries, qbytes, queries_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dq2 + qbytes, dq2, qbytes, hipMemcpyDeviceToDevice));
-  const size_t qrow_bytes = (size_t)ix->dim * dtype_size(ix->dtype);
-  SearchOutputs scratch;  // distances | labels, nothing else
+  SearchOutputs scratch;
   scratch.dist = ix->d_out.as<float>();
   scratch.labels = (int32_t*)(ix->d_out.as<uint8_t>() + o_lab);
-  auto launch = [&](int variant, uint64_t rotate = 0) -> int {
-    SearchOptions opt;
-    opt.force_variant = variant;
-    opt.timed = true;  // (time_variant reads ev0 / ev1)
-    return search_device_impl(ix, dq2 + (rotate % nq) * qrow_bytes, nq, K, ef_search, num_initializations, scratch, ix->stream, opt);
-  };
+  TuneMeter gpu{ix, dq2, nq, K, ef_search, num_initializations, scratch};
   // what kind of launch is this?  (one probing launch of the merged-beam kernel tells: plan, round size)
-  const int B = std::max(ef_search, K);
+  const int B = gpu.B;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    ix->layouts.erase(B);
-    ix->tuner.erase(tuner_key(B, false));
-    ix->tuner.erase(tuner_key(B, true));
-    ix->plan.valid = false;
-    ix->tune_epoch++;  // (whatever follows -- including the early return below -- lanes drop their copy of the old choice)
+    ix->measured.forget(B);  // (whatever follows -- including the early return below -- lanes drop their copy of the old choice)
   }
-  int rc = launch(1);
+  int rc = gpu.launch(1);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(ix->stream));
   if (ix->geom[6] == MODE_HEAPS || ix->sorted_beam != 2 || ix->sorted_variant >= 0 || nq < 2048) return FNV_OK;  // nothing to choose
-  // Every timed launch starts from cold caches: the SAME queries visit the same nodes launch after launch, so the index
-  // rows and -- above all -- the words of the per-slot HBM visited bitmaps they touch would sit in the 256 MiB Infinity
-  // Cache by the second launch, which flatters exactly the layouts that spill most (small visited tables); a caller's
-  // consecutive batches are different queries.  (Measured: without this the layout choice for 100-d rows at ef=200
-  // flipped between boxes to a 4096-slot table that is 10 % slower under the bench protocol.)
-  struct Flush {
-    void* p = nullptr;
-    size_t bytes = 768u << 20;
-    ~Flush() { if (p) (void)hipFree(p); }
-  } flush;
-  const char* flush_env = getenv("FLATNAV_TUNE_FLUSH");  // developer knob: 0 = time warm launches
-  if (flush_env && flush_env[0] == '0') flush.p = nullptr;
-  else if (hipMalloc(&flush.p, flush.bytes) != hipSuccess) flush.p = nullptr;  // (no room: tune warm, as before)
-  (void)hipGetLastError();
-  // mean of `reps` timed launches of one variant, each on another rotation of the batch (after a cold launch), ms per query
-  auto time_variant = [&](int v, int reps, float* out) -> int {
-    float sum = 0.f;
-    for (int rep = 0; rep <= reps; rep++) {
-      if (rep > 0 && flush.p) HIP_TRY(hipMemsetAsync(flush.p, rep, flush.bytes, ix->stream));
-      const int r = launch(v, rep == 0 ? 0 : (uint64_t)(rep - 1) * nq / (uint64_t)reps);
-      if (r) return r;
-      HIP_TRY(hipStreamSynchronize(ix->stream));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-      if (rep > 0) sum += ms;  // the first launch of a kernel is a cold one
-    }
-    *out = sum / (float)reps / (float)nq;
-    return FNV_OK;
-  };
-
-  // ---- 1. the LDS layout ------------------------------------------------------------------------------------------
-  // Resident queries, visited-table slots and the LDS home of the exact search's candidates heap trade against each
-  // other, and which trade wins depends on the data (how often queries tie, how many ids a query visits): rules cover
-  // the common cases (configure_launch), this measures the neighbours of the rule's choice -- heap home flipped, the
-  // table one size up / down -- with the merged-beam kernel alone and with its whole last round straight to the exact
-  // search, and keeps the fastest.  Skipped for whatever the caller pinned with an option.
   // (from the plan, not from the probing launch's geometry record: a DIRECT launch reports its bitmap's bits there)
-  uint32_t base_slots = 0, base_vis_w = 0;
-  bool base_heap_lds = false;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    base_slots = ix->plan.sorted.vis_slots;
-    base_vis_w = ix->plan.sorted.vis_w;
-    base_heap_lds = ix->plan.sorted.cand_slots != 0;
+    const SearchParams& rules = ix->plan.sorted;
+    gpu.cands = tune_layout_candidates(ix, rules.vis_slots, rules.vis_w, rules.cand_slots != 0);
   }
-  const std::vector<LayoutChoice> cands = tune_layout_candidates(ix, base_slots, base_vis_w, base_heap_lds);
-  const bool tune_log = getenv("FLATNAV_TUNE_LOG") != nullptr;  // developer aid: every measurement on stderr
-  size_t best_layout = 0;
-  float best_layout_t = -1.f;
-  // one layout's time: the better of the merged-beam kernel alone and with 75 % of its last round straight to the exact search
-  auto time_layout = [&](size_t li, float* out) -> int {
-    {
-      std::lock_guard<std::mutex> lock(ix->mu);
-      if (li == 0) ix->layouts.erase(B);
-      else ix->layouts[B] = cands[li];
-      ix->plan.valid = false;
-    }
-    float t1 = -1.f, t4 = -1.f;
-    int r = time_variant(1, 4, &t1);
-    if (r) return r;
-    const bool multi = multi_round_launch(ix, ix->plan, nq);
-    if (multi && ix->sorted_tail_exact_pct < 0 && (r = time_variant(3, 4, &t4)) != FNV_OK) return r;
-    *out = (t4 > 0.f && t4 < t1) ? t4 : t1;
-    if (tune_log)
-      fprintf(stderr, "fnv_tune B=%d layout %zu (heap in LDS %d, table %u): merged %.4f ms, 75%% tail exact %.4f ms -> %u slots, %d per CU\n", B,
-              li, (int)cands[li].cand_lds, cands[li].vis_slots, t1 * (float)nq, t4 * (float)nq, (unsigned)ix->geom[4], (int)ix->geom[3]);
-    return FNV_OK;
-  };
+  gpu.flush.open();
   // The device settles first.  After the GPU has idled (the caller computed something on the host) the first launches run
   // up to 70 % slower than the steady state, for about 0.3 s of work -- clocks and power state (measured inside bench.py:
   // the rules' layout, timed first, lost to a neighbour it beats by 10 %; launches of 8.3 ms that take 4.8 ms half a second
@@ -228,76 +228,27 @@ int fnv_tune(fnv_index_t ix, const void* queries, uint64_t nq, int queries_on_de
     float prev = -1.f;
     for (int i = 0; i < 400; i++) {
       float t = 0.f;
-      if (time_variant(1, 1, &t) != FNV_OK) break;
+      if (gpu.time(1, 1, &t) != FNV_OK) break;
       const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-      if (tune_log) fprintf(stderr, "fnv_tune B=%d settling: %.4f ms (at %.2f s)\n", B, t * (float)nq, waited);
+      if (gpu.tune_log) fprintf(stderr, "fnv_tune B=%d settling: %.4f ms (at %.2f s)\n", B, t * (float)nq, waited);
       if ((waited > 0.5 && prev > 0.f && fabsf(t - prev) < 0.02f * prev) || waited > 2.0) break;
       prev = t;
     }
   }
-  bool won_by_duel = false;
-  for (size_t li = 0; li < cands.size(); li++) {
-    float t = -1.f;
-    if (time_layout(li, &t) != FNV_OK) continue;  // e.g. a layout that does not fit LDS: not a candidate
-    if (best_layout_t < 0.f || t < best_layout_t * 0.95f) {  // a neighbour must win by 5 %: less is box-to-box noise (round 4: a 2 % margin picked layouts that lost 5 % under the bench protocol)
-      best_layout_t = t;
-      best_layout = li;
-      won_by_duel = false;
-    } else if (t < best_layout_t * 0.985f) {
-      // Inside the margin (round 6): ONE measurement cannot tell 2-4 % from drift, several that agree can -- the holder and the
-      // challenger are timed twice more, alternately; the challenger takes over if it wins BOTH rounds by 1 % (round 5 saw
-      // layouts that were 2-2.5 % faster on every box stay unused: 10M x 768 at 8192 slots; the means of four cold launches
-      // repeat within 0.3 % -- 90.4 / 90.8 ms against 93.0 / 92.3 ms in the tune log behind profiles/r6_bench.json).
-      float sum_b = 0.f, sum_c = 0.f;
-      bool wins = true;
-      int rounds = 0;
-      for (; rounds < 2 && wins; rounds++) {
-        float tb = -1.f, tc = -1.f;
-        if (time_layout(best_layout, &tb) != FNV_OK || time_layout(li, &tc) != FNV_OK) wins = false;
-        else wins = tc < tb * 0.99f;
-        sum_b += tb;
-        sum_c += tc;
-      }
-      if (tune_log) fprintf(stderr, "fnv_tune B=%d duel (%d round%s): layout %zu %.4f ms against layout %zu %.4f ms -> %s\n", B, rounds, rounds == 1 ? "" : "s",
-                            li, sum_c / (float)rounds * (float)nq, best_layout, sum_b / (float)rounds * (float)nq,
-                            wins ? "challenger" : "holder");
-      if (wins) {
-        best_layout_t = sum_c / (float)rounds;
-        best_layout = li;
-        won_by_duel = true;
-      }
-    }
-  }
-  if (best_layout != 0 && !won_by_duel) {  // a neighbour won on one measurement: the rules' layout was timed first, so it is timed once more, now last
-    float again = -1.f;
-    if (time_layout(0, &again) == FNV_OK && !(best_layout_t < again * 0.95f)) best_layout = 0;
-  }
-  {
-    std::lock_guard<std::mutex> lock(ix->mu);
-    if (best_layout == 0) ix->layouts.erase(B);
-    else ix->layouts[B] = cands[best_layout];
-    ix->plan.valid = false;
-    ix->tune_epoch++;
-  }
-  rc = launch(1);  // re-plan with the chosen layout
+  // ---- 1. the LDS layout
+  const bool try_tail = ix->sorted_tail_exact_pct < 0;
+  gpu.use_layout(tune_layout(gpu, gpu.cands.size(), try_tail));
+  rc = gpu.launch(1);  // re-plan with the chosen layout
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(ix->stream));
-
-  // ---- 2. the kernel variant on that layout --------------------------------------------------------------------------
-  const bool multi_round = multi_round_launch(ix, ix->plan, nq);
+  // ---- 2. the kernel variant on that layout
+  const bool multi_round = gpu.multi_round();
   Tuner t;
-  for (int v = 0; v < kNumVariants; v++) {
-    if (!variant_allowed(v, multi_round, ix->sorted_tail_exact_pct < 0, ix->shadow_exact != 0)) continue;
-    rc = time_variant(v, 4, &t.best[v]);
-    if (rc) return rc;
-    if (tune_log) fprintf(stderr, "fnv_tune B=%d variant %d: %.4f ms\n", B, v, t.best[v] * (float)nq);
-    t.samples[v] = 4;  // settled: later launches neither explore nor sample
-  }
+  rc = tune_variants(gpu, multi_round, try_tail, ix->shadow_exact != 0, &t);
+  if (rc) return rc;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    ix->tuner[tuner_key(B, multi_round)] = t;
-    ix->sample_kernel = -1;
-    ix->tune_epoch++;
+    ix->measured.settle(tuner_key(B, multi_round), t);
   }
   return check_device_status(ix);
 }
@@ -331,7 +282,7 @@ int fnv_gather_ceiling(fnv_index_t ix, int waves_per_cu, double* gbps_out) {
   HIP_TRY(hipEventSynchronize(ix->ev1));
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ix->ev0, ix->ev1));
-  ix->sample_kernel = -1;  // ev0 / ev1 no longer bracket a search launch
+  ix->measured.drop_pending();  // ev0 / ev1 no longer bracket a search launch
   *gbps_out = rows_per_iter * (double)iters * (double)ix->row_bytes / 1e9 / ((double)ms / 1e3);
   return FNV_OK;
 }
