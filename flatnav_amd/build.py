@@ -3,7 +3,8 @@
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container as well as on the MI355X box.
 The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 104
 objects (kernel_inst.hip: 13 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
-half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
+half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), four for the exhaustive search's matrix engine (MATRIX_FAMILY x uint8 / int8
+x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
 C ABI, the non-template kernels), one object each in the same pool, and linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
 from __future__ import annotations
@@ -20,7 +21,8 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
                                            "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "runtime.hpp",
-                                           "launch_plan.hpp", "measurements.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp")] + [
+                                           "launch_plan.hpp", "measurements.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp",
+                                           "scan_matrix.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
 # The host units behind runtime.hpp, which brings launch_plan.hpp with measurements.hpp (kernel units include none) and, through kernel_table.h,
 # the device headers that say what a launch passes.  Each unit with the kernel headers it includes on top of those (launch.hip:
@@ -41,6 +43,9 @@ FAMILIES = [(0, "exact"), (3, "wire"), (4, "merged"), (5, "merged1"), (6, "merge
 # the row format f32h (csrc/half_rows.hpp; kernel_table.h's FNV_FOR_EACH_HALF_ROWS_FAMILY): the families that read mirror rows
 HALF_ROWS_TYPE = ("fnv_dev::f32h", "f32h")
 HALF_ROWS_FAMILIES = [f for f in FAMILIES if f[0] == 0 or 4 <= f[0] <= 11]  # exact, merged beam and its DIRECT forms
+# the exhaustive search's matrix engine (csrc/scan_matrix.hpp; kernel_table.h's FNV_FOR_EACH_MATRIX_TYPE_METRIC): 1-byte types only
+MATRIX_FAMILY = (15, "scan_m")
+MATRIX_TYPES = [("uint8_t", "u8"), ("int8_t", "i8")]
 
 
 def hipcc() -> str:
@@ -56,7 +61,8 @@ def _units(defines):
     if "FNV_DEV_FAST_BUILD" in defines:  # developer build: the host units only, one instantiation per kernel (launch.hip)
         return [(o, s, f + ["-D" + d for d in defines]) for o, s, f in units]
     for (ctype, tag), families, extra in [(t, FAMILIES, []) for t in TYPES] + [(HALF_ROWS_TYPE, HALF_ROWS_FAMILIES,
-                                                                                 ["-DFNV_INST_HALF_ROWS"])]:
+                                                                                 ["-DFNV_INST_HALF_ROWS"])] + [
+                                                                                     (t, [MATRIX_FAMILY], []) for t in MATRIX_TYPES]:
         for metric, mtag in METRICS:
             for fam, fname in families:
                 units.append((os.path.join(OBJ, "inst_%s_%s_%s.o" % (fname, tag, mtag)), INST,

@@ -4,13 +4,16 @@
 // flatnav_amd/build.py compiles the 104 combinations in parallel and links them with the host units -- and eighteen more for the
 // row format f32h (float32 queries on the half-width mirror, half_rows.hpp; -DFNV_INST_T=fnv_dev::f32h -DFNV_INST_HALF_ROWS):
 // the exact family (without the entry scan) and the merged-beam families with their DIRECT forms, for the row configurations
-// a mirror exists for.
+// a mirror exists for -- and four for family 15 (scan_m: the exhaustive search's matrix engine, uint8 / int8 x the metrics).
 #include <hip/hip_runtime.h>
 
 #include "kernel_table.h"
 #include "kernels.hpp"
 #include "merged_beam.hpp"
 #include "scan.hpp"
+#if FNV_INST_FAMILY == 15
+#include "scan_matrix.hpp"
+#endif
 #include "wire.hpp"
 
 #define FNV_CAT_(a, b, c, d, e, f) a##b##c##d##e##f
@@ -42,6 +45,9 @@ constexpr int METRIC = FNV_INST_METRIC;
   slot[7][FULL] = K<T, METRIC, 8, 3, FULL __VA_ARGS__>;
 #endif
 
+#if FNV_INST_FAMILY == 15  // the matrix engine of the exhaustive search (1-byte element types): one kernel, run-time row geometry
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_m = exhaustive_scan_matrix_kernel<T, METRIC>; }
+#else
 template <bool FULL>
 static void fill_rows(KernelTable& t) {
 #if FNV_INST_FAMILY == 0
@@ -72,5 +78,6 @@ void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTab
 #endif
   fill_rows<true>(t);
 }
+#endif
 
 }  // namespace fnv_dev

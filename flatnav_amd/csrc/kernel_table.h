@@ -24,6 +24,7 @@ struct KernelTable {
   wire_fn connect[kNumCfgs][2];        // wire_connect_kernel
   scan_fn flat[kNumCfgs][2];           // exhaustive_scan_kernel (scan.hpp: the exhaustive search)
   scan_grouped_fn flat_g[kNumCfgs][2]; // exhaustive_scan_grouped_kernel (... with one filter per query)
+  scan_fn flat_m;                      // exhaustive_scan_matrix_kernel (scan_matrix.hpp; uint8 / int8 only, else null): row geometry is run-time
 };
 
 // X(element type, type tag, metric ordinal, metric tag)
@@ -50,12 +51,19 @@ struct KernelTable {
   X(7, merged2, __VA_ARGS__) X(8, merged_d, __VA_ARGS__) X(9, merged1_d, __VA_ARGS__) X(10, merged0_d, __VA_ARGS__)      \
   X(11, merged2_d, __VA_ARGS__)
 
+// Family 15, the exhaustive search's matrix engine (scan_matrix.hpp): one kernel per (1-byte element type, metric), no row
+// configurations; the float types' tables keep a null slot.  X(element type, type tag, metric ordinal, metric tag)
+#define FNV_FOR_EACH_MATRIX_TYPE_METRIC(X) X(uint8_t, u8, 0, l2) X(uint8_t, u8, 1, ip) X(int8_t, i8, 0, l2) X(int8_t, i8, 1, ip)
+
 #define FNV_DECLARE_FILLER(ordinal, family, tag, mtag) void fill_##family##_##tag##_##mtag(KernelTable& t);
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_FOR_EACH_FAMILY(FNV_DECLARE_FILLER, tag, mtag)
 FNV_FOR_EACH_TYPE_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #define FNV_DECLARE_FILLERS(M, mtag) FNV_FOR_EACH_HALF_ROWS_FAMILY(FNV_DECLARE_FILLER, f32h, mtag)
 FNV_FOR_EACH_HALF_ROWS_METRIC(FNV_DECLARE_FILLERS)
+#undef FNV_DECLARE_FILLERS
+#define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_DECLARE_FILLER(15, scan_m, tag, mtag)
+FNV_FOR_EACH_MATRIX_TYPE_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #undef FNV_DECLARE_FILLER
 

@@ -9,6 +9,9 @@
 #include "merged_beam.hpp"
 #endif
 #include "scan.hpp"
+#ifdef FNV_DEV_FAST_BUILD
+#include "scan_matrix.hpp"
+#endif
 
 namespace fnv_dev {
 
@@ -119,6 +122,8 @@ const KernelTable& kernel_table(int, int, bool = false) {
         k.flat[c][f] = FNV_DEV_KERNEL(exhaustive_scan_kernel);
         k.flat_g[c][f] = FNV_DEV_KERNEL(exhaustive_scan_grouped_kernel);
       }
+    k.flat_m = nullptr;
+    if constexpr (sizeof(FNV_DEV_T) == 1) k.flat_m = exhaustive_scan_matrix_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
     return k;
   }();
   return t;
@@ -146,6 +151,11 @@ const KernelTable& kernel_table(int dtype, int metric, bool half_rows = false) {
     FNV_FOR_EACH_HALF_ROWS_METRIC(FNV_FILL)
 #undef FNV_FILL
 #undef FNV_FILL_FAMILY
+    // the matrix engine of the exhaustive search: the 1-byte types' tables (tables[2 .. 5], in this order) only
+    i = 2;
+#define FNV_FILL(T, tag, M, mtag) fill_scan_m_##tag##_##mtag(tables[i++]);
+    FNV_FOR_EACH_MATRIX_TYPE_METRIC(FNV_FILL)
+#undef FNV_FILL
   });
   if (half_rows) return tables[8 + (metric == FNV_METRIC_IP ? 1 : 0)];
   int t;  // order of FNV_FOR_EACH_TYPE_METRIC; every caller has passed validate_geometry (dtype_size != 0)
@@ -509,9 +519,11 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const RowGeometry g = row_geometry(ix);
   const bool grouped = filter && filter->grouped, listed = filter && !grouped;
 
-  // -- shape
-  const ScanShape shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
-  if (shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
+  // -- shape: the vector scan's, or -- an ungrouped call the matrix engine takes ("scan_matrix") -- that engine's
+  const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
+  if (vector_shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
+  const ScanMatrixShape matrix = grouped ? ScanMatrixShape() : scan_matrix_shape(ix, g, nq, K, live);
+  const ScanShape shape = matrix.on ? static_cast<const ScanShape&>(matrix) : vector_shape;
   const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
   // -- workspace
@@ -542,7 +554,8 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
     rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full], gp, shape, nq, stream);
     if (rc) return rc;
   } else {
-    const scan_fn kern = kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
+    const scan_fn kern = matrix.on ? kernel_table(ix->dtype, ix->metric).flat_m : kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
+    if (!kern) return fail(FNV_ERR_RUNTIME, "the matrix scan kernel of this element type is missing from the build");
     HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
     hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp.s);
     HIP_TRY(hipGetLastError());
@@ -552,9 +565,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   HIP_TRY(hipEventRecord(ix->ev1, stream));
 
   // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
-  // queue, row segments)
-  record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped ? shape.tile : 0,
-                grouped ? SCAN_QUEUE_IDS : 0, grouped ? shape.segments : 0, 3, 0);
+  // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments)
+  record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
+                grouped ? SCAN_QUEUE_IDS : 0, grouped || matrix.on ? shape.segments : 0, matrix.on ? 4 : 3, 0);
   return FNV_OK;
 }
 

@@ -48,6 +48,7 @@ struct IndexOptions {
   int64_t half_rows = 1;  // searches read the half-width mirror of a float32 table while one is live (half_rows.hpp)
   int64_t overflow_list = -1;  // -1: automatic (a list in HBM only when the bitmap is larger than 512 KB)
   int64_t scan_segment_rows = 0;  // exhaustive search: candidate rows per block's segment (0: automatic)
+  int64_t scan_matrix = 0;  // exhaustive search on uint8 / int8 indexes: the matrix engine where it applies (scan_matrix_shape)
   // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
   // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
   int64_t filter_scan_max = 0, filter_scan_on_overflow = 0;
@@ -611,6 +612,20 @@ constexpr uint32_t kScanMaxLds = 160u << 10;  // one query and its list must fit
 struct ScanShape {
   uint32_t tile, tiles, segments, lds;
 };
+// The row segments of a launch of `tiles` query tiles: the rule of both scan engines.  `fill`: the segments that fill the
+// device, the engine's own count (the vector scan: eight blocks per CU, rounded up).
+inline uint32_t scan_segments(const PlanInputs* ix, uint32_t tiles, uint64_t nq, int K, uint64_t live, uint64_t fill) {
+  uint64_t seg;
+  if (ix->scan_segment_rows > 0) {
+    seg = std::min<uint64_t>((live + (uint64_t)ix->scan_segment_rows - 1) / (uint64_t)ix->scan_segment_rows, kScanForcedSegments);
+  } else {
+    seg = std::min<uint64_t>(std::max<uint64_t>(1, fill), std::max<uint64_t>(1, live / 1024));
+    seg = std::min<uint64_t>(seg, kScanMaxSegments);
+    seg = std::min<uint64_t>(seg, std::max<uint64_t>(1, kScanPartialBudget / (nq * (uint64_t)K * 8u)));
+  }
+  seg = std::min<uint64_t>(seg, 0x7FFFFFFFull / tiles);
+  return (uint32_t)std::max<uint64_t>(1, seg);
+}
 // `filter_rows` != 0: a grouped launch over that many filter rows -- the id queue comes out of the block's LDS budget, and
 // `tiles` is the bound on the data-dependent tile count that the launch covers (scan_select.hpp, group_tile_bound).
 inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows = 0) {
@@ -621,17 +636,43 @@ inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t
   s.tile = (uint32_t)std::min<uint64_t>(s.tile, nq);
   s.lds = s.tile * per_query + queue;
   s.tiles = (uint32_t)(filter_rows ? group_tile_bound(nq, filter_rows, s.tile) : (nq + s.tile - 1) / s.tile);
-  uint64_t seg;
-  if (ix->scan_segment_rows > 0) {
-    seg = std::min<uint64_t>((live + (uint64_t)ix->scan_segment_rows - 1) / (uint64_t)ix->scan_segment_rows, kScanForcedSegments);
-  } else {
-    const uint64_t want_blocks = (uint64_t)std::max(1, ix->num_cus) * 8u;
-    seg = std::min<uint64_t>((want_blocks + s.tiles - 1) / s.tiles, std::max<uint64_t>(1, live / 1024));
-    seg = std::min<uint64_t>(seg, kScanMaxSegments);
-    seg = std::min<uint64_t>(seg, std::max<uint64_t>(1, kScanPartialBudget / (nq * (uint64_t)K * 8u)));
-  }
-  seg = std::min<uint64_t>(seg, 0x7FFFFFFFull / s.tiles);
-  s.segments = (uint32_t)std::max<uint64_t>(1, seg);
+  const uint64_t want_blocks = (uint64_t)std::max(1, ix->num_cus) * 8u;
+  s.segments = scan_segments(ix, s.tiles, nq, K, live, (want_blocks + s.tiles - 1) / s.tiles);
+  return s;
+}
+// The matrix engine (scan_matrix.hpp, exhaustive_scan_matrix_kernel; option "scan_matrix") for an UNGROUPED exhaustive call:
+// whether it takes the call -- the option on, a 1-byte element type, one sub-tile of 32 queries with their lists within a
+// block's LDS -- and the launch it then gets: a tile of whole sub-tiles (as many as kScanMatrixLdsBudget holds, at most
+// kScanMatrixMaxTile and no more than the call has; one sub-tile for rows longer than the kernel keeps in registers, so that
+// no row is read twice by a block), one wavefront per block, the segments of scan_segments.  LDS per query of the tile: its
+// ceil(chunks / 2) MFMA steps of 32 bytes (the row's table chunks and the side table's), its list, its int32 term.
+// Segments that fill the device: as many as keep the whole grid resident at once -- the blocks a CU holds by LDS granules, at
+// most kScanMatrixWavesPerCu by registers -- rounded DOWN: every further segment costs each query K ln(n / K) more list
+// insertions, and a second, partly filled round of blocks costs more than the first round's idle slots.
+constexpr uint32_t kScanMatrixN = 32, kScanMatrixMaxTile = 128, kScanMatrixSpanSteps = 4;
+constexpr uint32_t kScanMatrixLdsBudget = 32u << 10;  // five blocks per CU
+constexpr uint32_t kScanMatrixWavesPerCu = 8;         // two wavefronts per SIMD, the vector scan's figure (registers allow three)
+struct ScanMatrixShape : ScanShape {
+  bool on = false;
+  uint32_t block = 0;  // threads per block
+};
+inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
+  ScanMatrixShape s;
+  s.tile = s.tiles = s.segments = s.lds = 0;
+  if (ix->scan_matrix == 0 || (ix->dtype != FNV_DTYPE_UINT8 && ix->dtype != FNV_DTYPE_INT8) || nq == 0) return s;
+  const uint32_t steps = (g.nchunks + g.tail_chunks + 1u) / 2u;
+  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + 4u;
+  if (kScanMatrixN * per_query > kScanMaxLds) return s;
+  uint32_t subtiles = std::max(1u, std::min(kScanMatrixMaxTile, kScanMatrixLdsBudget / per_query) / kScanMatrixN);
+  if (steps > kScanMatrixSpanSteps) subtiles = 1;
+  subtiles = (uint32_t)std::min<uint64_t>(subtiles, (nq + kScanMatrixN - 1) / kScanMatrixN);
+  s.on = true;
+  s.block = WAVE;
+  s.tile = subtiles * kScanMatrixN;
+  s.lds = s.tile * per_query;
+  s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);
+  const uint64_t per_cu = std::min<uint64_t>(kScanMatrixWavesPerCu, kLdsPerCu / lds_allocated(s.lds));
+  s.segments = scan_segments(ix, s.tiles, nq, K, live, (uint64_t)std::max(1, ix->num_cus) * per_cu / s.tiles);
   return s;
 }
 // The partial lists of a launch: one sorted list of K keys per (query, segment); the merge's LDS: three such lists.

@@ -567,8 +567,11 @@ class DeviceIndex:
         check(lib().fnv_last_launch_geometry(self._h, g))
         keys = ["grid_blocks", "block_threads", "lds_bytes", "blocks_per_cu", "visited_slots", "cand_slots"]
         out = {k: int(g[i]) for i, k in enumerate(keys)}
-        out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds", "exhaustive_scan"][int(g[6])]
+        out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds", "exhaustive_scan", "exhaustive_scan_matrix"][int(g[6])]
+        out["kernel_mode"] = int(g[6])  # fnv_last_launch_geometry's own ordinal (4: the exhaustive search's matrix engine)
         out["tail_exact"] = int(g[7])
+        if int(g[6]) == 4:
+            out["tile_queries"], out["segments"] = int(g[3]), int(g[5])
         if int(g[6]) == 3 and int(g[4]):  # the grouped scan reports its tiling in the slots the graph search's layout uses
             out["tile_queries"], out["queue_ids"], out["segments"] = int(g[3]), int(g[4]), int(g[5])
         return out

@@ -370,6 +370,13 @@ class Index {
     std::lock_guard<std::mutex> g(_mirror.mutex());
     _mirror.setFilterRouting(scan_max_allowed, scan_on_overflow);
   }
+  // The matrix engine of searchBatchExhaustive (flatnav_hip.h, option "scan_matrix"): on uint8 and int8 indexes the unfiltered
+  // and the single-filter exhaustive search score rows on the matrix cores -- the same bytes, sooner; every other call runs as
+  // before.  Applies to the device mirror now if there is one, and to every mirror made later.
+  void setExhaustiveMatrix(bool on) {
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    _mirror.setExhaustiveMatrix(on);
+  }
   // The C-ABI handle of the device mirror (valid until the next mutation); for callers that drive
   // fnv_search_batch_device on their own buffers / streams.
   fnv_index_t deviceHandle() {

@@ -251,6 +251,9 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *   "scan_segment_rows"  exhaustive search (fnv_search_batch_exhaustive): candidate rows that one block's row segment covers;
  *                     0 (default) = automatic (enough segments to fill the device, at most 64); tests force many segments and
  *                     a real merge on a small index with it (at most 1024 segments).  Same bytes.
+ *   "scan_matrix"     exhaustive search: 1 = the matrix engine (see fnv_search_batch_exhaustive, "Matrix engine"; default 0 = off):
+ *                     on uint8 / int8 indexes the unfiltered and the single-filter call score rows with the int8 matrix
+ *                     instructions; every other call runs the vector scan.  Same bytes.  Read per launch; keeps what fnv_tune measured.
  *   "filter_scan_max"  filter routing (see "Filter routing" below; default 0 = off): in fnv_search_batch_filtered[_grouped][_device] a
  *                     query whose filter allows at most this many live nodes is answered by the exhaustive scan instead of
  *                     the graph search.  Keeps what fnv_tune / the adaptive choice measured, as the next one does.
@@ -364,6 +367,15 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     call (given back with it): nq x K x S x 8 bytes of partial result lists, S = row segments <= 64, chosen so that the lists
  *     stay within 256 MB whenever S > 1 ("scan_segment_rows" forces S, up to 1024); filtered calls add capacity / 8 bytes (node
  *     bitmap) + 4 x capacity + 16 bytes (allowed node ids).
+ *   Matrix engine (option "scan_matrix" = 1): on a uint8 or int8 index the scan of these two calls scores rows 32 x 32 at a
+ *     time with v_mfma_i32_32x32x32_i8 and writes EXACTLY the bytes it writes with the option off -- results, distance bits,
+ *     padding, out_count, out_ndist, the (distance, node id) order -- for every row layout, segmentation, K and nq: a 1-byte
+ *     distance is a function of an exact int32 sum, which no order of addition changes (uint8 rows go through the signed
+ *     instruction as x - 128, with exact integer corrections).  The option never makes a valid call invalid; the vector scan
+ *     answers where the engine does not apply: float32 and float16 indexes (their sums are order-dependent), the _grouped calls,
+ *     the scan stage of a routed filtered graph search, and shapes whose 32 queries with their K-entry lists exceed a block's
+ *     LDS (K x row length too large).  fnv_last_launch_geometry then reports {grid_blocks, 64, lds_bytes, queries per tile, 0,
+ *     row segments, kernel = 4, 0}.
  * fnv_search_batch_exhaustive: host buffers (allowed_bits included); thread safety and lanes as fnv_search_batch.
  * fnv_search_batch_exhaustive_device: every buffer, allowed_bits included, in the index's device memory, enqueued on `hip_stream`
  *   without synchronising; one launch in flight per handle, as fnv_search_batch_device.
@@ -495,7 +507,7 @@ int fnv_last_replayed_queries(fnv_index_t index, uint64_t out[5]);
 
 /* Launch geometry of the most recent search: geom[8] = {grid_blocks, block_threads, lds_bytes,
  * blocks_per_cu, visited_slots, cand_slots (LDS entries of the exact search's candidates heap), kernel: 0 = two-heap
- * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, tail_exact: the last that-many queries of the launch
+ * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, tail_exact: the last that-many queries of the launch
  * went straight to the exact search (merged-beam kernel, see the "sorted_tail_exact_pct" option)}.
  * blocks_per_cu = the query slots a CU keeps resident = the grid's share per CU (round 5; gfx950 hands LDS out in 1280-byte
  * granules, so this is min(what the HIP occupancy API counts, 163840 / (ceil(lds_bytes / 1280) * 1280)); rounds 1-4 launched the

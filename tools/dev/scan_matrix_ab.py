@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Developer tool: the exhaustive search's two engines -- the vector scan and the matrix engine ("scan_matrix" = 1,
+csrc/scan_matrix.hpp) -- on ONE c2-uint8-like index, same handle, same process, alternating.
+
+  python tools/dev/scan_matrix_ab.py [--n 1000000] [--nq 10000] [--fractions 1,0.1,0.01,0.001] [--rounds 3] [--steps 5] [--json out.json]
+
+The SIFT-1M stand-in as uint8 (flatnav_amd.datasets.sift_like; rows stored without a graph: the scan does not read one),
+device-resident queries, K = 10.  For every fraction of allowed labels (1 = unfiltered; else a random set) it times, HIP
+events on the launch stream, `--rounds` rounds of `--steps` launches per engine, vector then matrix in every round.  Per line:
+each engine's median, min and max over the rounds, the ratio of the medians, whether the matrix median lies below the vector
+median by more than the vector engine's own max - min, the matrix engine's launch shape, its achieved integer op rate
+(2 * nq * candidates * padded dim) against the 5033 TOP/s int8 matrix peak (256 CUs x 4 SIMDs x 1024 MAC per cycle at 2.4 GHz)
+and the row bytes it moves (ceil(nq / tile) * candidates * row_bytes).  Before timing, both engines' outputs are compared byte
+for byte at every fraction."""
+import argparse
+import ctypes
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import flatnav_amd as flatnav  # noqa: E402
+from flatnav_amd import datasets as ds  # noqa: E402
+from flatnav_amd import hip  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--n", type=int, default=1_000_000)
+ap.add_argument("--nq", type=int, default=10_000)
+ap.add_argument("--fractions", default="1,0.1,0.01,0.001")
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--steps", type=int, default=5)
+ap.add_argument("--json", default="")
+args = ap.parse_args()
+
+N, NQ, K, DIM, ROW_BYTES = args.n, args.nq, 10, 128, 128
+PEAK_TOPS = 5033.0
+dev_t = torch.device("cuda", 0)
+torch.cuda.set_device(0)
+X, Q = ds.sift_like(N, NQ)
+index = flatnav.index.create("l2", DIM, N, 32, flatnav.data_type.DataType.uint8)
+index.set_device(0)
+index.allocate_nodes(X.astype(np.uint8))
+scan = hip.DeviceIndex(ctypes.c_void_p(index.device_handle()), owned=False)
+tq = torch.from_numpy(Q.astype(np.uint8)).to(dev_t)
+out = {e: (torch.empty((NQ, K), dtype=torch.float32, device=dev_t), torch.empty((NQ, K), dtype=torch.int32, device=dev_t),
+           torch.empty(NQ, dtype=torch.int32, device=dev_t), torch.empty(NQ, dtype=torch.int64, device=dev_t)) for e in (0, 1)}
+stream = torch.cuda.current_stream()
+rng = np.random.default_rng(1)
+
+
+def launch(engine, bits, n_bits):
+    d, l, c, nd = out[engine]
+    scan.set_option("scan_matrix", engine)
+    scan.search_device_exhaustive(tq.data_ptr(), NQ, K, d.data_ptr(), l.data_ptr(), c.data_ptr(), nd.data_ptr(),
+                                  bits_ptr=bits.data_ptr() if n_bits else 0, n_bits=n_bits, use_filter=n_bits > 0,
+                                  stream=stream.cuda_stream)
+
+
+def once(fn, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(stream)
+    for _ in range(steps):
+        fn()
+    b.record(stream)
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+lines = []
+for f in [float(x) for x in args.fractions.split(",")]:
+    rows = np.arange(N) if f >= 1 else np.sort(rng.choice(N, max(1, int(round(f * N))), replace=False))
+    b, n_bits = hip.pack_allowed(rows) if f < 1 else (np.zeros(1, np.uint8), 0)
+    bits = torch.from_numpy(b).to(dev_t)
+    geom = {}
+    for e in (0, 1):  # warm-up, the launch shapes, and the same bytes from both engines
+        once(lambda: launch(e, bits, n_bits), 1)
+        scan.status()
+        geom[e] = scan.launch_geometry()
+    assert geom[0]["kernel_mode"] == 3 and geom[1]["kernel_mode"] == 4, geom
+    for x, y in zip(out[0], out[1]):
+        assert torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y), f
+    assert int((out[1][3] != len(rows)).sum().item()) == 0
+    ms = {0: [], 1: []}
+    for _ in range(args.rounds):
+        for e in (0, 1):
+            ms[e].append(once(lambda: launch(e, bits, n_bits), args.steps))
+    med = {e: statistics.median(ms[e]) for e in (0, 1)}
+    spread = max(ms[0]) - min(ms[0])
+    tile = geom[1]["tile_queries"]
+    ops = 2.0 * NQ * len(rows) * DIM
+    line = dict(fraction=f, candidates=len(rows), vector_ms=ms[0], matrix_ms=ms[1], vector_median=med[0], matrix_median=med[1],
+                ratio=med[0] / med[1], vector_spread=spread, beats_by_more_than_spread=bool(med[0] - med[1] > spread),
+                vector_geometry=geom[0], matrix_geometry=geom[1], matrix_tops=ops / (med[1] * 1e-3) / 1e12,
+                matrix_of_peak=ops / (med[1] * 1e-3) / 1e12 / PEAK_TOPS, matrix_row_bytes=math.ceil(NQ / tile) * len(rows) * ROW_BYTES)
+    lines.append(line)
+    print("f=%-6g cand %8d | vector %9.3f ms [%9.3f .. %9.3f] | matrix %9.3f ms [%9.3f .. %9.3f] | %6.2fx  beats spread: %s | "
+          "matrix grid %d lds %d tile %d segments %d | %.1f TOP/s (%.4f of peak), row bytes %.3e"
+          % (f, len(rows), med[0], min(ms[0]), max(ms[0]), med[1], min(ms[1]), max(ms[1]), line["ratio"], line["beats_by_more_than_spread"],
+             geom[1]["grid_blocks"], geom[1]["lds_bytes"], tile, geom[1]["segments"], line["matrix_tops"], line["matrix_of_peak"],
+             line["matrix_row_bytes"]), flush=True)
+scan.set_option("scan_matrix", 0)
+if args.json:
+    json.dump(lines, open(args.json, "w"), indent=1)
