@@ -4,7 +4,7 @@ hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container
 The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 104
 objects (kernel_inst.hip: 13 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
 half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), four for the exhaustive search's matrix engine (MATRIX_FAMILY x uint8 / int8
-x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
+x 2 metrics) and two for its float16 form (MATRIX_FLOAT_FAMILY x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
 C ABI, the non-template kernels), one object each in the same pool, and linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
 from __future__ import annotations
@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
                                            "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "runtime.hpp",
                                            "launch_plan.hpp", "measurements.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp",
-                                           "scan_matrix.hpp")] + [
+                                           "scan_matrix.hpp", "scan_matrix_f16.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
 # The host units behind runtime.hpp, which brings launch_plan.hpp with measurements.hpp (kernel units include none) and, through kernel_table.h,
 # the device headers that say what a launch passes.  Each unit with the kernel headers it includes on top of those (launch.hip:
@@ -46,6 +46,12 @@ HALF_ROWS_FAMILIES = [f for f in FAMILIES if f[0] == 0 or 4 <= f[0] <= 11]  # ex
 # the exhaustive search's matrix engine (csrc/scan_matrix.hpp; kernel_table.h's FNV_FOR_EACH_MATRIX_TYPE_METRIC): 1-byte types only
 MATRIX_FAMILY = (15, "scan_m")
 MATRIX_TYPES = [("uint8_t", "u8"), ("int8_t", "i8")]
+# ... and its float16 form (csrc/scan_matrix_f16.hpp; FNV_FOR_EACH_MATRIX_FLOAT_METRIC).  Its units are new code and are compiled
+# without packed float32 arithmetic: the per-element fma of distance.hpp rounds the same either way.
+MATRIX_FLOAT_FAMILY = (16, "scan_mf")
+MATRIX_FLOAT_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# headers that one family's units alone include (a change to them leaves every other object current)
+FAMILY_HEADERS = {"scan_matrix.hpp": "scan_m", "scan_matrix_f16.hpp": "scan_mf"}
 
 
 def hipcc() -> str:
@@ -62,7 +68,8 @@ def _units(defines):
         return [(o, s, f + ["-D" + d for d in defines]) for o, s, f in units]
     for (ctype, tag), families, extra in [(t, FAMILIES, []) for t in TYPES] + [(HALF_ROWS_TYPE, HALF_ROWS_FAMILIES,
                                                                                  ["-DFNV_INST_HALF_ROWS"])] + [
-                                                                                     (t, [MATRIX_FAMILY], []) for t in MATRIX_TYPES]:
+                                                                                     (t, [MATRIX_FAMILY], []) for t in MATRIX_TYPES] + [
+                                                                                         (TYPES[3], [MATRIX_FLOAT_FAMILY], MATRIX_FLOAT_FLAGS)]:
         for metric, mtag in METRICS:
             for fam, fname in families:
                 units.append((os.path.join(OBJ, "inst_%s_%s_%s.o" % (fname, tag, mtag)), INST,
@@ -79,7 +86,9 @@ def _stale(obj, src):
     if name in HOST_UNITS:
         deps = [h for h in HEADERS if os.path.basename(h) not in KERNEL_HEADERS or os.path.basename(h) in HOST_UNITS[name]]
     else:  # runtime.hpp, launch_plan.hpp and measurements.hpp (the launch planner) are included by the host units only
-        deps = [h for h in HEADERS if os.path.basename(h) not in HOST_HEADERS]
+        family = os.path.basename(obj)[len("inst_"):].rsplit("_", 2)[0]  # inst_<family>_<type>_<metric>.o
+        deps = [h for h in HEADERS if os.path.basename(h) not in HOST_HEADERS and
+                FAMILY_HEADERS.get(os.path.basename(h), family) == family]
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 
 

@@ -13,6 +13,7 @@ typedef void (*kernel_fn)(const SearchParams);
 typedef void (*wire_fn)(const WireParams);
 typedef void (*scan_fn)(const ScanParams);
 typedef void (*scan_grouped_fn)(const GroupedScanParams);
+typedef void (*scan_mf_fn)(const ScanMatrixFloatParams);
 
 // All kernels for one (element type, metric): [row configuration][FULL rows].
 struct KernelTable {
@@ -25,6 +26,7 @@ struct KernelTable {
   scan_fn flat[kNumCfgs][2];           // exhaustive_scan_kernel (scan.hpp: the exhaustive search)
   scan_grouped_fn flat_g[kNumCfgs][2]; // exhaustive_scan_grouped_kernel (... with one filter per query)
   scan_fn flat_m;                      // exhaustive_scan_matrix_kernel (scan_matrix.hpp; uint8 / int8 only, else null): row geometry is run-time
+  scan_mf_fn flat_mf;                  // exhaustive_scan_matrix_f16_kernel (scan_matrix_f16.hpp; float16 only, else null): likewise
 };
 
 // X(element type, type tag, metric ordinal, metric tag)
@@ -54,6 +56,9 @@ struct KernelTable {
 // Family 15, the exhaustive search's matrix engine (scan_matrix.hpp): one kernel per (1-byte element type, metric), no row
 // configurations; the float types' tables keep a null slot.  X(element type, type tag, metric ordinal, metric tag)
 #define FNV_FOR_EACH_MATRIX_TYPE_METRIC(X) X(uint8_t, u8, 0, l2) X(uint8_t, u8, 1, ip) X(int8_t, i8, 0, l2) X(int8_t, i8, 1, ip)
+// Family 16, its float16 form (scan_matrix_f16.hpp: a matrix-instruction prefilter, survivors rescored in the vector scan's
+// arithmetic): one kernel per metric, for float16 indexes only.  X(metric ordinal, metric tag)
+#define FNV_FOR_EACH_MATRIX_FLOAT_METRIC(X) X(0, l2) X(1, ip)
 
 #define FNV_DECLARE_FILLER(ordinal, family, tag, mtag) void fill_##family##_##tag##_##mtag(KernelTable& t);
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_FOR_EACH_FAMILY(FNV_DECLARE_FILLER, tag, mtag)
@@ -64,6 +69,9 @@ FNV_FOR_EACH_HALF_ROWS_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_DECLARE_FILLER(15, scan_m, tag, mtag)
 FNV_FOR_EACH_MATRIX_TYPE_METRIC(FNV_DECLARE_FILLERS)
+#undef FNV_DECLARE_FILLERS
+#define FNV_DECLARE_FILLERS(M, mtag) FNV_DECLARE_FILLER(16, scan_mf, f16, mtag)
+FNV_FOR_EACH_MATRIX_FLOAT_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #undef FNV_DECLARE_FILLER
 

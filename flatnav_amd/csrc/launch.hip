@@ -11,6 +11,7 @@
 #include "scan.hpp"
 #ifdef FNV_DEV_FAST_BUILD
 #include "scan_matrix.hpp"
+#include "scan_matrix_f16.hpp"
 #endif
 
 namespace fnv_dev {
@@ -124,6 +125,8 @@ const KernelTable& kernel_table(int, int, bool = false) {
       }
     k.flat_m = nullptr;
     if constexpr (sizeof(FNV_DEV_T) == 1) k.flat_m = exhaustive_scan_matrix_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
+    k.flat_mf = nullptr;
+    if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) k.flat_mf = exhaustive_scan_matrix_f16_kernel<FNV_DEV_METRIC>;
     return k;
   }();
   return t;
@@ -155,6 +158,11 @@ const KernelTable& kernel_table(int dtype, int metric, bool half_rows = false) {
     i = 2;
 #define FNV_FILL(T, tag, M, mtag) fill_scan_m_##tag##_##mtag(tables[i++]);
     FNV_FOR_EACH_MATRIX_TYPE_METRIC(FNV_FILL)
+#undef FNV_FILL
+    // ... and its float16 form: the float16 tables (tables[6], tables[7])
+    i = 6;
+#define FNV_FILL(M, mtag) fill_scan_mf_f16_##mtag(tables[i++]);
+    FNV_FOR_EACH_MATRIX_FLOAT_METRIC(FNV_FILL)
 #undef FNV_FILL
   });
   if (half_rows) return tables[8 + (metric == FNV_METRIC_IP ? 1 : 0)];
@@ -519,7 +527,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const RowGeometry g = row_geometry(ix);
   const bool grouped = filter && filter->grouped, listed = filter && !grouped;
 
-  // -- shape: the vector scan's, or -- an ungrouped call the matrix engine takes ("scan_matrix") -- that engine's
+  // -- shape: the vector scan's, or -- an ungrouped call a matrix engine takes ("scan_matrix", "scan_matrix_float") -- that engine's
   const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
   if (vector_shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
   const ScanMatrixShape matrix = grouped ? ScanMatrixShape() : scan_matrix_shape(ix, g, nq, K, live);
@@ -554,10 +562,22 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
     rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full], gp, shape, nq, stream);
     if (rc) return rc;
   } else {
-    const scan_fn kern = matrix.on ? kernel_table(ix->dtype, ix->metric).flat_m : kernel_table(ix->dtype, ix->metric).flat[g.cfg][g.full];
-    if (!kern) return fail(FNV_ERR_RUNTIME, "the matrix scan kernel of this element type is missing from the build");
-    HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
-    hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp.s);
+    const KernelTable& table = kernel_table(ix->dtype, ix->metric);
+    if (matrix.float_rows) {  // the float16 form: the plain block, the rescoring groups, the two counters the memset above cleared
+      const scan_mf_fn kern = table.flat_mf;
+      if (!kern) return fail(FNV_ERR_RUNTIME, "the float16 matrix scan kernel is missing from the build");
+      ScanMatrixFloatParams fp;
+      static_cast<ScanParams&>(fp) = gp.s;
+      fp.group_lanes = matrix.group_lanes;
+      fp.counters = reinterpret_cast<unsigned long long*>(block + fnv_index_s::kScanCounterWord);
+      HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
+      hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, fp);
+    } else {
+      const scan_fn kern = matrix.on ? table.flat_m : table.flat[g.cfg][g.full];
+      if (!kern) return fail(FNV_ERR_RUNTIME, "the matrix scan kernel of this element type is missing from the build");
+      HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
+      hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp.s);
+    }
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(exhaustive_merge_kernel, dim3((unsigned)nq), dim3(WAVE), scan_merge_lds((uint32_t)K), stream, gp.s);
   }
@@ -565,9 +585,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   HIP_TRY(hipEventRecord(ix->ev1, stream));
 
   // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
-  // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments)
+  // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments.  Mode 5: its float16 form, likewise)
   record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
-                grouped ? SCAN_QUEUE_IDS : 0, grouped || matrix.on ? shape.segments : 0, matrix.on ? 4 : 3, 0);
+                grouped ? SCAN_QUEUE_IDS : 0, grouped || matrix.on ? shape.segments : 0, matrix.float_rows ? 5 : matrix.on ? 4 : 3, 0);
   return FNV_OK;
 }
 

@@ -49,6 +49,7 @@ struct IndexOptions {
   int64_t overflow_list = -1;  // -1: automatic (a list in HBM only when the bitmap is larger than 512 KB)
   int64_t scan_segment_rows = 0;  // exhaustive search: candidate rows per block's segment (0: automatic)
   int64_t scan_matrix = 0;  // exhaustive search on uint8 / int8 indexes: the matrix engine where it applies (scan_matrix_shape)
+  int64_t scan_matrix_float = 0;  // ... on float16 indexes: the matrix prefilter with exact rescoring (scan_matrix_f16.hpp)
   // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
   // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
   int64_t filter_scan_max = 0, filter_scan_on_overflow = 0;
@@ -649,25 +650,35 @@ inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t
 // Segments that fill the device: as many as keep the whole grid resident at once -- the blocks a CU holds by LDS granules, at
 // most kScanMatrixWavesPerCu by registers -- rounded DOWN: every further segment costs each query K ln(n / K) more list
 // insertions, and a second, partly filled round of blocks costs more than the first round's idle slots.
-constexpr uint32_t kScanMatrixN = 32, kScanMatrixMaxTile = 128, kScanMatrixSpanSteps = 4;
+// The float16 form (scan_matrix_f16.hpp, exhaustive_scan_matrix_f16_kernel; option "scan_matrix_float") takes float16 indexes
+// by the same rules: a step is two chunks -- sixteen elements -- there as well, the kernel keeps kScanMatrixFloatSpanSteps of
+// them in registers (rows of 256 bytes: 128-d), and a query's terms are two floats, its norm and its share of the margin.
+// It is also told the lanes per vector of the row configuration (`group_lanes`): survivors are rescored in that lane order.
+constexpr uint32_t kScanMatrixN = 32, kScanMatrixMaxTile = 128, kScanMatrixSpanSteps = 4, kScanMatrixFloatSpanSteps = 8;
 constexpr uint32_t kScanMatrixLdsBudget = 32u << 10;  // five blocks per CU
 constexpr uint32_t kScanMatrixWavesPerCu = 8;         // two wavefronts per SIMD, the vector scan's figure (registers allow three)
 struct ScanMatrixShape : ScanShape {
   bool on = false;
   uint32_t block = 0;  // threads per block
+  bool float_rows = false;   // the float16 form
+  uint32_t group_lanes = 0;  // ... and its rescoring groups: kCfgs[cfg].G
 };
 inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
   ScanMatrixShape s;
   s.tile = s.tiles = s.segments = s.lds = 0;
-  if (ix->scan_matrix == 0 || (ix->dtype != FNV_DTYPE_UINT8 && ix->dtype != FNV_DTYPE_INT8) || nq == 0) return s;
+  const bool bytes = ix->scan_matrix != 0 && (ix->dtype == FNV_DTYPE_UINT8 || ix->dtype == FNV_DTYPE_INT8);
+  const bool halves = ix->scan_matrix_float != 0 && ix->dtype == FNV_DTYPE_FLOAT16;
+  if ((!bytes && !halves) || nq == 0) return s;
   const uint32_t steps = (g.nchunks + g.tail_chunks + 1u) / 2u;
-  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + 4u;
+  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + (halves ? 8u : 4u);
   if (kScanMatrixN * per_query > kScanMaxLds) return s;
   uint32_t subtiles = std::max(1u, std::min(kScanMatrixMaxTile, kScanMatrixLdsBudget / per_query) / kScanMatrixN);
-  if (steps > kScanMatrixSpanSteps) subtiles = 1;
+  if (steps > (halves ? kScanMatrixFloatSpanSteps : kScanMatrixSpanSteps)) subtiles = 1;
   subtiles = (uint32_t)std::min<uint64_t>(subtiles, (nq + kScanMatrixN - 1) / kScanMatrixN);
   s.on = true;
   s.block = WAVE;
+  s.float_rows = halves;
+  s.group_lanes = halves ? (uint32_t)kCfgs[g.cfg].G : 0u;
   s.tile = subtiles * kScanMatrixN;
   s.lds = s.tile * per_query;
   s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);

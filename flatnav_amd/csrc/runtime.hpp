@@ -272,6 +272,7 @@ struct fnv_index_s : PlanInputs {  // (options, table geometry, capacity, num_cu
   static constexpr uint32_t kDispenserStride = 32;  // (128 bytes: the two blocks never share a cache line)
   static constexpr uint32_t kBuilderWord = 64;      // the device builder's own dispenser word; [+1]: gather_ceiling's sink
   static constexpr uint32_t kDispenserWords = 80;
+  static constexpr uint32_t kScanCounterWord = 12;  // an exhaustive launch's block: [12..15] two uint64, {pairs scored, pairs rescored} (scan_matrix_f16.hpp)
   uint32_t* d_dispenser = nullptr;
   uint32_t* last_block = nullptr;  // the block of the most recent launch (record_launch); before any: d_dispenser
   int zeroed_block = -1;           // 0 / 1: the block the most recent launch's kernel zeroes on last_stream; -1: none

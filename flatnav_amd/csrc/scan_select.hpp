@@ -8,6 +8,7 @@
 // is a TOTAL order on distinct node ids, so a result depends neither on how rows were tiled into segments nor on which lane
 // saw a row first.  (The graph search orders equal distances as libstdc++'s heaps leave them; this order is not that one.)
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -100,6 +101,51 @@ struct ScanParams {
   uint32_t segments;           // row segments: block b scans segment b / tiles for query tile b % tiles
   uint32_t tile_queries;       // queries staged in LDS per block: that many share one load of a row
   uint32_t tiles;              // ceil(nq / tile_queries)
+};
+
+// ---- the float16 matrix engine's prefilter (scan_matrix_f16.hpp, option "scan_matrix_float") ---------------------------------
+// That engine forms an APPROXIMATE score of a (query, row) pair from a matrix-instruction dot product and two norms,
+//   L2: s~ = rn + qn - 2 dot~      IP: s~ = 1 - dot~,      rn ~ sum x_i^2,  qn ~ sum y_i^2  (each a float32 sum in some order),
+// and drops the pair when  s~ - scan_margin(P, rn, qn, ip) > the query's K-th exact distance so far.  For that to lose nothing,
+// scan_margin must bound |s~ - d| for every finite input, d being the float32 distance the vector scan reports for the pair
+// (distance.hpp, Dist<_Float16, METRIC>: per-element fma chains, lane sums, group_sum).  P = the elements the instruction sums,
+// zero padding included; u = 2^-24; D = the real-number distance; A = sum |x_i y_i| <= (RN + QN) / 2 with RN, QN the real norms;
+// sum (x_i - y_i)^2 <= 2 (RN + QN).
+// Assumptions, each named where it is used:
+//   (a) a product of two binary16 values is exact in float32 (22 significant bits, exponents within float32's normal range);
+//   (b) every accumulation step inside the matrix instruction is off by at most one unit in the last place of the running
+//       magnitude, 2 u |partial|, whatever the order of the steps and whether they round or truncate;
+//   (c) the norms are float32 sums of exact squares, each step rounded to nearest (the kernel's v_fma_mix_f32 chain, which
+//       keeps binary16 subnormals: profiles/distance_bits.md);
+//   (d) the matrix instruction MAY flush binary16 subnormal inputs to zero (not established for gfx950 either way).
+// L2.  The vector scan: every difference rounded once, P fused steps and log2(64) + 1 additions:  |d - D| <= (P + 8) 2u D
+//      <= (P + 8) 4u (RN + QN).  The score: |rn - RN| <= P 2u RN and the same for qn (c); |dot~ - dot| <= P 2u A (1 + P 2u)
+//      (a, b); the two additions of the combination round an amount of at most 2 (rn + qn) each.  Together
+//      |s~ - d| <= (4 P + 20) 2u (RN + QN) (1 + P 2u), and RN <= rn (1 + P 2u).
+// IP.  |s_v - dot| <= (P + 8) u A for the vector scan's sum, |dot~ - dot| as above, and each side rounds 1 - s once:
+//      |s~ - d| <= (1.5 P + 5) 2u (RN + QN) / 2 + 2u (1 + A).
+// (d)  A flushed element loses its products: less than 2^-14 |other side| each, at most
+//      2^-14 (sum |y_i| + sum |x_i|) <= 2^-14 (sqrt(P QN) + sqrt(P RN))  (Cauchy-Schwarz), twice that in L2's -2 dot~.
+// scan_margin is kappa (P + 4) 2u (rn + qn) with kappa = 16 -- four times what L2 needs, over twenty times what IP needs, which
+// also covers the float32 rounding of this function and P 2u <= 1 (rows below 4 M elements) -- plus 2^-11 sqrt(P n) per side
+// for (d), four times the bound, plus 2^-21 for the rounding of 1 - s.  A margin too wide costs rescored pairs; one too narrow
+// costs a wrong result, so none of these constants is tuned against a test.  NaN and infinite norms give a NaN or infinite
+// margin, which the kernel's compare lets pass (tests/test_scan_matrix_f16_plan.py holds the finite case on the CPU).
+constexpr float kScanMarginKappa = 16.0f;
+FNV_SCAN_HD inline float scan_margin_term(uint32_t P, float n) {  // one side's share: the kernel forms it once per row and per query
+  return kScanMarginKappa * (float)(P + 4u) * 0x1p-23f * n + 0x1p-11f * sqrtf((float)P * n);
+}
+FNV_SCAN_HD inline float scan_margin_of_terms(float row_term, float query_term, bool ip) {
+  return row_term + query_term + (ip ? 0x1p-21f : 0.0f);
+}
+FNV_SCAN_HD inline float scan_margin(uint32_t P, float rn, float qn, bool ip) {
+  return scan_margin_of_terms(scan_margin_term(P, rn), scan_margin_term(P, qn), ip);
+}
+// Its parameter block: the plain one, the lanes per vector (G) of the index's row configuration -- survivors are rescored in the
+// vector scan's own lane order -- and two counters of the launch, {pairs scored, pairs rescored}, zero at launch.
+struct ScanMatrixFloatParams : ScanParams {
+  uint32_t group_lanes;
+  unsigned long long* counters;
 };
 
 // ---- grouped filters (fnv_search_batch_*_grouped): one allowed set per query ---------------------------------------------

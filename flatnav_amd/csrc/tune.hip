@@ -360,6 +360,17 @@ int fnv_last_replayed_queries(fnv_index_t ix, uint64_t out[5]) {
   uint32_t w[5];
   HIP_TRY(hipMemcpy(w, ix->last_block + 3, sizeof(w), hipMemcpyDeviceToHost));  // (the most recent launch's block)
   for (int i = 0; i < 5; i++) out[i] = w[i];
+  bool matrix_float;
+  {
+    std::lock_guard<std::mutex> lock(ix->mu);
+    matrix_float = ix->geom[6] == 5;
+  }
+  if (matrix_float) {  // the float16 matrix engine's scan (scan_matrix_f16.hpp): {pairs scored, pairs rescored} behind the words above
+    uint64_t c[2];
+    HIP_TRY(hipMemcpy(c, ix->last_block + fnv_index_s::kScanCounterWord, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = c[1];
+    out[1] = c[0];
+  }
   return FNV_OK;
 }
 

@@ -91,7 +91,7 @@ class DeviceMirror {
   DirtyRows _dirty;       // link rows of synced nodes that changed since
   int64_t _filter_scan_max = 0;  // setFilterRouting: re-applied whenever the mirror is created anew
   bool _filter_scan_on_overflow = false;
-  bool _exhaustive_matrix = false;  // setExhaustiveMatrix: likewise
+  bool _exhaustive_matrix = false, _exhaustive_matrix_float = false;  // setExhaustiveMatrix: likewise
   // several GPUs: the mirror on _ordinal is the primary; replicas of it live on the other devices of _devices (filled by peer
   // copies, refreshed whenever the primary changes); batches are sharded over all of them
   int _ordinal = 0;
@@ -150,7 +150,7 @@ class DeviceMirror {
       throwOnDeviceError(fnv_index_set_live_nodes(_handle, s.cur_nodes));
     }
     if (_filter_scan_max != 0 || _filter_scan_on_overflow) applyFilterRouting();  // (a new handle starts with the library's defaults)
-    if (_exhaustive_matrix) throwOnDeviceError(fnv_set_option(_handle, "scan_matrix", 1));
+    if (_exhaustive_matrix) applyExhaustiveMatrix();
   }
 
   // The GPUs this index spreads its batches over: setDevices(), else the FLATNAV_DEVICES environment variable
@@ -289,10 +289,18 @@ class DeviceMirror {
     _filter_scan_on_overflow = scan_on_overflow;
     if (_handle) applyFilterRouting();
   }
-  // The exhaustive search's matrix engine (option "scan_matrix"): now if there is a mirror, and on every mirror made later.
-  void setExhaustiveMatrix(bool on) {
+  // The exhaustive search's matrix engines (options "scan_matrix" and, with `float_rows`, "scan_matrix_float"): now if there
+  // is a mirror, and on every mirror made later.
+  void setExhaustiveMatrix(bool on, bool float_rows = false) {
     _exhaustive_matrix = on;
-    if (_handle) throwOnDeviceError(fnv_set_option(_handle, "scan_matrix", on ? 1 : 0));
+    _exhaustive_matrix_float = on && float_rows;
+    if (_handle) applyExhaustiveMatrix();
+  }
+
+ private:
+  void applyExhaustiveMatrix() {
+    throwOnDeviceError(fnv_set_option(_handle, "scan_matrix", _exhaustive_matrix ? 1 : 0));
+    throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_float", _exhaustive_matrix_float ? 1 : 0));
   }
 };
 

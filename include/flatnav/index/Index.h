@@ -372,10 +372,12 @@ class Index {
   }
   // The matrix engine of searchBatchExhaustive (flatnav_hip.h, option "scan_matrix"): on uint8 and int8 indexes the unfiltered
   // and the single-filter exhaustive search score rows on the matrix cores -- the same bytes, sooner; every other call runs as
-  // before.  Applies to the device mirror now if there is one, and to every mirror made later.
-  void setExhaustiveMatrix(bool on) {
+  // before.  With `float_rows` (option "scan_matrix_float") float16 indexes take part too: the matrix cores discard the rows
+  // that provably cannot reach a query's K-th distance and the rest is scored as the vector scan scores it -- again the same
+  // bytes.  Applies to the device mirror now if there is one, and to every mirror made later.
+  void setExhaustiveMatrix(bool on, bool float_rows = false) {
     std::lock_guard<std::mutex> g(_mirror.mutex());
-    _mirror.setExhaustiveMatrix(on);
+    _mirror.setExhaustiveMatrix(on, float_rows);
   }
   // The C-ABI handle of the device mirror (valid until the next mutation); for callers that drive
   // fnv_search_batch_device on their own buffers / streams.

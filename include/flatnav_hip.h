@@ -254,6 +254,11 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *   "scan_matrix"     exhaustive search: 1 = the matrix engine (see fnv_search_batch_exhaustive, "Matrix engine"; default 0 = off):
  *                     on uint8 / int8 indexes the unfiltered and the single-filter call score rows with the int8 matrix
  *                     instructions; every other call runs the vector scan.  Same bytes.  Read per launch; keeps what fnv_tune measured.
+ *   "scan_matrix_float"  exhaustive search: 1 = the float16 matrix engine (see fnv_search_batch_exhaustive, "Float16 matrix engine";
+ *                     default 0 = off): on float16 indexes the unfiltered and the single-filter call discard rows by a matrix-instruction
+ *                     score with a proved error margin and score the survivors as the vector scan does; every other call
+ *                     (float32 and 1-byte indexes included, which "scan_matrix" alone governs) runs as before.  Same bytes.
+ *                     Read per launch; keeps what fnv_tune measured.
  *   "filter_scan_max"  filter routing (see "Filter routing" below; default 0 = off): in fnv_search_batch_filtered[_grouped][_device] a
  *                     query whose filter allows at most this many live nodes is answered by the exhaustive scan instead of
  *                     the graph search.  Keeps what fnv_tune / the adaptive choice measured, as the next one does.
@@ -376,6 +381,17 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     the scan stage of a routed filtered graph search, and shapes whose 32 queries with their K-entry lists exceed a block's
  *     LDS (K x row length too large).  fnv_last_launch_geometry then reports {grid_blocks, 64, lds_bytes, queries per tile, 0,
  *     row segments, kernel = 4, 0}.
+ *   Float16 matrix engine (option "scan_matrix_float" = 1): on a float16 index the scan of these two calls is a FILTER on the
+ *     matrix cores followed by the vector scan's own arithmetic.  v_mfma_f32_32x32x16_f16 gives an approximate score of 32 rows x
+ *     32 queries at a time; a pair is dropped when that score, less a margin that bounds its distance from the vector scan's
+ *     float32 value (scan_margin, csrc/scan_select.hpp, with its derivation and assumptions), is still above the query's K-th
+ *     exact distance so far.  Every pair that is not dropped -- a NaN or infinite score or margin never is -- is scored again with
+ *     the vector scan's operations in the vector scan's lane order, and only that distance is compared, inserted and reported.
+ *     So every reported distance has the vector scan's bits whatever the margin, and a sound margin makes the selection the
+ *     same as well: results, distance bits, padding, out_count and out_ndist (the candidate count) are those of the option off.
+ *     The option never makes a valid call invalid; float32 and 1-byte indexes, the _grouped calls, routed scans and shapes
+ *     beyond a block's LDS keep their engine.  fnv_last_launch_geometry reports kernel = 5 in kernel 4's layout;
+ *     fnv_last_replayed_queries how many pairs the filter let through.
  * fnv_search_batch_exhaustive: host buffers (allowed_bits included); thread safety and lanes as fnv_search_batch.
  * fnv_search_batch_exhaustive_device: every buffer, allowed_bits included, in the index's device memory, enqueued on `hip_stream`
  *   without synchronising; one launch in flight per handle, as fnv_search_batch_device.
@@ -502,12 +518,16 @@ int fnv_last_kernel_ms(fnv_index_t index, float* ms);
 
 /* The merged-beam kernel searches a query again with the exact (libstdc++-replay) two-heap code when equal
  * distances meet at a decision.  out[5] = queries of the most recent search that were: {total, eviction tie,
- * selection tie, result tie, NaN/inf}; synchronises with that launch.  Results do not depend on it. */
+ * selection tie, result tie, NaN/inf}; synchronises with that launch.  Results do not depend on it.
+ * The float16 matrix engine of the exhaustive search ("scan_matrix_float", kernel 5 of fnv_last_launch_geometry) hands PAIRS
+ * over to exact arithmetic in the same way, and after a launch it served the call counts them: out[0] = (query, row) pairs
+ * that passed the prefilter and were scored again exactly, out[1] = pairs scored on the matrix cores, out[2 .. 4] = 0.  After
+ * every other exhaustive launch all five are 0, as before. */
 int fnv_last_replayed_queries(fnv_index_t index, uint64_t out[5]);
 
 /* Launch geometry of the most recent search: geom[8] = {grid_blocks, block_threads, lds_bytes,
  * blocks_per_cu, visited_slots, cand_slots (LDS entries of the exact search's candidates heap), kernel: 0 = two-heap
- * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, tail_exact: the last that-many queries of the launch
+ * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, 5 = its float16 form, tail_exact: the last that-many queries of the launch
  * went straight to the exact search (merged-beam kernel, see the "sorted_tail_exact_pct" option)}.
  * blocks_per_cu = the query slots a CU keeps resident = the grid's share per CU (round 5; gfx950 hands LDS out in 1280-byte
  * granules, so this is min(what the HIP occupancy API counts, 163840 / (ceil(lds_bytes / 1280) * 1280)); rounds 1-4 launched the

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Developer tool: the exhaustive search's two engines -- the vector scan and the matrix engine ("scan_matrix" = 1,
-csrc/scan_matrix.hpp) -- on ONE c2-uint8-like index, same handle, same process, alternating.
+csrc/scan_matrix.hpp) -- on ONE c2-uint8-like index, same handle, same process, alternating.  With --dtype float16: the vector
+scan and the float16 matrix engine ("scan_matrix_float" = 1, csrc/scan_matrix_f16.hpp) on one float16 index of Gaussian rows of
+--dim elements; the line then also carries the share of the scored pairs that the prefilter let through to the exact rescoring
+(DeviceIndex.scan_rescored), and the peak is the 2517 TFLOP/s of the float16 matrix instructions.
 
-  python tools/dev/scan_matrix_ab.py [--n 1000000] [--nq 10000] [--fractions 1,0.1,0.01,0.001] [--rounds 3] [--steps 5] [--json out.json]
+  python tools/dev/scan_matrix_ab.py [--dtype uint8|float16] [--dim 128] [--n 1000000] [--nq 10000] [--fractions 1,0.1,0.01,0.001]
+                                     [--rounds 3] [--steps 5] [--json out.json]
 
 The SIFT-1M stand-in as uint8 (flatnav_amd.datasets.sift_like; rows stored without a graph: the scan does not read one),
 device-resident queries, K = 10.  For every fraction of allowed labels (1 = unfiltered; else a random set) it times, HIP
@@ -37,18 +41,25 @@ ap.add_argument("--fractions", default="1,0.1,0.01,0.001")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--json", default="")
+ap.add_argument("--dtype", default="uint8", choices=["uint8", "float16"])
+ap.add_argument("--dim", type=int, default=128)
 args = ap.parse_args()
 
-N, NQ, K, DIM, ROW_BYTES = args.n, args.nq, 10, 128, 128
-PEAK_TOPS = 5033.0
+HALVES = args.dtype == "float16"
+assert HALVES or args.dim == 128, "the uint8 index is the 128-d SIFT stand-in"
+N, NQ, K, DIM = args.n, args.nq, 10, args.dim
+ROW_BYTES = DIM * (2 if HALVES else 1)
+PEAK_TOPS = 2517.0 if HALVES else 5033.0
+OPTION, MODE = ("scan_matrix_float", 5) if HALVES else ("scan_matrix", 4)
+NP_T, DATA_T = (np.float16, flatnav.data_type.DataType.float16) if HALVES else (np.uint8, flatnav.data_type.DataType.uint8)
 dev_t = torch.device("cuda", 0)
 torch.cuda.set_device(0)
-X, Q = ds.sift_like(N, NQ)
-index = flatnav.index.create("l2", DIM, N, 32, flatnav.data_type.DataType.uint8)
+X, Q = ds.randn(N, NQ, DIM, seed=1) if HALVES else ds.sift_like(N, NQ)
+index = flatnav.index.create("l2", DIM, N, 32, DATA_T)
 index.set_device(0)
-index.allocate_nodes(X.astype(np.uint8))
+index.allocate_nodes(X.astype(NP_T))
 scan = hip.DeviceIndex(ctypes.c_void_p(index.device_handle()), owned=False)
-tq = torch.from_numpy(Q.astype(np.uint8)).to(dev_t)
+tq = torch.from_numpy(Q.astype(NP_T)).to(dev_t)
 out = {e: (torch.empty((NQ, K), dtype=torch.float32, device=dev_t), torch.empty((NQ, K), dtype=torch.int32, device=dev_t),
            torch.empty(NQ, dtype=torch.int32, device=dev_t), torch.empty(NQ, dtype=torch.int64, device=dev_t)) for e in (0, 1)}
 stream = torch.cuda.current_stream()
@@ -57,7 +68,7 @@ rng = np.random.default_rng(1)
 
 def launch(engine, bits, n_bits):
     d, l, c, nd = out[engine]
-    scan.set_option("scan_matrix", engine)
+    scan.set_option(OPTION, engine)
     scan.search_device_exhaustive(tq.data_ptr(), NQ, K, d.data_ptr(), l.data_ptr(), c.data_ptr(), nd.data_ptr(),
                                   bits_ptr=bits.data_ptr() if n_bits else 0, n_bits=n_bits, use_filter=n_bits > 0,
                                   stream=stream.cuda_stream)
@@ -83,7 +94,9 @@ for f in [float(x) for x in args.fractions.split(",")]:
         once(lambda: launch(e, bits, n_bits), 1)
         scan.status()
         geom[e] = scan.launch_geometry()
-    assert geom[0]["kernel_mode"] == 3 and geom[1]["kernel_mode"] == 4, geom
+    rescored = scan.scan_rescored() if HALVES else {"scored": 0, "rescored": 0}
+    assert geom[0]["kernel_mode"] == 3 and geom[1]["kernel_mode"] == MODE, geom
+    assert not HALVES or rescored["scored"] == NQ * len(rows), rescored
     for x, y in zip(out[0], out[1]):
         assert torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y), f
     assert int((out[1][3] != len(rows)).sum().item()) == 0
@@ -98,13 +111,14 @@ for f in [float(x) for x in args.fractions.split(",")]:
     line = dict(fraction=f, candidates=len(rows), vector_ms=ms[0], matrix_ms=ms[1], vector_median=med[0], matrix_median=med[1],
                 ratio=med[0] / med[1], vector_spread=spread, beats_by_more_than_spread=bool(med[0] - med[1] > spread),
                 vector_geometry=geom[0], matrix_geometry=geom[1], matrix_tops=ops / (med[1] * 1e-3) / 1e12,
-                matrix_of_peak=ops / (med[1] * 1e-3) / 1e12 / PEAK_TOPS, matrix_row_bytes=math.ceil(NQ / tile) * len(rows) * ROW_BYTES)
+                matrix_of_peak=ops / (med[1] * 1e-3) / 1e12 / PEAK_TOPS, matrix_row_bytes=math.ceil(NQ / tile) * len(rows) * ROW_BYTES,
+                rescored_share=rescored["rescored"] / max(1, rescored["scored"]), dtype=args.dtype, dim=DIM)
     lines.append(line)
     print("f=%-6g cand %8d | vector %9.3f ms [%9.3f .. %9.3f] | matrix %9.3f ms [%9.3f .. %9.3f] | %6.2fx  beats spread: %s | "
-          "matrix grid %d lds %d tile %d segments %d | %.1f TOP/s (%.4f of peak), row bytes %.3e"
+          "matrix grid %d lds %d tile %d segments %d | %.1f TOP/s (%.4f of peak), row bytes %.3e | rescored %.4f of the pairs"
           % (f, len(rows), med[0], min(ms[0]), max(ms[0]), med[1], min(ms[1]), max(ms[1]), line["ratio"], line["beats_by_more_than_spread"],
              geom[1]["grid_blocks"], geom[1]["lds_bytes"], tile, geom[1]["segments"], line["matrix_tops"], line["matrix_of_peak"],
-             line["matrix_row_bytes"]), flush=True)
-scan.set_option("scan_matrix", 0)
+             line["matrix_row_bytes"], line["rescored_share"]), flush=True)
+scan.set_option(OPTION, 0)
 if args.json:
     json.dump(lines, open(args.json, "w"), indent=1)
