@@ -4,8 +4,9 @@
 // flatnav_amd/build.py compiles the 104 combinations in parallel and links them with the host units -- and eighteen more for the
 // row format f32h (float32 queries on the half-width mirror, half_rows.hpp; -DFNV_INST_T=fnv_dev::f32h -DFNV_INST_HALF_ROWS):
 // the exact family (without the entry scan) and the merged-beam families with their DIRECT forms, for the row configurations
-// a mirror exists for -- four for family 15 (scan_m: the exhaustive search's matrix engine, uint8 / int8 x the metrics) and two
-// for family 16 (scan_mf: that engine's float16 form, scan_matrix_f16.hpp).
+// a mirror exists for -- four for family 15 (scan_m: the exhaustive search's matrix engine, uint8 / int8 x the metrics), two
+// for family 16 (scan_mf: that engine's float16 form, scan_matrix_f16.hpp) and two for family 17 (scan_mf32: its float32 form,
+// scan_matrix_f32.hpp).
 #include <hip/hip_runtime.h>
 
 #include "kernel_table.h"
@@ -16,6 +17,8 @@
 #include "scan_matrix.hpp"
 #elif FNV_INST_FAMILY == 16
 #include "scan_matrix_f16.hpp"
+#elif FNV_INST_FAMILY == 17
+#include "scan_matrix_f32.hpp"
 #endif
 #include "wire.hpp"
 
@@ -52,6 +55,8 @@ constexpr int METRIC = FNV_INST_METRIC;
 void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_m = exhaustive_scan_matrix_kernel<T, METRIC>; }
 #elif FNV_INST_FAMILY == 16  // ... and its float16 form
 void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_mf = exhaustive_scan_matrix_f16_kernel<METRIC>; }
+#elif FNV_INST_FAMILY == 17  // ... and its float32 form
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_mf32 = exhaustive_scan_matrix_f32_kernel<METRIC>; }
 #else
 template <bool FULL>
 static void fill_rows(KernelTable& t) {

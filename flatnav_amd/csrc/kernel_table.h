@@ -27,6 +27,7 @@ struct KernelTable {
   scan_grouped_fn flat_g[kNumCfgs][2]; // exhaustive_scan_grouped_kernel (... with one filter per query)
   scan_fn flat_m;                      // exhaustive_scan_matrix_kernel (scan_matrix.hpp; uint8 / int8 only, else null): row geometry is run-time
   scan_mf_fn flat_mf;                  // exhaustive_scan_matrix_f16_kernel (scan_matrix_f16.hpp; float16 only, else null): likewise
+  scan_mf_fn flat_mf32;                // exhaustive_scan_matrix_f32_kernel (scan_matrix_f32.hpp; float32 only, else null): likewise
 };
 
 // X(element type, type tag, metric ordinal, metric tag)
@@ -59,6 +60,9 @@ struct KernelTable {
 // Family 16, its float16 form (scan_matrix_f16.hpp: a matrix-instruction prefilter, survivors rescored in the vector scan's
 // arithmetic): one kernel per metric, for float16 indexes only.  X(metric ordinal, metric tag)
 #define FNV_FOR_EACH_MATRIX_FLOAT_METRIC(X) X(0, l2) X(1, ip)
+// Family 17, its float32 form (scan_matrix_f32.hpp: the same prefilter on operands narrowed to bfloat16 in registers): one kernel
+// per metric, for float32 indexes only.  X(metric ordinal, metric tag)
+#define FNV_FOR_EACH_MATRIX_FLOAT32_METRIC(X) X(0, l2) X(1, ip)
 
 #define FNV_DECLARE_FILLER(ordinal, family, tag, mtag) void fill_##family##_##tag##_##mtag(KernelTable& t);
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_FOR_EACH_FAMILY(FNV_DECLARE_FILLER, tag, mtag)
@@ -72,6 +76,9 @@ FNV_FOR_EACH_MATRIX_TYPE_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #define FNV_DECLARE_FILLERS(M, mtag) FNV_DECLARE_FILLER(16, scan_mf, f16, mtag)
 FNV_FOR_EACH_MATRIX_FLOAT_METRIC(FNV_DECLARE_FILLERS)
+#undef FNV_DECLARE_FILLERS
+#define FNV_DECLARE_FILLERS(M, mtag) FNV_DECLARE_FILLER(17, scan_mf32, f32, mtag)
+FNV_FOR_EACH_MATRIX_FLOAT32_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #undef FNV_DECLARE_FILLER
 

@@ -12,6 +12,7 @@
 #ifdef FNV_DEV_FAST_BUILD
 #include "scan_matrix.hpp"
 #include "scan_matrix_f16.hpp"
+#include "scan_matrix_f32.hpp"
 #endif
 
 namespace fnv_dev {
@@ -127,6 +128,8 @@ const KernelTable& kernel_table(int, int, bool = false) {
     if constexpr (sizeof(FNV_DEV_T) == 1) k.flat_m = exhaustive_scan_matrix_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
     k.flat_mf = nullptr;
     if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) k.flat_mf = exhaustive_scan_matrix_f16_kernel<FNV_DEV_METRIC>;
+    k.flat_mf32 = nullptr;
+    if constexpr (std::is_same<FNV_DEV_T, float>::value) k.flat_mf32 = exhaustive_scan_matrix_f32_kernel<FNV_DEV_METRIC>;
     return k;
   }();
   return t;
@@ -163,6 +166,11 @@ const KernelTable& kernel_table(int dtype, int metric, bool half_rows = false) {
     i = 6;
 #define FNV_FILL(M, mtag) fill_scan_mf_f16_##mtag(tables[i++]);
     FNV_FOR_EACH_MATRIX_FLOAT_METRIC(FNV_FILL)
+#undef FNV_FILL
+    // ... and its float32 form: the float32 tables (tables[0], tables[1])
+    i = 0;
+#define FNV_FILL(M, mtag) fill_scan_mf32_f32_##mtag(tables[i++]);
+    FNV_FOR_EACH_MATRIX_FLOAT32_METRIC(FNV_FILL)
 #undef FNV_FILL
   });
   if (half_rows) return tables[8 + (metric == FNV_METRIC_IP ? 1 : 0)];
@@ -527,7 +535,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const RowGeometry g = row_geometry(ix);
   const bool grouped = filter && filter->grouped, listed = filter && !grouped;
 
-  // -- shape: the vector scan's, or -- an ungrouped call a matrix engine takes ("scan_matrix", "scan_matrix_float") -- that engine's
+  // -- shape: the vector scan's, or -- an ungrouped call a matrix engine takes ("scan_matrix", "scan_matrix_float", "scan_matrix_float32") -- that engine's
   const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
   if (vector_shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
   const ScanMatrixShape matrix = grouped ? ScanMatrixShape() : scan_matrix_shape(ix, g, nq, K, live);
@@ -563,9 +571,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
     if (rc) return rc;
   } else {
     const KernelTable& table = kernel_table(ix->dtype, ix->metric);
-    if (matrix.float_rows) {  // the float16 form: the plain block, the rescoring groups, the two counters the memset above cleared
-      const scan_mf_fn kern = table.flat_mf;
-      if (!kern) return fail(FNV_ERR_RUNTIME, "the float16 matrix scan kernel is missing from the build");
+    if (matrix.float_rows || matrix.float32_rows) {  // the float forms: the plain block, the rescoring groups, the two counters the memset above cleared
+      const scan_mf_fn kern = matrix.float32_rows ? table.flat_mf32 : table.flat_mf;
+      if (!kern) return fail(FNV_ERR_RUNTIME, "the float matrix scan kernel of this element type is missing from the build");
       ScanMatrixFloatParams fp;
       static_cast<ScanParams&>(fp) = gp.s;
       fp.group_lanes = matrix.group_lanes;
@@ -585,9 +593,10 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   HIP_TRY(hipEventRecord(ix->ev1, stream));
 
   // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
-  // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments.  Mode 5: its float16 form, likewise)
+  // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments.  Modes 5 and 6: its float16 and
+  // float32 forms, likewise)
   record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
-                grouped ? SCAN_QUEUE_IDS : 0, grouped || matrix.on ? shape.segments : 0, matrix.float_rows ? 5 : matrix.on ? 4 : 3, 0);
+                grouped ? SCAN_QUEUE_IDS : 0, grouped || matrix.on ? shape.segments : 0, matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, 0);
   return FNV_OK;
 }
 

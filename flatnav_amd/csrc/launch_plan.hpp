@@ -50,6 +50,7 @@ struct IndexOptions {
   int64_t scan_segment_rows = 0;  // exhaustive search: candidate rows per block's segment (0: automatic)
   int64_t scan_matrix = 0;  // exhaustive search on uint8 / int8 indexes: the matrix engine where it applies (scan_matrix_shape)
   int64_t scan_matrix_float = 0;  // ... on float16 indexes: the matrix prefilter with exact rescoring (scan_matrix_f16.hpp)
+  int64_t scan_matrix_float32 = 0;  // ... on float32 indexes: the same on operands narrowed to bfloat16 (scan_matrix_f32.hpp)
   // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
   // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
   int64_t filter_scan_max = 0, filter_scan_on_overflow = 0;
@@ -654,31 +655,40 @@ inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t
 // by the same rules: a step is two chunks -- sixteen elements -- there as well, the kernel keeps kScanMatrixFloatSpanSteps of
 // them in registers (rows of 256 bytes: 128-d), and a query's terms are two floats, its norm and its share of the margin.
 // It is also told the lanes per vector of the row configuration (`group_lanes`): survivors are rescored in that lane order.
-constexpr uint32_t kScanMatrixN = 32, kScanMatrixMaxTile = 128, kScanMatrixSpanSteps = 4, kScanMatrixFloatSpanSteps = 8;
+// The float32 form (scan_matrix_f32.hpp, exhaustive_scan_matrix_f32_kernel; option "scan_matrix_float32") takes float32 indexes:
+// a step is still sixteen elements, now FOUR chunks; the staged query is narrowed to bfloat16, so its LDS is float16's (the
+// float32 query that rescoring needs is read from global memory); the kernel keeps kScanMatrixFloat32SpanSteps steps in
+// registers (rows of 512 bytes: 128-d).  Budget and widest tile are the other engines'.
+constexpr uint32_t kScanMatrixN = 32, kScanMatrixMaxTile = 128, kScanMatrixSpanSteps = 4, kScanMatrixFloatSpanSteps = 8,
+                   kScanMatrixFloat32SpanSteps = 8;
 constexpr uint32_t kScanMatrixLdsBudget = 32u << 10;  // five blocks per CU
 constexpr uint32_t kScanMatrixWavesPerCu = 8;         // two wavefronts per SIMD, the vector scan's figure (registers allow three)
 struct ScanMatrixShape : ScanShape {
   bool on = false;
   uint32_t block = 0;  // threads per block
-  bool float_rows = false;   // the float16 form
-  uint32_t group_lanes = 0;  // ... and its rescoring groups: kCfgs[cfg].G
+  bool float_rows = false;    // the float16 form
+  bool float32_rows = false;  // the float32 form
+  uint32_t group_lanes = 0;   // the float forms' rescoring groups: kCfgs[cfg].G
 };
 inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
   ScanMatrixShape s;
   s.tile = s.tiles = s.segments = s.lds = 0;
   const bool bytes = ix->scan_matrix != 0 && (ix->dtype == FNV_DTYPE_UINT8 || ix->dtype == FNV_DTYPE_INT8);
   const bool halves = ix->scan_matrix_float != 0 && ix->dtype == FNV_DTYPE_FLOAT16;
-  if ((!bytes && !halves) || nq == 0) return s;
-  const uint32_t steps = (g.nchunks + g.tail_chunks + 1u) / 2u;
-  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + (halves ? 8u : 4u);
+  const bool floats = ix->scan_matrix_float32 != 0 && ix->dtype == FNV_DTYPE_FLOAT32;
+  if ((!bytes && !halves && !floats) || nq == 0) return s;
+  const uint32_t chunks_per_step = floats ? 4u : 2u;
+  const uint32_t steps = (g.nchunks + g.tail_chunks + chunks_per_step - 1u) / chunks_per_step;
+  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + (bytes ? 4u : 8u);
   if (kScanMatrixN * per_query > kScanMaxLds) return s;
   uint32_t subtiles = std::max(1u, std::min(kScanMatrixMaxTile, kScanMatrixLdsBudget / per_query) / kScanMatrixN);
-  if (steps > (halves ? kScanMatrixFloatSpanSteps : kScanMatrixSpanSteps)) subtiles = 1;
+  if (steps > (floats ? kScanMatrixFloat32SpanSteps : halves ? kScanMatrixFloatSpanSteps : kScanMatrixSpanSteps)) subtiles = 1;
   subtiles = (uint32_t)std::min<uint64_t>(subtiles, (nq + kScanMatrixN - 1) / kScanMatrixN);
   s.on = true;
   s.block = WAVE;
   s.float_rows = halves;
-  s.group_lanes = halves ? (uint32_t)kCfgs[g.cfg].G : 0u;
+  s.float32_rows = floats;
+  s.group_lanes = halves || floats ? (uint32_t)kCfgs[g.cfg].G : 0u;
   s.tile = subtiles * kScanMatrixN;
   s.lds = s.tile * per_query;
   s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);

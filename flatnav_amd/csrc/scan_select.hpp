@@ -141,7 +141,48 @@ FNV_SCAN_HD inline float scan_margin_of_terms(float row_term, float query_term, 
 FNV_SCAN_HD inline float scan_margin(uint32_t P, float rn, float qn, bool ip) {
   return scan_margin_of_terms(scan_margin_term(P, rn), scan_margin_term(P, qn), ip);
 }
-// Its parameter block: the plain one, the lanes per vector (G) of the index's row configuration -- survivors are rescored in the
+// ---- the float32 matrix engine's prefilter (scan_matrix_f32.hpp, option "scan_matrix_float32") -------------------------------
+// The same score from float32 rows and queries whose elements were NARROWED to bfloat16 for the matrix instruction (round to
+// nearest even, 8 significant bits), with rn and qn float32 fma chains over the ORIGINAL float32 values.  scan_margin_f32 must
+// bound |s~ - d|, d now Dist<float, METRIC>'s float32 distance.  Notation as above; x^ = the narrowed x.
+// Assumptions:
+//   (a') a product of two bfloat16 values is exact in float32 (16 significant bits; an exponent outside float32's range: (f), (g));
+//   (b)  as above, for the accumulation inside the matrix instruction, on the magnitudes A^ = sum |x^_i y^_i| <= (1 + 2^-9)^2 A;
+//   (c') the norms are float32 fma chains, one rounding to nearest per element: |rn - RN| <= P 2u RN as before;
+//   (d') the matrix instruction MAY flush bfloat16 subnormal inputs, and the conversion float32 subnormals, to zero (neither is
+//        established for gfx950); bfloat16's subnormal threshold is float32's, 2^-126;
+//   (e)  every float32 step, of the vector scan and of the score alike, MAY flush a subnormal result (at most 2^-126 absolute).
+// Accumulation and combination.  The derivation above carries over with this P, with A^ for A in the dot product's term and
+//      one more rounding per product in the vector scan's L2 (x_i - y_i of two float32 values rounds; of two binary16 values it
+//      did not): within the factor four that kappa = 16 leaves.
+// Operand rounding.  x^ = x (1 + e), |e| <= 2^-9 for every x^ that is a normal number, so
+//      |sum x^_i y^_i - sum x_i y_i| <= (2^-8 + 2^-18) A <= (2^-8 + 2^-18) (RN + QN) / 2;  L2's -2 dot~ takes twice that:
+//      (2^-8 + 2^-18) (RN + QN).  The margin takes 2^-7 (rn + qn) for L2 and 2^-8 (rn + qn) for IP -- TWICE the bound of
+//      either (both are attained, up to 2^-18, by a row equal to its query whose every element lies halfway between two
+//      bfloat16 values), which also covers RN <= rn (1 + P 2u) and the float32 rounding of this function.  This term is the
+//      margin for real data: 2^-7 of the norms against the 2^-18 or so of everything else.
+// (d') An element that is flushed, or is a subnormal rounded absolutely rather than relatively, moves by less than 2^-126 and
+//      its products by less than 2^-126 |other side| each: at most 2^-126 (sqrt(P QN) + sqrt(P RN)), twice that in L2.
+//      2^-123 sqrt(P n) per side is four times the L2 bound.
+// (e)  At most 4 P + 20 float32 steps lie between the inputs and |s~ - d| (P + 8 in the vector scan, P in each norm, P in the
+//      dot product, the combination), the dot product's counted twice in L2: less than (6 P + 20) 2^-126.  (P + 4) 2^-122 per
+//      side is more than four times that.  Both (d') and (e) vanish beside the other terms unless the norms are below 2^-100.
+// (f)  An element of magnitude above 2^127 (2 - 2^-8) narrows to bfloat16 infinity.  Its float32 square overflows, so rn or qn
+//      is +inf, the margin is +inf or NaN, and score - margin is -inf or NaN: the pair survives, whatever the instruction made
+//      of the infinite operand.  The same holds when a norm overflows without any element doing so.
+// (g)  With finite rn + qn no partial sum of the dot product exceeds A^ <= (1 + 2^-8) (rn + qn) / 2, so the dot product can
+//      overflow only with norms at the very top of the range, where the vector scan's distance may still be finite.  The kernel
+//      therefore lets a pair through whenever score - margin is not a FINITE number above the K-th distance.
+// As above, none of these constants is tuned against a test (tests/test_scan_matrix_f32_plan.py holds the finite case on the
+// CPU, with bfloat16 narrowing done by bit arithmetic, with and without the flushes).
+FNV_SCAN_HD inline float scan_margin_f32_term(uint32_t P, float n, bool ip) {  // one side's share, formed once per row and per query
+  return (kScanMarginKappa * (float)(P + 4u) * 0x1p-23f + (ip ? 0x1p-8f : 0x1p-7f)) * n + 0x1p-123f * (sqrtf((float)P) * sqrtf(n)) +
+         (float)(P + 4u) * 0x1p-122f;  // (two roots: P n may overflow where n does not)
+}
+FNV_SCAN_HD inline float scan_margin_f32(uint32_t P, float rn, float qn, bool ip) {
+  return scan_margin_of_terms(scan_margin_f32_term(P, rn, ip), scan_margin_f32_term(P, qn, ip), ip);
+}
+// The float engines' parameter block: the plain one, the lanes per vector (G) of the index's row configuration -- survivors are rescored in the
 // vector scan's own lane order -- and two counters of the launch, {pairs scored, pairs rescored}, zero at launch.
 struct ScanMatrixFloatParams : ScanParams {
   uint32_t group_lanes;

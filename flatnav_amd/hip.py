@@ -554,12 +554,12 @@ class DeviceIndex:
         return dict(zip(["total", "eviction_tie", "selection_tie", "result_tie", "nan_inf"], [int(x) for x in r]))
 
     def scan_rescored(self) -> dict:
-        """The float16 matrix engine of the last exhaustive search (what fnv_last_replayed_queries reports after a launch it
+        """The float16 or float32 matrix engine of the last exhaustive search (what fnv_last_replayed_queries reports after a launch it
         served): (query, row) pairs scored on the matrix cores, and pairs that passed the prefilter and were scored again
         exactly; zeros when another engine ran."""
         r = (C.c_uint64 * 5)()
         check(lib().fnv_last_replayed_queries(self._h, r))
-        on = self.launch_geometry()["kernel_mode"] == 5
+        on = self.launch_geometry()["kernel_mode"] in (5, 6)
         return {"scored": int(r[1]) if on else 0, "rescored": int(r[0]) if on else 0}
 
     def handover_stats(self) -> dict:
@@ -577,10 +577,10 @@ class DeviceIndex:
         keys = ["grid_blocks", "block_threads", "lds_bytes", "blocks_per_cu", "visited_slots", "cand_slots"]
         out = {k: int(g[i]) for i, k in enumerate(keys)}
         out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds", "exhaustive_scan", "exhaustive_scan_matrix",
-                         "exhaustive_scan_matrix_float"][int(g[6])]
-        out["kernel_mode"] = int(g[6])  # fnv_last_launch_geometry's own ordinal (4: the exhaustive search's matrix engine, 5: its float16 form)
+                         "exhaustive_scan_matrix_float", "exhaustive_scan_matrix_float32"][int(g[6])]
+        out["kernel_mode"] = int(g[6])  # fnv_last_launch_geometry's own ordinal (4: the exhaustive search's matrix engine, 5: its float16 form, 6: its float32 form)
         out["tail_exact"] = int(g[7])
-        if int(g[6]) in (4, 5):
+        if int(g[6]) in (4, 5, 6):
             out["tile_queries"], out["segments"] = int(g[3]), int(g[5])
         if int(g[6]) == 3 and int(g[4]):  # the grouped scan reports its tiling in the slots the graph search's layout uses
             out["tile_queries"], out["queue_ids"], out["segments"] = int(g[3]), int(g[4]), int(g[5])

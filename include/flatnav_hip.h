@@ -259,6 +259,11 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *                     score with a proved error margin and score the survivors as the vector scan does; every other call
  *                     (float32 and 1-byte indexes included, which "scan_matrix" alone governs) runs as before.  Same bytes.
  *                     Read per launch; keeps what fnv_tune measured.
+ *   "scan_matrix_float32"  exhaustive search: 1 = the float32 matrix engine (see fnv_search_batch_exhaustive, "Float32 matrix
+ *                     engine"; default 0 = off): on float32 indexes the unfiltered and the single-filter call do what
+ *                     "scan_matrix_float" does on float16 ones, on operands narrowed to bfloat16 in registers; every other
+ *                     call (float16 and 1-byte indexes included, which the two other options govern) runs as before.
+ *                     Same bytes.  Read per launch; keeps what fnv_tune measured.
  *   "filter_scan_max"  filter routing (see "Filter routing" below; default 0 = off): in fnv_search_batch_filtered[_grouped][_device] a
  *                     query whose filter allows at most this many live nodes is answered by the exhaustive scan instead of
  *                     the graph search.  Keeps what fnv_tune / the adaptive choice measured, as the next one does.
@@ -392,6 +397,14 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     The option never makes a valid call invalid; float32 and 1-byte indexes, the _grouped calls, routed scans and shapes
  *     beyond a block's LDS keep their engine.  fnv_last_launch_geometry reports kernel = 5 in kernel 4's layout;
  *     fnv_last_replayed_queries how many pairs the filter let through.
+ *   Float32 matrix engine (option "scan_matrix_float32" = 1): the same on a float32 index.  Rows and queries are narrowed to
+ *     bfloat16 in registers (v_cvt_pk_bf16_f32, round to nearest even) for v_mfma_f32_32x32x16_bf16 ONLY; the norms of the
+ *     score, and every distance that is compared, inserted or reported, are computed from the float32 values.  The margin
+ *     (scan_margin_f32, csrc/scan_select.hpp) adds the narrowing's error, 2^-7 of the two norms for L2 and 2^-8 for IP; a value
+ *     that narrows to bfloat16 infinity has an infinite norm and always passes.  A float32 index with a live half-width mirror
+ *     is scanned from its float32 table.  Same bytes as with the option off; not taken for the same calls as the float16
+ *     engine, and for every other element type.  fnv_last_launch_geometry reports kernel = 6 in kernel 4's layout;
+ *     fnv_last_replayed_queries the pairs as for kernel 5.
  * fnv_search_batch_exhaustive: host buffers (allowed_bits included); thread safety and lanes as fnv_search_batch.
  * fnv_search_batch_exhaustive_device: every buffer, allowed_bits included, in the index's device memory, enqueued on `hip_stream`
  *   without synchronising; one launch in flight per handle, as fnv_search_batch_device.
@@ -519,7 +532,7 @@ int fnv_last_kernel_ms(fnv_index_t index, float* ms);
 /* The merged-beam kernel searches a query again with the exact (libstdc++-replay) two-heap code when equal
  * distances meet at a decision.  out[5] = queries of the most recent search that were: {total, eviction tie,
  * selection tie, result tie, NaN/inf}; synchronises with that launch.  Results do not depend on it.
- * The float16 matrix engine of the exhaustive search ("scan_matrix_float", kernel 5 of fnv_last_launch_geometry) hands PAIRS
+ * The float16 and float32 matrix engines of the exhaustive search ("scan_matrix_float", "scan_matrix_float32"; kernels 5 and 6 of fnv_last_launch_geometry) hand PAIRS
  * over to exact arithmetic in the same way, and after a launch it served the call counts them: out[0] = (query, row) pairs
  * that passed the prefilter and were scored again exactly, out[1] = pairs scored on the matrix cores, out[2 .. 4] = 0.  After
  * every other exhaustive launch all five are 0, as before. */
@@ -527,7 +540,7 @@ int fnv_last_replayed_queries(fnv_index_t index, uint64_t out[5]);
 
 /* Launch geometry of the most recent search: geom[8] = {grid_blocks, block_threads, lds_bytes,
  * blocks_per_cu, visited_slots, cand_slots (LDS entries of the exact search's candidates heap), kernel: 0 = two-heap
- * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, 5 = its float16 form, tail_exact: the last that-many queries of the launch
+ * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, 5 = its float16 form, 6 = its float32 form, tail_exact: the last that-many queries of the launch
  * went straight to the exact search (merged-beam kernel, see the "sorted_tail_exact_pct" option)}.
  * blocks_per_cu = the query slots a CU keeps resident = the grid's share per CU (round 5; gfx950 hands LDS out in 1280-byte
  * granules, so this is min(what the HIP occupancy API counts, 163840 / (ceil(lds_bytes / 1280) * 1280)); rounds 1-4 launched the

@@ -3,9 +3,11 @@
 csrc/scan_matrix.hpp) -- on ONE c2-uint8-like index, same handle, same process, alternating.  With --dtype float16: the vector
 scan and the float16 matrix engine ("scan_matrix_float" = 1, csrc/scan_matrix_f16.hpp) on one float16 index of Gaussian rows of
 --dim elements; the line then also carries the share of the scored pairs that the prefilter let through to the exact rescoring
-(DeviceIndex.scan_rescored), and the peak is the 2517 TFLOP/s of the float16 matrix instructions.
+(DeviceIndex.scan_rescored), and the peak is the 2517 TFLOP/s of the float16 matrix instructions.  With --dtype float32: the same
+for the float32 matrix engine ("scan_matrix_float32" = 1, csrc/scan_matrix_f32.hpp) on one float32 index; the peak is that of the
+bfloat16 matrix instructions, the same figure.
 
-  python tools/dev/scan_matrix_ab.py [--dtype uint8|float16] [--dim 128] [--n 1000000] [--nq 10000] [--fractions 1,0.1,0.01,0.001]
+  python tools/dev/scan_matrix_ab.py [--dtype uint8|float16|float32] [--dim 128] [--n 1000000] [--nq 10000] [--fractions 1,0.1,0.01,0.001]
                                      [--rounds 3] [--steps 5] [--json out.json]
 
 The SIFT-1M stand-in as uint8 (flatnav_amd.datasets.sift_like; rows stored without a graph: the scan does not read one),
@@ -41,17 +43,18 @@ ap.add_argument("--fractions", default="1,0.1,0.01,0.001")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--json", default="")
-ap.add_argument("--dtype", default="uint8", choices=["uint8", "float16"])
+ap.add_argument("--dtype", default="uint8", choices=["uint8", "float16", "float32"])
 ap.add_argument("--dim", type=int, default=128)
 args = ap.parse_args()
 
-HALVES = args.dtype == "float16"
+HALVES = args.dtype != "uint8"  # a float engine: Gaussian rows, a prefilter with rescoring
 assert HALVES or args.dim == 128, "the uint8 index is the 128-d SIFT stand-in"
 N, NQ, K, DIM = args.n, args.nq, 10, args.dim
-ROW_BYTES = DIM * (2 if HALVES else 1)
+ROW_BYTES = DIM * {"uint8": 1, "float16": 2, "float32": 4}[args.dtype]
 PEAK_TOPS = 2517.0 if HALVES else 5033.0
-OPTION, MODE = ("scan_matrix_float", 5) if HALVES else ("scan_matrix", 4)
-NP_T, DATA_T = (np.float16, flatnav.data_type.DataType.float16) if HALVES else (np.uint8, flatnav.data_type.DataType.uint8)
+OPTION, MODE = {"uint8": ("scan_matrix", 4), "float16": ("scan_matrix_float", 5), "float32": ("scan_matrix_float32", 6)}[args.dtype]
+NP_T, DATA_T = {"uint8": (np.uint8, flatnav.data_type.DataType.uint8), "float16": (np.float16, flatnav.data_type.DataType.float16),
+                "float32": (np.float32, flatnav.data_type.DataType.float32)}[args.dtype]
 dev_t = torch.device("cuda", 0)
 torch.cuda.set_device(0)
 X, Q = ds.randn(N, NQ, DIM, seed=1) if HALVES else ds.sift_like(N, NQ)
