@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
                                            "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "runtime.hpp",
                                            "launch_plan.hpp", "measurements.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp",
-                                           "scan_matrix.hpp", "scan_matrix_f16.hpp", "scan_matrix_f32.hpp")] + [
+                                           "scan_matrix.hpp", "scan_matrix_f16.hpp", "scan_matrix_f32.hpp", "scan_matrix_feed.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
 # The host units behind runtime.hpp, which brings launch_plan.hpp with measurements.hpp (kernel units include none) and, through kernel_table.h,
 # the device headers that say what a launch passes.  Each unit with the kernel headers it includes on top of those (launch.hip:
@@ -53,8 +53,11 @@ MATRIX_FLOAT_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops
 # ... and its float32 form (csrc/scan_matrix_f32.hpp; FNV_FOR_EACH_MATRIX_FLOAT32_METRIC): new code as well, same flags -- the norms
 # and the rescoring are per-element fma chains there too.
 MATRIX_FLOAT32_FAMILY = (17, "scan_mf32")
-# headers that one family's units alone include (a change to them leaves every other object current)
-FAMILY_HEADERS = {"scan_matrix.hpp": "scan_m", "scan_matrix_f16.hpp": "scan_mf", "scan_matrix_f32.hpp": "scan_mf32"}
+# The units of these three families also hold their engine's grouped kernel (option "scan_matrix_grouped"): the same body fed from a
+# filter row's bitmap by csrc/scan_matrix_feed.hpp, which all three include.
+# headers that only some families' units include (a change to them leaves every other object current)
+FAMILY_HEADERS = {"scan_matrix.hpp": ("scan_m",), "scan_matrix_f16.hpp": ("scan_mf",), "scan_matrix_f32.hpp": ("scan_mf32",),
+                  "scan_matrix_feed.hpp": ("scan_m", "scan_mf", "scan_mf32")}
 
 
 def hipcc() -> str:
@@ -92,7 +95,7 @@ def _stale(obj, src):
     else:  # runtime.hpp, launch_plan.hpp and measurements.hpp (the launch planner) are included by the host units only
         family = os.path.basename(obj)[len("inst_"):].rsplit("_", 2)[0]  # inst_<family>_<type>_<metric>.o
         deps = [h for h in HEADERS if os.path.basename(h) not in HOST_HEADERS and
-                FAMILY_HEADERS.get(os.path.basename(h), family) == family]
+                family in FAMILY_HEADERS.get(os.path.basename(h), (family,))]
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 
 

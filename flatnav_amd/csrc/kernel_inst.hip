@@ -6,7 +6,7 @@
 // the exact family (without the entry scan) and the merged-beam families with their DIRECT forms, for the row configurations
 // a mirror exists for -- four for family 15 (scan_m: the exhaustive search's matrix engine, uint8 / int8 x the metrics), two
 // for family 16 (scan_mf: that engine's float16 form, scan_matrix_f16.hpp) and two for family 17 (scan_mf32: its float32 form,
-// scan_matrix_f32.hpp).
+// scan_matrix_f32.hpp); each of those eight holds the engine's ungrouped and its grouped kernel.
 #include <hip/hip_runtime.h>
 
 #include "kernel_table.h"
@@ -52,11 +52,20 @@ constexpr int METRIC = FNV_INST_METRIC;
 #endif
 
 #if FNV_INST_FAMILY == 15  // the matrix engine of the exhaustive search (1-byte element types): one kernel, run-time row geometry
-void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_m = exhaustive_scan_matrix_kernel<T, METRIC>; }
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
+  t.flat_m = exhaustive_scan_matrix_kernel<T, METRIC>;
+  t.flat_mg = exhaustive_scan_matrix_grouped_kernel<T, METRIC>;
+}
 #elif FNV_INST_FAMILY == 16  // ... and its float16 form
-void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_mf = exhaustive_scan_matrix_f16_kernel<METRIC>; }
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
+  t.flat_mf = exhaustive_scan_matrix_f16_kernel<METRIC>;
+  t.flat_mg = exhaustive_scan_matrix_f16_grouped_kernel<METRIC>;
+}
 #elif FNV_INST_FAMILY == 17  // ... and its float32 form
-void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) { t.flat_mf32 = exhaustive_scan_matrix_f32_kernel<METRIC>; }
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
+  t.flat_mf32 = exhaustive_scan_matrix_f32_kernel<METRIC>;
+  t.flat_mg = exhaustive_scan_matrix_f32_grouped_kernel<METRIC>;
+}
 #else
 template <bool FULL>
 static void fill_rows(KernelTable& t) {

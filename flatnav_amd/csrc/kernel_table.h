@@ -28,6 +28,7 @@ struct KernelTable {
   scan_fn flat_m;                      // exhaustive_scan_matrix_kernel (scan_matrix.hpp; uint8 / int8 only, else null): row geometry is run-time
   scan_mf_fn flat_mf;                  // exhaustive_scan_matrix_f16_kernel (scan_matrix_f16.hpp; float16 only, else null): likewise
   scan_mf_fn flat_mf32;                // exhaustive_scan_matrix_f32_kernel (scan_matrix_f32.hpp; float32 only, else null): likewise
+  scan_grouped_fn flat_mg;             // the grouped form of whichever of the three the element type has (families 15-17 fill it with their own)
 };
 
 // X(element type, type tag, metric ordinal, metric tag)
@@ -55,7 +56,8 @@ struct KernelTable {
   X(11, merged2_d, __VA_ARGS__)
 
 // Family 15, the exhaustive search's matrix engine (scan_matrix.hpp): one kernel per (1-byte element type, metric), no row
-// configurations; the float types' tables keep a null slot.  X(element type, type tag, metric ordinal, metric tag)
+// configurations; the float types' tables keep a null slot.  Its units, and those of families 16 and 17, also hold the engine's
+// grouped form (the same body over another row source, scan_matrix_feed.hpp): flat_mg.  X(element type, type tag, metric ordinal, metric tag)
 #define FNV_FOR_EACH_MATRIX_TYPE_METRIC(X) X(uint8_t, u8, 0, l2) X(uint8_t, u8, 1, ip) X(int8_t, i8, 0, l2) X(int8_t, i8, 1, ip)
 // Family 16, its float16 form (scan_matrix_f16.hpp: a matrix-instruction prefilter, survivors rescored in the vector scan's
 // arithmetic): one kernel per metric, for float16 indexes only.  X(metric ordinal, metric tag)

@@ -130,6 +130,10 @@ const KernelTable& kernel_table(int, int, bool = false) {
     if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) k.flat_mf = exhaustive_scan_matrix_f16_kernel<FNV_DEV_METRIC>;
     k.flat_mf32 = nullptr;
     if constexpr (std::is_same<FNV_DEV_T, float>::value) k.flat_mf32 = exhaustive_scan_matrix_f32_kernel<FNV_DEV_METRIC>;
+    k.flat_mg = nullptr;  // ... and the grouped form of whichever the element type has
+    if constexpr (sizeof(FNV_DEV_T) == 1) k.flat_mg = exhaustive_scan_matrix_grouped_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
+    if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) k.flat_mg = exhaustive_scan_matrix_f16_grouped_kernel<FNV_DEV_METRIC>;
+    if constexpr (std::is_same<FNV_DEV_T, float>::value) k.flat_mg = exhaustive_scan_matrix_f32_grouped_kernel<FNV_DEV_METRIC>;
     return k;
   }();
   return t;
@@ -535,10 +539,11 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const RowGeometry g = row_geometry(ix);
   const bool grouped = filter && filter->grouped, listed = filter && !grouped;
 
-  // -- shape: the vector scan's, or -- an ungrouped call a matrix engine takes ("scan_matrix", "scan_matrix_float", "scan_matrix_float32") -- that engine's
+  // -- shape: the vector scan's, or -- a call a matrix engine takes ("scan_matrix", "scan_matrix_float", "scan_matrix_float32"; a
+  // grouped call: with "scan_matrix_grouped" as well) -- that engine's
   const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
   if (vector_shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
-  const ScanMatrixShape matrix = grouped ? ScanMatrixShape() : scan_matrix_shape(ix, g, nq, K, live);
+  const ScanMatrixShape matrix = scan_matrix_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
   const ScanShape shape = matrix.on ? static_cast<const ScanShape&>(matrix) : vector_shape;
   const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
@@ -567,7 +572,12 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   ix->measured.drop_pending();  // ev0 / ev1 no longer bracket a graph-search launch
   HIP_TRY(hipEventRecord(ix->ev0, stream));
   if (grouped) {
-    rc = launch_grouped_scan(ix, kernel_table(ix->dtype, ix->metric).flat_g[g.cfg][g.full], gp, shape, nq, stream);
+    const KernelTable& table = kernel_table(ix->dtype, ix->metric);
+    const scan_grouped_fn kern = matrix.on ? table.flat_mg : table.flat_g[g.cfg][g.full];
+    if (!kern) return fail(FNV_ERR_RUNTIME, "the grouped matrix scan kernel of this element type is missing from the build");
+    gp.group_lanes = matrix.group_lanes;  // (the float forms: the rescoring groups, the two counters the memset above cleared)
+    gp.counters = reinterpret_cast<unsigned long long*>(block + fnv_index_s::kScanCounterWord);
+    rc = launch_grouped_scan(ix, kern, gp, shape, nq, stream);
     if (rc) return rc;
   } else {
     const KernelTable& table = kernel_table(ix->dtype, ix->metric);
@@ -594,9 +604,9 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
 
   // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
   // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments.  Modes 5 and 6: its float16 and
-  // float32 forms, likewise)
+  // float32 forms, likewise; a grouped call one of them took: the entries of its id queue where the grouped vector scan has its own)
   record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
-                grouped ? SCAN_QUEUE_IDS : 0, grouped || matrix.on ? shape.segments : 0, matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, 0);
+                !grouped ? 0 : matrix.on ? MATRIX_QUEUE_IDS : SCAN_QUEUE_IDS, grouped || matrix.on ? shape.segments : 0, matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, 0);
   return FNV_OK;
 }
 

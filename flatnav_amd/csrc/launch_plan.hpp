@@ -51,6 +51,7 @@ struct IndexOptions {
   int64_t scan_matrix = 0;  // exhaustive search on uint8 / int8 indexes: the matrix engine where it applies (scan_matrix_shape)
   int64_t scan_matrix_float = 0;  // ... on float16 indexes: the matrix prefilter with exact rescoring (scan_matrix_f16.hpp)
   int64_t scan_matrix_float32 = 0;  // ... on float32 indexes: the same on operands narrowed to bfloat16 (scan_matrix_f32.hpp)
+  int64_t scan_matrix_grouped = 0;  // ... and, with the element type's own option, the grouped exhaustive call (scan_matrix_feed.hpp)
   // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
   // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
   int64_t filter_scan_max = 0, filter_scan_on_overflow = 0;
@@ -659,6 +660,10 @@ inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t
 // a step is still sixteen elements, now FOUR chunks; the staged query is narrowed to bfloat16, so its LDS is float16's (the
 // float32 query that rescoring needs is read from global memory); the kernel keeps kScanMatrixFloat32SpanSteps steps in
 // registers (rows of 512 bytes: 128-d).  Budget and widest tile are the other engines'.
+// `filter_rows` != 0: a GROUPED call over that many filter rows.  An engine takes it only with "scan_matrix_grouped" on top of
+// its own option (else `on` is false: the grouped vector scan).  Its id queue (MATRIX_QUEUE_IDS entries, scan_matrix_feed.hpp)
+// comes out of the block's LDS budget as in scan_shape and is counted in `lds`; `tiles` is group_tile_bound's bound on the
+// data-dependent tile count; and where 32 queries, their lists and the queue exceed a block's LDS the call keeps the vector scan.
 constexpr uint32_t kScanMatrixN = 32, kScanMatrixMaxTile = 128, kScanMatrixSpanSteps = 4, kScanMatrixFloatSpanSteps = 8,
                    kScanMatrixFloat32SpanSteps = 8;
 constexpr uint32_t kScanMatrixLdsBudget = 32u << 10;  // five blocks per CU
@@ -670,18 +675,20 @@ struct ScanMatrixShape : ScanShape {
   bool float32_rows = false;  // the float32 form
   uint32_t group_lanes = 0;   // the float forms' rescoring groups: kCfgs[cfg].G
 };
-inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live) {
+inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live,
+                                         uint64_t filter_rows = 0) {
   ScanMatrixShape s;
   s.tile = s.tiles = s.segments = s.lds = 0;
   const bool bytes = ix->scan_matrix != 0 && (ix->dtype == FNV_DTYPE_UINT8 || ix->dtype == FNV_DTYPE_INT8);
   const bool halves = ix->scan_matrix_float != 0 && ix->dtype == FNV_DTYPE_FLOAT16;
   const bool floats = ix->scan_matrix_float32 != 0 && ix->dtype == FNV_DTYPE_FLOAT32;
-  if ((!bytes && !halves && !floats) || nq == 0) return s;
+  if ((!bytes && !halves && !floats) || nq == 0 || (filter_rows != 0 && ix->scan_matrix_grouped == 0)) return s;
   const uint32_t chunks_per_step = floats ? 4u : 2u;
   const uint32_t steps = (g.nchunks + g.tail_chunks + chunks_per_step - 1u) / chunks_per_step;
   const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + (bytes ? 4u : 8u);
-  if (kScanMatrixN * per_query > kScanMaxLds) return s;
-  uint32_t subtiles = std::max(1u, std::min(kScanMatrixMaxTile, kScanMatrixLdsBudget / per_query) / kScanMatrixN);
+  const uint32_t queue = filter_rows ? MATRIX_QUEUE_IDS * 4u : 0u;
+  if (kScanMatrixN * per_query + queue > kScanMaxLds) return s;
+  uint32_t subtiles = std::max(1u, std::min(kScanMatrixMaxTile, (kScanMatrixLdsBudget - queue) / per_query) / kScanMatrixN);
   if (steps > (floats ? kScanMatrixFloat32SpanSteps : halves ? kScanMatrixFloatSpanSteps : kScanMatrixSpanSteps)) subtiles = 1;
   subtiles = (uint32_t)std::min<uint64_t>(subtiles, (nq + kScanMatrixN - 1) / kScanMatrixN);
   s.on = true;
@@ -690,8 +697,8 @@ inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry
   s.float32_rows = floats;
   s.group_lanes = halves || floats ? (uint32_t)kCfgs[g.cfg].G : 0u;
   s.tile = subtiles * kScanMatrixN;
-  s.lds = s.tile * per_query;
-  s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);
+  s.lds = s.tile * per_query + queue;
+  s.tiles = (uint32_t)(filter_rows ? group_tile_bound(nq, filter_rows, s.tile) : (nq + s.tile - 1) / s.tile);
   const uint64_t per_cu = std::min<uint64_t>(kScanMatrixWavesPerCu, kLdsPerCu / lds_allocated(s.lds));
   s.segments = scan_segments(ix, s.tiles, nq, K, live, (uint64_t)std::max(1, ix->num_cus) * per_cu / s.tiles);
   return s;

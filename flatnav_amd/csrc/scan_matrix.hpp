@@ -33,10 +33,16 @@
 // against the list's real K-th key -- rows past the segment's end are dropped there, before that compare -- and insert it with
 // scan_insert.  The lists are scan.hpp's ([tile][K] keys) and leave through scan_flush_tile, so the merge does not change.
 //
-// Not taken by this engine (the call runs the vector scan): float32 and float16 indexes, grouped calls, the scan stage of a
-// routed filtered graph search, and shapes whose 32 queries and lists exceed a block's LDS.
+// Grouped calls ("scan_matrix_grouped" = 1 as well): exhaustive_scan_matrix_grouped_kernel, one wavefront per (tile descriptor,
+// row segment) as exhaustive_scan_grouped_kernel.  The tile's queries are perm[first ..] (GroupTile), up to the matrix tile; the
+// rows are the bits of the tile's filter row, turned into 32-row tiles by MatrixRowFeeder (scan_matrix_feed.hpp); the id queue
+// follows the query terms in LDS.  Everything else -- staging, terms, scoring, lists -- is the one kernel template below; the
+// ungrouped kernel keeps its own walk over the candidates, so it compiles to the code it was before the grouped form existed.
+//
+// Not taken by this engine (the call runs the vector scan): float32 and float16 indexes, grouped calls without that option, the
+// scan stage of a routed filtered graph search, and shapes whose 32 queries and lists exceed a block's LDS.
 #pragma once
-#include "scan.hpp"
+#include "scan_matrix_feed.hpp"
 namespace fnv_dev {
 
 typedef int ms_i32x4 __attribute__((ext_vector_type(4)));
@@ -44,8 +50,11 @@ typedef int ms_i32x16 __attribute__((ext_vector_type(16)));
 constexpr int MS_N = 32;    // the MFMA's N: queries per sub-tile (and its M: rows per row tile)
 constexpr int MS_SPAN = 4;  // MFMA steps (32 bytes of a row each) a lane keeps in registers: rows of up to 128 bytes whole
 
-template <typename T, int METRIC>
-__global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const ScanParams p) {
+// One kernel template for both kinds of call.  GROUPED: the parameter block is the grouped launch's, `gp` points at it.
+template <typename T, int METRIC, bool GROUPED>
+__global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_any_kernel(const std::conditional_t<GROUPED, GroupedScanParams, ScanParams> kp) {
+  const ScanParams& p = matrix_scan_params(kp);
+  [[maybe_unused]] const GroupedScanParams* const gp = matrix_grouped_params(kp);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef Dist<T, METRIC> D;
   constexpr bool FLIP = !D::SIGNED;                                // uint8: bytes go through the signed MFMA as x - 128
@@ -53,8 +62,11 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const Scan
   constexpr bool SIDE = L2 || FLIP;                                // a term per row and one per query on top of the dot
   const int lane = threadIdx.x, col = lane & (MS_N - 1), half = lane >> 5;
   const uint32_t tile = blockIdx.x % p.tiles, seg = blockIdx.x / p.tiles;
-  const uint32_t q0 = tile * p.tile_queries;
-  const uint32_t nqb = min(p.tile_queries, p.nq - q0);
+  GroupTile gt = {0u, 0u, 0u};
+  if constexpr (GROUPED) gt = gp->tiles[tile];
+  const uint32_t q0 = tile * p.tile_queries;  // (an ungrouped call's first query)
+  const uint32_t nqb = GROUPED ? gt.count : min(p.tile_queries, p.nq - q0);
+  if (GROUPED && nqb == 0u) return;  // (past the real tiles: the launch is an upper bound)
   const uint32_t nsub = (nqb + MS_N - 1) / MS_N;
   const int K = (int)p.K;
   const uint32_t nchunks = p.nchunks, tc = p.tail_chunks, C = nchunks + tc;
@@ -62,7 +74,10 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const Scan
   uint4* const qlds = reinterpret_cast<uint4*>(smem);                                                            // [tile / 32][S][64]
   uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * (uint32_t)S * 32u);        // [tile][K]
   int* const qterm = reinterpret_cast<int*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u));     // [tile]
-  const auto query_of = [&](uint32_t qq) { return q0 + qq; };
+  const auto query_of = [&](uint32_t qq) {
+    if constexpr (GROUPED) return gp->perm[gt.first + qq];
+    else return q0 + qq;
+  };
 
   // ---- the tile's queries in operand order (zero beyond dim, flipped over the P elements the rows cover), their terms, the lists
   for (uint32_t i = lane; i < nsub * (uint32_t)S * 64u; i += WAVE) {
@@ -70,7 +85,7 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const Scan
     const uint32_t qq = t * MS_N + (l & 31u), c = 2u * s + (l >> 5);
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (qq < nqb && c < C) {
-      const uint8_t* qsrc = p.queries + (uint64_t)(q0 + qq) * p.dim;
+      const uint8_t* qsrc = p.queries + (uint64_t)(GROUPED ? query_of(qq) : q0 + qq) * p.dim;
 #pragma unroll
       for (uint32_t e = 0; e < 16u; e++) {
         const uint32_t at = c * 16u + e;
@@ -99,8 +114,9 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const Scan
     wave_sync();
   }
 
-  // ---- this block's share of the candidates, 32 rows a step
-  const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
+  // ---- this block's share of the candidates, 32 rows a step: slots [lo, hi) of the id list or of the live nodes (a grouped
+  // call: the bits of the tile's filter row, below)
+  const uint64_t ncand = GROUPED ? 0u : p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
   const uint64_t lo = ncand * seg / p.segments, hi = ncand * (seg + 1) / p.segments;
   const bool one_span = S <= MS_SPAN;
   // Row `id`'s steps s0 .. s0 + MS_SPAN - 1 (this lane's chunk of each) as they lie in the table.  No branch at all and no use
@@ -140,17 +156,17 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const Scan
     }
     return r;
   };
-  const auto row_of = [&](uint64_t base, uint32_t* id) {  // the lane's row of the tile that starts at candidate `base`
+  [[maybe_unused]] const auto row_of = [&](uint64_t base, uint32_t* id) {  // the lane's row of the tile that starts at candidate `base`
     const uint64_t slot = base + (uint64_t)col;
     const bool valid = slot < hi;
     *id = valid ? (p.cand_ids ? p.cand_ids[slot] : (uint32_t)slot) : 0u;
     return valid;
   };
 
-  // One 32-row tile (candidates base .. base + 31; `a`: its first span as load_span left it, when rows are one span) against
+  // One 32-row tile (candidates base .. base + 31 -- a grouped call: `base` IS the number of its rows, the feeder's nrows(); `a`: its first span as load_span left it, when rows are one span) against
   // every sub-tile of the query tile.
   const auto score_tile = [&](ms_i32x4 (&a)[MS_SPAN], uint32_t id, bool valid, uint64_t base) __attribute__((always_inline)) {
-    const uint32_t nrows = (uint32_t)min((uint64_t)MS_N, hi - base);
+    const uint32_t nrows = GROUPED ? (uint32_t)base : (uint32_t)min((uint64_t)MS_N, hi - base);
     int rterm = 0;  // the row's term, whole in both lanes of the row once its spans are summed
     int rv[16];     // ... and of the sixteen rows this lane's accumulators belong to
     const auto spread_term = [&]() {
@@ -221,19 +237,43 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_kernel(const Scan
   ms_i32x4 a0[MS_SPAN], a1[MS_SPAN];
   uint32_t id0 = 0, id1 = 0;
   bool valid0 = false, valid1 = false;
-  const auto request = [&](ms_i32x4 (&a)[MS_SPAN], uint32_t* id, bool* valid, uint64_t base) __attribute__((always_inline)) {
-    *valid = row_of(base, id);  // (a tile past the segment's end: no lane has a row, all read row 0)
-    if (one_span) load_span(a, *id, 0);
-  };
-  request(a0, &id0, &valid0, lo);
-  for (uint64_t base = lo; base < hi; base += 2 * MS_N) {
-    request(a1, &id1, &valid1, base + MS_N);
-    score_tile(a0, id0, valid0, base);
-    if (base + MS_N >= hi) break;
-    request(a0, &id0, &valid0, base + 2 * MS_N);
-    score_tile(a1, id1, valid1, base + MS_N);
+  if constexpr (GROUPED) {  // the rows are the bits of the tile's filter row over this segment's words (scan_matrix_feed.hpp)
+    uint32_t* const queue = reinterpret_cast<uint32_t*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u + 4u));
+    MatrixRowFeeder src(queue, gp, gt.row, seg, p.segments, lane);
+    const auto request = [&](ms_i32x4 (&a)[MS_SPAN], uint32_t* id, bool* valid, int k) __attribute__((always_inline)) {
+      *valid = src.row(k, id);  // (no such tile: no lane has a row, all read row 0)
+      if (one_span) load_span(a, *id, 0);
+    };
+    request(a0, &id0, &valid0, 0);
+    while (src.more()) {
+      request(a1, &id1, &valid1, 1);
+      score_tile(a0, id0, valid0, src.nrows());
+      src.advance();
+      if (!src.more()) break;
+      request(a0, &id0, &valid0, 1);
+      score_tile(a1, id1, valid1, src.nrows());
+      src.advance();
+    }
+  } else {
+    const auto request = [&](ms_i32x4 (&a)[MS_SPAN], uint32_t* id, bool* valid, uint64_t base) __attribute__((always_inline)) {
+      *valid = row_of(base, id);  // (a tile past the segment's end: no lane has a row, all read row 0)
+      if (one_span) load_span(a, *id, 0);
+    };
+    request(a0, &id0, &valid0, lo);
+    for (uint64_t base = lo; base < hi; base += 2 * MS_N) {
+      request(a1, &id1, &valid1, base + MS_N);
+      score_tile(a0, id0, valid0, base);
+      if (base + MS_N >= hi) break;
+      request(a0, &id0, &valid0, base + 2 * MS_N);
+      score_tile(a1, id1, valid1, base + MS_N);
+    }
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
 }
+
+template <typename T, int METRIC>
+constexpr scan_fn exhaustive_scan_matrix_kernel = exhaustive_scan_matrix_any_kernel<T, METRIC, false>;
+template <typename T, int METRIC>
+constexpr scan_grouped_fn exhaustive_scan_matrix_grouped_kernel = exhaustive_scan_matrix_any_kernel<T, METRIC, true>;
 
 }  // namespace fnv_dev

@@ -36,10 +36,14 @@
 // 3. Counters.  A block adds {pairs scored, pairs rescored} to the launch's two counters with one atomic each
 //    (fnv_last_replayed_queries reports them); out_ndist stays the candidate count.
 //
-// Not taken by this engine (the call keeps its own): float32 and 1-byte indexes, grouped calls, the scan stage of a routed
-// filtered graph search, and shapes whose 32 queries and lists exceed a block's LDS.
+// Grouped calls ("scan_matrix_grouped" = 1 as well): exhaustive_scan_matrix_f16_grouped_kernel, as scan_matrix.hpp's grouped
+// form -- the tile's queries are perm[first ..], its rows the bits of its filter row by way of MatrixRowFeeder
+// (scan_matrix_feed.hpp), the id queue behind the query terms in LDS; one kernel template, the ungrouped walk kept as it was.
+//
+// Not taken by this engine (the call keeps its own): float32 and 1-byte indexes, grouped calls without that option, the scan
+// stage of a routed filtered graph search, and shapes whose 32 queries and lists exceed a block's LDS.
 #pragma once
-#include "scan.hpp"
+#include "scan_matrix_feed.hpp"
 namespace fnv_dev {
 
 typedef _Float16 mf_f16x8 __attribute__((ext_vector_type(8)));
@@ -57,7 +61,7 @@ __device__ __forceinline__ uint32_t mf_row(int v, int half) { return (uint32_t)(
 // exactly and offered to their lists.  `qsub`: the sub-tile's queries in operand order, `sublists`: its lists, `id`: the row
 // tile's node ids (lane l: row l % 32).  Returns how many there were.
 template <int METRIC, int G>
-__device__ __forceinline__ uint32_t mf_rescore(const ScanMatrixFloatParams& p, const uint4* qsub, uint64_t* sublists, uint32_t mine,
+__device__ __forceinline__ uint32_t mf_rescore(const ScanParams& p, const uint4* qsub, uint64_t* sublists, uint32_t mine,
                                                uint32_t id, int lane) {
   typedef Dist<_Float16, METRIC> D;
   constexpr int VPW = WAVE / G;
@@ -98,14 +102,20 @@ __device__ __forceinline__ uint32_t mf_rescore(const ScanMatrixFloatParams& p, c
   return total;
 }
 
-template <int METRIC>
-__global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const ScanMatrixFloatParams p) {
+// One kernel template for both kinds of call.  GROUPED: the parameter block is the grouped launch's, `gp` points at it.
+template <int METRIC, bool GROUPED>
+__global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_any_kernel(const std::conditional_t<GROUPED, GroupedScanParams, ScanMatrixFloatParams> kp) {
+  const ScanParams& p = matrix_scan_params(kp);
+  [[maybe_unused]] const GroupedScanParams* const gp = matrix_grouped_params(kp);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool L2 = METRIC == FNV_METRIC_L2;
   const int lane = threadIdx.x, col = lane & (MF_N - 1), half = lane >> 5;
   const uint32_t tile = blockIdx.x % p.tiles, seg = blockIdx.x / p.tiles;
-  const uint32_t q0 = tile * p.tile_queries;
-  const uint32_t nqb = min(p.tile_queries, p.nq - q0);
+  GroupTile gt = {0u, 0u, 0u};
+  if constexpr (GROUPED) gt = gp->tiles[tile];
+  const uint32_t q0 = tile * p.tile_queries;  // (an ungrouped call's first query)
+  const uint32_t nqb = GROUPED ? gt.count : min(p.tile_queries, p.nq - q0);
+  if (GROUPED && nqb == 0u) return;  // (past the real tiles: the launch is an upper bound)
   const uint32_t nsub = (nqb + MF_N - 1) / MF_N;
   const int K = (int)p.K;
   const uint32_t nchunks = p.nchunks, tc = p.tail_chunks, C = nchunks + tc;
@@ -114,7 +124,10 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const 
   uint4* const qlds = reinterpret_cast<uint4*>(smem);                                                            // [tile / 32][S][64]
   uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * (uint32_t)S * 32u);        // [tile][K]
   float2* const qterm = reinterpret_cast<float2*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u));  // [tile] {qn, margin term}
-  const auto query_of = [&](uint32_t qq) { return q0 + qq; };
+  const auto query_of = [&](uint32_t qq) {
+    if constexpr (GROUPED) return gp->perm[gt.first + qq];
+    else return q0 + qq;
+  };
 
   // ---- the tile's queries in operand order (zero beyond dim and beyond the tile), their norms and margin terms, the lists
   for (uint32_t i = lane; i < nsub * (uint32_t)S * 64u; i += WAVE) {
@@ -122,7 +135,7 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const 
     const uint32_t qq = t * MF_N + (l & 31u), c = 2u * s + (l >> 5);
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (qq < nqb && c < C) {
-      const uint16_t* qsrc = reinterpret_cast<const uint16_t*>(p.queries) + (uint64_t)(q0 + qq) * p.dim;
+      const uint16_t* qsrc = reinterpret_cast<const uint16_t*>(p.queries) + (uint64_t)(GROUPED ? query_of(qq) : q0 + qq) * p.dim;
 #pragma unroll
       for (uint32_t e = 0; e < 8u; e++) {
         const uint32_t at = c * 8u + e;
@@ -143,8 +156,9 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const 
   }
   wave_sync();
 
-  // ---- this block's share of the candidates, 32 rows a step
-  const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
+  // ---- this block's share of the candidates, 32 rows a step: slots [lo, hi) of the id list or of the live nodes (a grouped
+  // call: the bits of the tile's filter row, below)
+  const uint64_t ncand = GROUPED ? 0u : p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
   const uint64_t lo = ncand * seg / p.segments, hi = ncand * (seg + 1) / p.segments;
   const bool one_span = S <= MF_SPAN;
   unsigned long long scored = 0, rescored = 0;  // (wave-uniform) this block's pairs
@@ -179,17 +193,17 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const 
     }
     return r;
   };
-  const auto row_of = [&](uint64_t base, uint32_t* id) {  // the lane's row of the tile that starts at candidate `base`
+  [[maybe_unused]] const auto row_of = [&](uint64_t base, uint32_t* id) {  // the lane's row of the tile that starts at candidate `base`
     const uint64_t slot = base + (uint64_t)col;
     const bool valid = slot < hi;
     *id = valid ? (p.cand_ids ? p.cand_ids[slot] : (uint32_t)slot) : 0u;
     return valid;
   };
 
-  // One 32-row tile (candidates base .. base + 31; `a`: its first span as load_span left it, when rows are one span) against
+  // One 32-row tile (candidates base .. base + 31 -- a grouped call: `base` IS the number of its rows, the feeder's nrows(); `a`: its first span as load_span left it, when rows are one span) against
   // every sub-tile of the query tile.
   const auto score_tile = [&](mf_u32x4 (&a)[MF_SPAN], uint32_t id, bool valid, uint64_t base) __attribute__((always_inline)) {
-    const uint32_t nrows = (uint32_t)min((uint64_t)MF_N, hi - base);
+    const uint32_t nrows = GROUPED ? (uint32_t)base : (uint32_t)min((uint64_t)MF_N, hi - base);
     f32x2 rsum = {0.f, 0.f};  // the squares of the lane's chunks of its row
     float rv[16], rt[16];     // the norms and margin terms of the sixteen rows this lane's accumulators belong to
     const auto spread_terms = [&]() {
@@ -247,7 +261,7 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const 
       if (__ballot(mine != 0u)) {  // about K ln(n / K) rows per query, and what the margin adds
         uint64_t* const sublists = lists + (size_t)t * MF_N * K;
         uint32_t n = 0;
-        switch (p.group_lanes) {  // the row configurations of float16 rows (search_types.h, kCfgs)
+        switch (kp.group_lanes) {  // the row configurations of float16 rows (search_types.h, kCfgs)
           case 8: n = mf_rescore<METRIC, 8>(p, qsub, sublists, mine, id, lane); break;
           case 16: n = mf_rescore<METRIC, 16>(p, qsub, sublists, mine, id, lane); break;
           case 32: n = mf_rescore<METRIC, 32>(p, qsub, sublists, mine, id, lane); break;
@@ -262,23 +276,47 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_kernel(const 
   mf_u32x4 a0[MF_SPAN], a1[MF_SPAN];
   uint32_t id0 = 0, id1 = 0;
   bool valid0 = false, valid1 = false;
-  const auto request = [&](mf_u32x4 (&a)[MF_SPAN], uint32_t* id, bool* valid, uint64_t base) __attribute__((always_inline)) {
-    *valid = row_of(base, id);  // (a tile past the segment's end: no lane has a row, all read row 0)
-    if (one_span) load_span(a, *id, 0);
-  };
-  request(a0, &id0, &valid0, lo);
-  for (uint64_t base = lo; base < hi; base += 2 * MF_N) {
-    request(a1, &id1, &valid1, base + MF_N);
-    score_tile(a0, id0, valid0, base);
-    if (base + MF_N >= hi) break;
-    request(a0, &id0, &valid0, base + 2 * MF_N);
-    score_tile(a1, id1, valid1, base + MF_N);
+  if constexpr (GROUPED) {  // the rows are the bits of the tile's filter row over this segment's words (scan_matrix_feed.hpp)
+    uint32_t* const queue = reinterpret_cast<uint32_t*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u + 8u));
+    MatrixRowFeeder src(queue, gp, gt.row, seg, p.segments, lane);
+    const auto request = [&](mf_u32x4 (&a)[MF_SPAN], uint32_t* id, bool* valid, int k) __attribute__((always_inline)) {
+      *valid = src.row(k, id);  // (no such tile: no lane has a row, all read row 0)
+      if (one_span) load_span(a, *id, 0);
+    };
+    request(a0, &id0, &valid0, 0);
+    while (src.more()) {
+      request(a1, &id1, &valid1, 1);
+      score_tile(a0, id0, valid0, src.nrows());
+      src.advance();
+      if (!src.more()) break;
+      request(a0, &id0, &valid0, 1);
+      score_tile(a1, id1, valid1, src.nrows());
+      src.advance();
+    }
+  } else {
+    const auto request = [&](mf_u32x4 (&a)[MF_SPAN], uint32_t* id, bool* valid, uint64_t base) __attribute__((always_inline)) {
+      *valid = row_of(base, id);  // (a tile past the segment's end: no lane has a row, all read row 0)
+      if (one_span) load_span(a, *id, 0);
+    };
+    request(a0, &id0, &valid0, lo);
+    for (uint64_t base = lo; base < hi; base += 2 * MF_N) {
+      request(a1, &id1, &valid1, base + MF_N);
+      score_tile(a0, id0, valid0, base);
+      if (base + MF_N >= hi) break;
+      request(a0, &id0, &valid0, base + 2 * MF_N);
+      score_tile(a1, id1, valid1, base + MF_N);
+    }
   }
   if (lane == 0) {
-    atomicAdd(p.counters, scored);
-    atomicAdd(p.counters + 1, rescored);
+    atomicAdd(kp.counters, scored);
+    atomicAdd(kp.counters + 1, rescored);
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
 }
+
+template <int METRIC>
+constexpr scan_mf_fn exhaustive_scan_matrix_f16_kernel = exhaustive_scan_matrix_f16_any_kernel<METRIC, false>;
+template <int METRIC>
+constexpr scan_grouped_fn exhaustive_scan_matrix_f16_grouped_kernel = exhaustive_scan_matrix_f16_any_kernel<METRIC, true>;
 
 }  // namespace fnv_dev

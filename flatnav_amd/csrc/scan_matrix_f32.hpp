@@ -41,10 +41,15 @@
 //    thousand gets here on real data), elements at or past dim zero.
 // 3. Counters.  {pairs scored, pairs rescored}, one atomic each per block; out_ndist stays the candidate count.
 //
-// Not taken by this engine (the call keeps its own): other element types, grouped calls, the scan stage of a routed filtered
-// graph search, and shapes whose 32 queries and lists exceed a block's LDS.
+// Grouped calls ("scan_matrix_grouped" = 1 as well): exhaustive_scan_matrix_f32_grouped_kernel, as scan_matrix.hpp's grouped
+// form -- the tile's queries are perm[first ..] (rescoring finds a survivor's float32 query through perm as well), its rows the
+// bits of its filter row by way of MatrixRowFeeder (scan_matrix_feed.hpp), the id queue behind the query terms in LDS; one
+// kernel template, the ungrouped staging and walk kept as they were (a grouped lane looks its query up in perm once per sub-tile).
+//
+// Not taken by this engine (the call keeps its own): other element types, grouped calls without that option, the scan stage of
+// a routed filtered graph search, and shapes whose 32 queries and lists exceed a block's LDS.
 #pragma once
-#include "scan.hpp"
+#include "scan_matrix_feed.hpp"
 namespace fnv_dev {
 
 typedef __bf16 mf32_bf16x2 __attribute__((ext_vector_type(2)));
@@ -71,11 +76,10 @@ __device__ __forceinline__ f32x2 mf32_squares(f32x2 acc, const mf32_u32x4& x) {
 __device__ __forceinline__ uint32_t mf32_row(int v, int half) { return (uint32_t)(8 * (v >> 2) + (v & 3) + 4 * half); }
 
 // The survivors of one (row tile, sub-tile) -- bit v of `mine`: this lane's query against row mf32_row(v, lane / 32) -- scored
-// exactly and offered to their lists.  `qsub`: the sub-tile's first query in p.queries, `sublists`: its lists, `id`: the row
-// tile's node ids (lane l: row l % 32).  Returns how many there were.
-template <int METRIC, int G>
-__device__ __forceinline__ uint32_t mf32_rescore(const ScanMatrixFloatParams& p, const float* qsub, uint64_t* sublists, uint32_t mine,
-                                                 uint32_t id, int lane) {
+// exactly and offered to their lists.  `query_at(j)`: the float32 query of the sub-tile's column j in p.queries, `sublists`: its
+// lists, `id`: the row tile's node ids (lane l: row l % 32).  Returns how many there were.
+template <int METRIC, int G, typename F>
+__device__ __forceinline__ uint32_t mf32_rescore(const ScanParams& p, F query_at, uint64_t* sublists, uint32_t mine, uint32_t id, int lane) {
   typedef Dist<float, METRIC> D;
   constexpr int VPW = WAVE / G;
   const uint32_t g = (uint32_t)(lane % G);
@@ -95,7 +99,7 @@ __device__ __forceinline__ uint32_t mf32_rescore(const ScanMatrixFloatParams& p,
       if (on) {
         const uint8_t* const rowp = p.vectors + (uint64_t)node * p.row_bytes;
         const uint8_t* const tailp = p.tails + (uint64_t)node * tc * 16u;
-        const float* const qp = qsub + (uint64_t)j * dim;  // (a query row is aligned to its elements only)
+        const float* const qp = query_at(j);  // (a query row is aligned to its elements only)
         for (uint32_t c = g; c < nchunks + tc; c += G) {
           uint32_t w[4];
 #pragma unroll
@@ -120,14 +124,21 @@ __device__ __forceinline__ uint32_t mf32_rescore(const ScanMatrixFloatParams& p,
 }
 
 // (two wavefronts per SIMD: 256 registers each -- raw 64, narrowed 32, accumulators 16, row terms 32)
-template <int METRIC>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void exhaustive_scan_matrix_f32_kernel(const ScanMatrixFloatParams p) {
+// One kernel template for both kinds of call.  GROUPED: the parameter block is the grouped launch's, `gp` points at it.
+template <int METRIC, bool GROUPED>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void exhaustive_scan_matrix_f32_any_kernel(
+    const std::conditional_t<GROUPED, GroupedScanParams, ScanMatrixFloatParams> kp) {
+  const ScanParams& p = matrix_scan_params(kp);
+  [[maybe_unused]] const GroupedScanParams* const gp = matrix_grouped_params(kp);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool L2 = METRIC == FNV_METRIC_L2;
   const int lane = threadIdx.x, col = lane & (MF32_N - 1), half = lane >> 5;
   const uint32_t tile = blockIdx.x % p.tiles, seg = blockIdx.x / p.tiles;
-  const uint32_t q0 = tile * p.tile_queries;
-  const uint32_t nqb = min(p.tile_queries, p.nq - q0);
+  GroupTile gt = {0u, 0u, 0u};
+  if constexpr (GROUPED) gt = gp->tiles[tile];
+  const uint32_t q0 = tile * p.tile_queries;  // (an ungrouped call's first query)
+  const uint32_t nqb = GROUPED ? gt.count : min(p.tile_queries, p.nq - q0);
+  if (GROUPED && nqb == 0u) return;  // (past the real tiles: the launch is an upper bound)
   const uint32_t nsub = (nqb + MF32_N - 1) / MF32_N;
   const int K = (int)p.K;
   const uint32_t nchunks = p.nchunks, tc = p.tail_chunks, C = nchunks + tc, dim = p.dim;
@@ -137,25 +148,49 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
   uint64_t* const lists = reinterpret_cast<uint64_t*>(smem + (size_t)p.tile_queries * (uint32_t)S * 32u);        // [tile][K]
   float2* const qterm = reinterpret_cast<float2*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u));  // [tile] {qn, margin term}
   const float* const queries = reinterpret_cast<const float*>(p.queries) + (uint64_t)q0 * dim;  // the tile's first query
-  const auto query_of = [&](uint32_t qq) { return q0 + qq; };
+  const auto query_of = [&](uint32_t qq) {
+    if constexpr (GROUPED) return gp->perm[gt.first + qq];
+    else return q0 + qq;
+  };
+  // the float32 query of tile slot qq (a grouped call: through the permutation)
+  const auto query_ptr = [&](uint32_t qq) {
+    if constexpr (GROUPED) return reinterpret_cast<const float*>(p.queries) + (uint64_t)gp->perm[gt.first + qq] * dim;
+    else return queries + (uint64_t)qq * dim;
+  };
 
   // ---- the tile's queries narrowed into operand order (zero beyond dim and beyond the tile), their norms and margin terms
   // from the float32 values, the lists
-  for (uint32_t i = lane; i < nsub * (uint32_t)S * 64u; i += WAVE) {
-    const uint32_t l = i & 63u, st = i >> 6, s = st % (uint32_t)S, t = st / (uint32_t)S;
-    const uint32_t qq = t * MF32_N + (l & 31u), e0 = 16u * s + 8u * (l >> 5);
-    uint32_t w[8];
+  if constexpr (GROUPED) {  // (a lane stages ONE query per sub-tile: its place in the permutation is looked up once)
+    for (uint32_t t = 0; t < nsub; t++) {
+      const uint32_t qq = t * MF32_N + (uint32_t)col;
+      const float* const qsrc = query_ptr(qq < nqb ? qq : 0u);
+      for (uint32_t s = 0; s < (uint32_t)S; s++) {
+        const uint32_t e0 = 16u * s + 8u * (uint32_t)half;
+        uint32_t w[8];
 #pragma unroll
-    for (uint32_t e = 0; e < 8u; e++) w[e] = qq < nqb && e0 + e < dim ? __float_as_uint(queries[(uint64_t)qq * dim + e0 + e]) : 0u;
-    const mf32_u32x4 x = mf32_narrow8(mf32_u32x4{w[0], w[1], w[2], w[3]}, mf32_u32x4{w[4], w[5], w[6], w[7]});
-    qlds[i] = make_uint4(x[0], x[1], x[2], x[3]);
+        for (uint32_t e = 0; e < 8u; e++) w[e] = qq < nqb && e0 + e < dim ? __float_as_uint(qsrc[e0 + e]) : 0u;
+        const mf32_u32x4 x = mf32_narrow8(mf32_u32x4{w[0], w[1], w[2], w[3]}, mf32_u32x4{w[4], w[5], w[6], w[7]});
+        qlds[(t * (uint32_t)S + s) * 64u + (uint32_t)lane] = make_uint4(x[0], x[1], x[2], x[3]);
+      }
+    }
+  } else {
+    for (uint32_t i = lane; i < nsub * (uint32_t)S * 64u; i += WAVE) {
+      const uint32_t l = i & 63u, st = i >> 6, s = st % (uint32_t)S, t = st / (uint32_t)S;
+      const uint32_t qq = t * MF32_N + (l & 31u), e0 = 16u * s + 8u * (l >> 5);
+      uint32_t w[8];
+#pragma unroll
+      for (uint32_t e = 0; e < 8u; e++) w[e] = qq < nqb && e0 + e < dim ? __float_as_uint(queries[(uint64_t)qq * dim + e0 + e]) : 0u;
+      const mf32_u32x4 x = mf32_narrow8(mf32_u32x4{w[0], w[1], w[2], w[3]}, mf32_u32x4{w[4], w[5], w[6], w[7]});
+      qlds[i] = make_uint4(x[0], x[1], x[2], x[3]);
+    }
   }
   for (uint32_t i = lane; i < nqb * p.K; i += WAVE) lists[i] = SCAN_PAD;
   for (uint32_t qq = lane; qq < nsub * MF32_N; qq += WAVE) {
     float qn = 0.f;
     if (qq < nqb) {
+      [[maybe_unused]] const float* const qsrc = query_ptr(qq);
       for (uint32_t e = 0; e < dim; e++) {
-        const float x = queries[(uint64_t)qq * dim + e];
+        const float x = GROUPED ? qsrc[e] : queries[(uint64_t)qq * dim + e];
         qn = __builtin_fmaf(x, x, qn);
       }
     }
@@ -164,7 +199,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
   wave_sync();
 
   // ---- this block's share of the candidates, 32 rows a step
-  const uint64_t ncand = p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
+  const uint64_t ncand = GROUPED ? 0u : p.cand_ids ? (uint64_t)*p.cand_count : p.n_live;
   const uint64_t lo = ncand * seg / p.segments, hi = ncand * (seg + 1) / p.segments;
   const bool one_span = S <= MF32_SPAN;
   unsigned long long scored = 0, rescored = 0;  // (wave-uniform) this block's pairs
@@ -201,7 +236,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
       }
     }
   };
-  const auto row_of = [&](uint64_t base, uint32_t* id) {  // the lane's row of the tile that starts at candidate `base`
+  [[maybe_unused]] const auto row_of = [&](uint64_t base, uint32_t* id) {  // the lane's row of the tile that starts at candidate `base`
     const uint64_t slot = base + (uint64_t)col;
     const bool valid = slot < hi;
     *id = valid ? (p.cand_ids ? p.cand_ids[slot] : (uint32_t)slot) : 0u;
@@ -210,12 +245,20 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
 
   mf32_u32x4 raw[MF32_SPAN][2], a[MF32_SPAN];
   uint32_t next_id = 0;
-  bool next_valid = row_of(lo, &next_id);
+  // The walk over the 32-row tiles: candidates base .. base + 31 of [lo, hi), or -- a grouped call -- what the feeder hands out
+  // from the bits of the tile's filter row over this segment's words (scan_matrix_feed.hpp; its queue lies behind the query terms).
+  uint32_t* const queue = reinterpret_cast<uint32_t*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u + 8u));
+  std::conditional_t<GROUPED, MatrixRowFeeder, MatrixNoFeeder> src(queue, gp, gt.row, seg, p.segments, lane);
+  const auto next_row = [&](uint64_t base, uint32_t* id) {  // this lane's row of the tile after the current one
+    if constexpr (GROUPED) return src.row(1, id);
+    else return row_of(base + MF32_N, id);
+  };
+  bool next_valid = GROUPED ? src.row(0, &next_id) : row_of(lo, &next_id);
   load_span(raw, next_id, 0);
-  for (uint64_t base = lo; base < hi; base += MF32_N) {
+  for (uint64_t base = lo; GROUPED ? src.more() : base < hi; base += MF32_N, src.advance()) {
     const uint32_t id = next_id;
     const bool valid = next_valid;
-    const uint32_t nrows = (uint32_t)min((uint64_t)MF32_N, hi - base);
+    const uint32_t nrows = GROUPED ? src.nrows() : (uint32_t)min((uint64_t)MF32_N, hi - base);
     f32x2 rsum = {0.f, 0.f};  // the squares of the lane's chunks of its row
     float rv[16], rt[16];     // the norms and margin terms of the sixteen rows this lane's accumulators belong to
     for (uint32_t t = 0; t < nsub; t++) {
@@ -227,7 +270,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
           narrow_span(a, sq, raw, valid, s0);
           if (t == 0) rsum = sq;
           const bool same_rows = !one_span && (s0 + MF32_SPAN < S || t + 1 < nsub);
-          if (!same_rows) next_valid = row_of(base + MF32_N, &next_id);  // (past the segment's end: no lane has a row, all read row 0)
+          if (!same_rows) next_valid = next_row(base, &next_id);  // (past the segment's end: no lane has a row, all read row 0)
           load_span(raw, same_rows ? id : next_id, s0 + MF32_SPAN < S ? s0 + MF32_SPAN : 0);
         }
 #pragma unroll
@@ -270,23 +313,31 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
       scored += (unsigned long long)nrows * min((uint32_t)MF32_N, nqb - t * MF32_N);
       if (__ballot(mine != 0u)) {  // about K ln(n / K) rows per query, and what the margin adds
         uint64_t* const sublists = lists + (size_t)t * MF32_N * K;
-        const float* const qfirst = queries + (uint64_t)t * MF32_N * dim;
+        [[maybe_unused]] const float* const qfirst = queries + (uint64_t)t * MF32_N * dim;
+        const auto query_at = [&](uint32_t j) {
+          if constexpr (GROUPED) return query_ptr(t * MF32_N + j);
+          else return qfirst + (uint64_t)j * dim;
+        };
         uint32_t n = 0;
-        switch (p.group_lanes) {  // the row configurations of float32 rows (search_types.h, kCfgs)
-          case 8: n = mf32_rescore<METRIC, 8>(p, qfirst, sublists, mine, id, lane); break;
-          case 16: n = mf32_rescore<METRIC, 16>(p, qfirst, sublists, mine, id, lane); break;
-          case 32: n = mf32_rescore<METRIC, 32>(p, qfirst, sublists, mine, id, lane); break;
-          default: n = mf32_rescore<METRIC, 64>(p, qfirst, sublists, mine, id, lane); break;
+        switch (kp.group_lanes) {  // the row configurations of float32 rows (search_types.h, kCfgs)
+          case 8: n = mf32_rescore<METRIC, 8>(p, query_at, sublists, mine, id, lane); break;
+          case 16: n = mf32_rescore<METRIC, 16>(p, query_at, sublists, mine, id, lane); break;
+          case 32: n = mf32_rescore<METRIC, 32>(p, query_at, sublists, mine, id, lane); break;
+          default: n = mf32_rescore<METRIC, 64>(p, query_at, sublists, mine, id, lane); break;
         }
         rescored += n;
       }
     }
   }
   if (lane == 0) {
-    atomicAdd(p.counters, scored);
-    atomicAdd(p.counters + 1, rescored);
+    atomicAdd(kp.counters, scored);
+    atomicAdd(kp.counters + 1, rescored);
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
 }
+template <int METRIC>
+constexpr scan_mf_fn exhaustive_scan_matrix_f32_kernel = exhaustive_scan_matrix_f32_any_kernel<METRIC, false>;
+template <int METRIC>
+constexpr scan_grouped_fn exhaustive_scan_matrix_f32_grouped_kernel = exhaustive_scan_matrix_f32_any_kernel<METRIC, true>;
 
 }  // namespace fnv_dev

@@ -272,6 +272,11 @@ inline uint32_t group_tiles_layout(const uint32_t* counts, uint32_t rows, uint32
 // 1280-byte LDS granules, eight blocks per CU as the plain scan; and a queue that holds less than a batch (at most 24 rows)
 // plus one 32-node word could not make progress.
 constexpr uint32_t SCAN_QUEUE_IDS = 256;
+// The matrix engines' grouped forms ("scan_matrix_grouped"; scan_matrix_feed.hpp) queue ids the same way and hand them out as
+// 32-row tiles, the tile after the current one already requested from HBM: the queue is refilled whenever it holds fewer than
+// two tiles, so it must take 63 leftovers and one 32-node word (95 ids) to make progress.  256 ids = 1 KB again: a refill then
+// queues six tiles' worth of a dense row at once, and the prefix over the words' popcounts is paid once per six tiles.
+constexpr uint32_t MATRIX_QUEUE_IDS = 256;
 
 // Parameter block of the grouped scan and its merge: the plain block (cand_ids / cand_count null, tiles = the launched bound)
 // and what grouping adds.
@@ -284,6 +289,8 @@ struct GroupedScanParams {
   const uint32_t* row_count;   // [n_filters + 2] nodes set in each row = the candidates of its queries
   uint32_t row_words;          // words per bitmap row: ceil(capacity / 32)
   uint32_t live_words;         // ceil(n_live / 32): the segments cut [0, live_words) in whole words
+  uint32_t group_lanes;        // the float matrix engines' grouped forms only: as ScanMatrixFloatParams
+  unsigned long long* counters;
 };
 
 }  // namespace fnv_dev

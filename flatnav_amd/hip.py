@@ -582,6 +582,8 @@ class DeviceIndex:
         out["tail_exact"] = int(g[7])
         if int(g[6]) in (4, 5, 6):
             out["tile_queries"], out["segments"] = int(g[3]), int(g[5])
+            if int(g[4]):  # a grouped call ("scan_matrix_grouped"): the engine's id queue
+                out["queue_ids"] = int(g[4])
         if int(g[6]) == 3 and int(g[4]):  # the grouped scan reports its tiling in the slots the graph search's layout uses
             out["tile_queries"], out["queue_ids"], out["segments"] = int(g[3]), int(g[4]), int(g[5])
         return out

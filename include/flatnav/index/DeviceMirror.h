@@ -91,7 +91,8 @@ class DeviceMirror {
   DirtyRows _dirty;       // link rows of synced nodes that changed since
   int64_t _filter_scan_max = 0;  // setFilterRouting: re-applied whenever the mirror is created anew
   bool _filter_scan_on_overflow = false;
-  bool _exhaustive_matrix = false, _exhaustive_matrix_float = false, _exhaustive_matrix_float32 = false;  // setExhaustiveMatrix: likewise
+  bool _exhaustive_matrix = false, _exhaustive_matrix_float = false, _exhaustive_matrix_float32 = false,
+       _exhaustive_matrix_grouped = false;  // setExhaustiveMatrix: likewise
   // several GPUs: the mirror on _ordinal is the primary; replicas of it live on the other devices of _devices (filled by peer
   // copies, refreshed whenever the primary changes); batches are sharded over all of them
   int _ordinal = 0;
@@ -290,11 +291,13 @@ class DeviceMirror {
     if (_handle) applyFilterRouting();
   }
   // The exhaustive search's matrix engines (options "scan_matrix" and, with `float_rows`, "scan_matrix_float", with
-  // `float32_rows`, "scan_matrix_float32"): now if there is a mirror, and on every mirror made later.
-  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false) {
+  // `float32_rows`, "scan_matrix_float32"; with `grouped`, "scan_matrix_grouped": the grouped exhaustive search takes the engines
+  // that are on): now if there is a mirror, and on every mirror made later.
+  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false) {
     _exhaustive_matrix = on;
     _exhaustive_matrix_float = on && float_rows;
     _exhaustive_matrix_float32 = on && float32_rows;
+    _exhaustive_matrix_grouped = on && grouped;
     if (_handle) applyExhaustiveMatrix();
   }
 
@@ -303,6 +306,7 @@ class DeviceMirror {
     throwOnDeviceError(fnv_set_option(_handle, "scan_matrix", _exhaustive_matrix ? 1 : 0));
     throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_float", _exhaustive_matrix_float ? 1 : 0));
     throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_float32", _exhaustive_matrix_float32 ? 1 : 0));
+    throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_grouped", _exhaustive_matrix_grouped ? 1 : 0));
   }
 };
 

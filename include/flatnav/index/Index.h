@@ -375,10 +375,12 @@ class Index {
   // before.  With `float_rows` (option "scan_matrix_float") float16 indexes take part too: the matrix cores discard the rows
   // that provably cannot reach a query's K-th distance and the rest is scored as the vector scan scores it -- again the same
   // bytes.  With `float32_rows` (option "scan_matrix_float32") float32 indexes do the same, their operands narrowed to bfloat16
-  // for the matrix cores only.  Applies to the device mirror now if there is one, and to every mirror made later.
-  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false) {
+  // for the matrix cores only.  With `grouped` (option "scan_matrix_grouped") searchBatchExhaustiveGrouped runs on whichever of these
+  // engines is on for the index's element type, its rows fed from each filter's node bitmap -- the same bytes once more.
+  // Applies to the device mirror now if there is one, and to every mirror made later.
+  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false) {
     std::lock_guard<std::mutex> g(_mirror.mutex());
-    _mirror.setExhaustiveMatrix(on, float_rows, float32_rows);
+    _mirror.setExhaustiveMatrix(on, float_rows, float32_rows, grouped);
   }
   // The C-ABI handle of the device mirror (valid until the next mutation); for callers that drive
   // fnv_search_batch_device on their own buffers / streams.

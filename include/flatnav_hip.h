@@ -264,6 +264,10 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *                     "scan_matrix_float" does on float16 ones, on operands narrowed to bfloat16 in registers; every other
  *                     call (float16 and 1-byte indexes included, which the two other options govern) runs as before.
  *                     Same bytes.  Read per launch; keeps what fnv_tune measured.
+ *   "scan_matrix_grouped"  exhaustive search: 1 = fnv_search_batch_exhaustive_grouped[_device] runs on the matrix engine of the
+ *                     index's element type as well, PROVIDED that engine's own option above is on too (see
+ *                     fnv_search_batch_exhaustive, "Grouped calls"; default 0 = off: a grouped call keeps the vector scan
+ *                     whatever the three options say).  Same bytes.  Read per launch; keeps what fnv_tune measured.
  *   "filter_scan_max"  filter routing (see "Filter routing" below; default 0 = off): in fnv_search_batch_filtered[_grouped][_device] a
  *                     query whose filter allows at most this many live nodes is answered by the exhaustive scan instead of
  *                     the graph search.  Keeps what fnv_tune / the adaptive choice measured, as the next one does.
@@ -382,8 +386,8 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     padding, out_count, out_ndist, the (distance, node id) order -- for every row layout, segmentation, K and nq: a 1-byte
  *     distance is a function of an exact int32 sum, which no order of addition changes (uint8 rows go through the signed
  *     instruction as x - 128, with exact integer corrections).  The option never makes a valid call invalid; the vector scan
- *     answers where the engine does not apply: float32 and float16 indexes (their sums are order-dependent), the _grouped calls,
- *     the scan stage of a routed filtered graph search, and shapes whose 32 queries with their K-entry lists exceed a block's
+ *     answers where the engine does not apply: float32 and float16 indexes (their sums are order-dependent), the _grouped calls
+ *     without "scan_matrix_grouped", the scan stage of a routed filtered graph search, and shapes whose 32 queries with their K-entry lists exceed a block's
  *     LDS (K x row length too large).  fnv_last_launch_geometry then reports {grid_blocks, 64, lds_bytes, queries per tile, 0,
  *     row segments, kernel = 4, 0}.
  *   Float16 matrix engine (option "scan_matrix_float" = 1): on a float16 index the scan of these two calls is a FILTER on the
@@ -394,7 +398,7 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     the vector scan's operations in the vector scan's lane order, and only that distance is compared, inserted and reported.
  *     So every reported distance has the vector scan's bits whatever the margin, and a sound margin makes the selection the
  *     same as well: results, distance bits, padding, out_count and out_ndist (the candidate count) are those of the option off.
- *     The option never makes a valid call invalid; float32 and 1-byte indexes, the _grouped calls, routed scans and shapes
+ *     The option never makes a valid call invalid; float32 and 1-byte indexes, the _grouped calls without "scan_matrix_grouped", routed scans and shapes
  *     beyond a block's LDS keep their engine.  fnv_last_launch_geometry reports kernel = 5 in kernel 4's layout;
  *     fnv_last_replayed_queries how many pairs the filter let through.
  *   Float32 matrix engine (option "scan_matrix_float32" = 1): the same on a float32 index.  Rows and queries are narrowed to
@@ -405,6 +409,14 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     is scanned from its float32 table.  Same bytes as with the option off; not taken for the same calls as the float16
  *     engine, and for every other element type.  fnv_last_launch_geometry reports kernel = 6 in kernel 4's layout;
  *     fnv_last_replayed_queries the pairs as for kernel 5.
+ *   Grouped calls (option "scan_matrix_grouped" = 1 AND the element type's own option): fnv_search_batch_exhaustive_grouped[_device]
+ *     runs the same engine, one wavefront per (tile of queries that share a filter row, row segment).  The rows of a tile are the
+ *     bits of its filter row, turned into node ids in an LDS queue and scored 32 at a time, the next 32 rows already requested
+ *     from memory; scoring, margins and rescoring are the engine's own, so the bytes are those of the grouped vector scan, which
+ *     are those of the single-filter call per query.  Where 32 queries, their lists and the queue exceed a block's LDS the call
+ *     keeps the vector scan; the scan stage of a routed filtered graph search keeps it under every option.
+ *     fnv_last_launch_geometry reports {grid_blocks, 64, lds_bytes, queries per tile, entries of the id queue, row segments,
+ *     kernel = 4, 5 or 6, 0}; fnv_last_replayed_queries the pairs after kernels 5 and 6.
  * fnv_search_batch_exhaustive: host buffers (allowed_bits included); thread safety and lanes as fnv_search_batch.
  * fnv_search_batch_exhaustive_device: every buffer, allowed_bits included, in the index's device memory, enqueued on `hip_stream`
  *   without synchronising; one launch in flight per handle, as fnv_search_batch_device.

@@ -17,7 +17,12 @@ each engine's median, min and max over the rounds, the ratio of the medians, whe
 median by more than the vector engine's own max - min, the matrix engine's launch shape, its achieved integer op rate
 (2 * nq * candidates * padded dim) against the 5033 TOP/s int8 matrix peak (256 CUs x 4 SIMDs x 1024 MAC per cycle at 2.4 GHz)
 and the row bytes it moves (ceil(nq / tile) * candidates * row_bytes).  Before timing, both engines' outputs are compared byte
-for byte at every fraction."""
+for byte at every fraction.
+
+With --grouped N_FILTERS[,N_FILTERS...] the call is search_exhaustive_grouped instead ("scan_matrix_grouped" = 1 on top of the
+engine's option against the grouped vector scan, csrc/scan_matrix_feed.hpp): for every filter count and every share of
+--allowed SHARE[,SHARE...] a table of that many random filters, each allowing that share of the labels, the queries spread evenly
+over the filters (query q uses filter q % N_FILTERS).  The line's candidates are then the mean per query, and --fractions is not read."""
 import argparse
 import ctypes
 import json
@@ -45,6 +50,8 @@ ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--json", default="")
 ap.add_argument("--dtype", default="uint8", choices=["uint8", "float16", "float32"])
 ap.add_argument("--dim", type=int, default=128)
+ap.add_argument("--grouped", default="", help="filter counts of grouped calls, comma separated")
+ap.add_argument("--allowed", default="0.5", help="grouped calls: the share of the labels a filter allows, comma separated")
 args = ap.parse_args()
 
 HALVES = args.dtype != "uint8"  # a float engine: Gaussian rows, a prefilter with rescoring
@@ -69,8 +76,13 @@ stream = torch.cuda.current_stream()
 rng = np.random.default_rng(1)
 
 
-def launch(engine, bits, n_bits):
+def launch(engine, bits, n_bits, qf=None):
     d, l, c, nd = out[engine]
+    if qf is not None:  # a grouped call: `bits` is the filter table [filters][ceil(n_bits / 8)]
+        scan.set_option("scan_matrix_grouped", engine)
+        scan.search_device_exhaustive_grouped(tq.data_ptr(), NQ, K, bits.data_ptr(), bits.shape[0], bits.shape[1], n_bits, qf.data_ptr(),
+                                              d.data_ptr(), l.data_ptr(), c.data_ptr(), nd.data_ptr(), stream=stream.cuda_stream)
+        return
     scan.set_option(OPTION, engine)
     scan.search_device_exhaustive(tq.data_ptr(), NQ, K, d.data_ptr(), l.data_ptr(), c.data_ptr(), nd.data_ptr(),
                                   bits_ptr=bits.data_ptr() if n_bits else 0, n_bits=n_bits, use_filter=n_bits > 0,
@@ -87,41 +99,67 @@ def once(fn, steps):
     return a.elapsed_time(b) / steps
 
 
+def filter_table(n_filters, share):
+    """(table uint8 [n_filters][ceil(N / 8)] on the device, labels allowed per filter): random filters, made and packed on the device."""
+    torch.manual_seed(n_filters)
+    weights = (2 ** torch.arange(8, device=dev_t)).to(torch.int32)
+    table = torch.empty((n_filters, (N + 7) // 8), dtype=torch.uint8, device=dev_t)
+    counts = torch.empty(n_filters, dtype=torch.int64, device=dev_t)
+    for r in range(n_filters):
+        mask = torch.zeros(table.shape[1] * 8, dtype=torch.int32, device=dev_t)
+        mask[:N] = torch.rand(N, device=dev_t) < share
+        counts[r] = mask.sum()
+        table[r] = (mask.view(-1, 8) * weights).sum(1).to(torch.uint8)
+    return table, counts
+
+
+GROUPED = [int(x) for x in args.grouped.split(",") if x]
+CASES = [(f, g) for g in GROUPED for f in [float(x) for x in args.allowed.split(",")]] if GROUPED else [(float(x), 0) for x in args.fractions.split(",")]
+scan.set_option(OPTION, 1 if GROUPED else 0)  # (grouped calls: the engine's own option stays on, "scan_matrix_grouped" alternates)
 lines = []
-for f in [float(x) for x in args.fractions.split(",")]:
-    rows = np.arange(N) if f >= 1 else np.sort(rng.choice(N, max(1, int(round(f * N))), replace=False))
-    b, n_bits = hip.pack_allowed(rows) if f < 1 else (np.zeros(1, np.uint8), 0)
-    bits = torch.from_numpy(b).to(dev_t)
+for f, n_filters in CASES:
+    qf = None
+    if n_filters:
+        bits, counts = filter_table(n_filters, f)
+        n_bits, qf = N, (torch.arange(NQ, device=dev_t) % n_filters).to(torch.int32)
+        per_query = counts[qf.long()]
+        rows = range(int(round(per_query.double().mean().item())))  # (its length: the mean candidates of a query)
+    else:
+        rows = np.arange(N) if f >= 1 else np.sort(rng.choice(N, max(1, int(round(f * N))), replace=False))
+        b, n_bits = hip.pack_allowed(rows) if f < 1 else (np.zeros(1, np.uint8), 0)
+        bits = torch.from_numpy(b).to(dev_t)
+        per_query = torch.full((NQ,), len(rows), dtype=torch.int64, device=dev_t)
     geom = {}
     for e in (0, 1):  # warm-up, the launch shapes, and the same bytes from both engines
-        once(lambda: launch(e, bits, n_bits), 1)
+        once(lambda: launch(e, bits, n_bits, qf), 1)
         scan.status()
         geom[e] = scan.launch_geometry()
     rescored = scan.scan_rescored() if HALVES else {"scored": 0, "rescored": 0}
-    assert geom[0]["kernel_mode"] == 3 and geom[1]["kernel_mode"] == MODE, geom
-    assert not HALVES or rescored["scored"] == NQ * len(rows), rescored
+    assert geom[0]["kernel_mode"] == 3 and geom[1]["kernel_mode"] == MODE and ("queue_ids" in geom[1]) == bool(n_filters), geom
+    assert not HALVES or rescored["scored"] == int(per_query.sum().item()), rescored
     for x, y in zip(out[0], out[1]):
         assert torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y), f
-    assert int((out[1][3] != len(rows)).sum().item()) == 0
+    assert torch.equal(out[1][3], per_query)
     ms = {0: [], 1: []}
     for _ in range(args.rounds):
         for e in (0, 1):
-            ms[e].append(once(lambda: launch(e, bits, n_bits), args.steps))
+            ms[e].append(once(lambda: launch(e, bits, n_bits, qf), args.steps))
     med = {e: statistics.median(ms[e]) for e in (0, 1)}
     spread = max(ms[0]) - min(ms[0])
     tile = geom[1]["tile_queries"]
     ops = 2.0 * NQ * len(rows) * DIM
-    line = dict(fraction=f, candidates=len(rows), vector_ms=ms[0], matrix_ms=ms[1], vector_median=med[0], matrix_median=med[1],
+    line = dict(fraction=f, filters=n_filters, candidates=len(rows), vector_ms=ms[0], matrix_ms=ms[1], vector_median=med[0], matrix_median=med[1],
                 ratio=med[0] / med[1], vector_spread=spread, beats_by_more_than_spread=bool(med[0] - med[1] > spread),
                 vector_geometry=geom[0], matrix_geometry=geom[1], matrix_tops=ops / (med[1] * 1e-3) / 1e12,
                 matrix_of_peak=ops / (med[1] * 1e-3) / 1e12 / PEAK_TOPS, matrix_row_bytes=math.ceil(NQ / tile) * len(rows) * ROW_BYTES,
                 rescored_share=rescored["rescored"] / max(1, rescored["scored"]), dtype=args.dtype, dim=DIM)
     lines.append(line)
-    print("f=%-6g cand %8d | vector %9.3f ms [%9.3f .. %9.3f] | matrix %9.3f ms [%9.3f .. %9.3f] | %6.2fx  beats spread: %s | "
+    print("filters %-5d f=%-6g cand %8d | vector %9.3f ms [%9.3f .. %9.3f] | matrix %9.3f ms [%9.3f .. %9.3f] | %6.2fx  beats spread: %s | "
           "matrix grid %d lds %d tile %d segments %d | %.1f TOP/s (%.4f of peak), row bytes %.3e | rescored %.4f of the pairs"
-          % (f, len(rows), med[0], min(ms[0]), max(ms[0]), med[1], min(ms[1]), max(ms[1]), line["ratio"], line["beats_by_more_than_spread"],
+          % (n_filters, f, len(rows), med[0], min(ms[0]), max(ms[0]), med[1], min(ms[1]), max(ms[1]), line["ratio"], line["beats_by_more_than_spread"],
              geom[1]["grid_blocks"], geom[1]["lds_bytes"], tile, geom[1]["segments"], line["matrix_tops"], line["matrix_of_peak"],
              line["matrix_row_bytes"], line["rescored_share"]), flush=True)
 scan.set_option(OPTION, 0)
+scan.set_option("scan_matrix_grouped", 0)
 if args.json:
     json.dump(lines, open(args.json, "w"), indent=1)
