@@ -55,16 +55,22 @@ constexpr int METRIC = FNV_INST_METRIC;
 void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
   t.flat_m = exhaustive_scan_matrix_kernel<T, METRIC>;
   t.flat_mg = exhaustive_scan_matrix_grouped_kernel<T, METRIC>;
+  t.flat_mr = exhaustive_scan_matrix_kernel<T, METRIC, true>;  // (the RANGE forms: range search)
+  t.flat_mgr = exhaustive_scan_matrix_grouped_kernel<T, METRIC, true>;
 }
 #elif FNV_INST_FAMILY == 16  // ... and its float16 form
 void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
   t.flat_mf = exhaustive_scan_matrix_f16_kernel<METRIC>;
   t.flat_mg = exhaustive_scan_matrix_f16_grouped_kernel<METRIC>;
+  t.flat_mfr = exhaustive_scan_matrix_f16_kernel<METRIC, true>;
+  t.flat_mgr = exhaustive_scan_matrix_f16_grouped_kernel<METRIC, true>;
 }
 #elif FNV_INST_FAMILY == 17  // ... and its float32 form
 void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
   t.flat_mf32 = exhaustive_scan_matrix_f32_kernel<METRIC>;
   t.flat_mg = exhaustive_scan_matrix_f32_grouped_kernel<METRIC>;
+  t.flat_mf32r = exhaustive_scan_matrix_f32_kernel<METRIC, true>;
+  t.flat_mgr = exhaustive_scan_matrix_f32_grouped_kernel<METRIC, true>;
 }
 #else
 template <bool FULL>
@@ -78,8 +84,10 @@ static void fill_rows(KernelTable& t) {
   FNV_ROW(t.exact_f, beam_search_filtered_kernel)
 #elif FNV_INST_FAMILY == 13
   FNV_ROW(t.flat, exhaustive_scan_kernel)
+  FNV_ROW(t.flat_r, exhaustive_scan_kernel, , true)  // (the RANGE form: range search)
 #elif FNV_INST_FAMILY == 14
   FNV_ROW(t.flat_g, exhaustive_scan_grouped_kernel)
+  FNV_ROW(t.flat_gr, exhaustive_scan_grouped_kernel, , true)
 #elif FNV_INST_FAMILY >= 4 && FNV_INST_FAMILY <= 11
   constexpr int kFormOfFamily[4] = {3, 1, 0, 2};  // families 4-7 (and 8-11): MB_R / one / no (LDS) / two register chunks
   constexpr int form = kFormOfFamily[(FNV_INST_FAMILY - 4) % 4];

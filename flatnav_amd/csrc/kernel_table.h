@@ -29,6 +29,13 @@ struct KernelTable {
   scan_mf_fn flat_mf;                  // exhaustive_scan_matrix_f16_kernel (scan_matrix_f16.hpp; float16 only, else null): likewise
   scan_mf_fn flat_mf32;                // exhaustive_scan_matrix_f32_kernel (scan_matrix_f32.hpp; float32 only, else null): likewise
   scan_grouped_fn flat_mg;             // the grouped form of whichever of the three the element type has (families 15-17 fill it with their own)
+  // The RANGE forms of the eight above (range search, option "scan_radius": scan.hpp), filled by the same families' units.  A
+  // launch without a radius never looks at them.
+  scan_fn flat_r[kNumCfgs][2];
+  scan_grouped_fn flat_gr[kNumCfgs][2];
+  scan_fn flat_mr;
+  scan_mf_fn flat_mfr, flat_mf32r;
+  scan_grouped_fn flat_mgr;
 };
 
 // X(element type, type tag, metric ordinal, metric tag)

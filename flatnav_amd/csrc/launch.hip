@@ -123,7 +123,24 @@ const KernelTable& kernel_table(int, int, bool = false) {
         k.connect[c][f] = FNV_DEV_KERNEL(wire_connect_kernel);
         k.flat[c][f] = FNV_DEV_KERNEL(exhaustive_scan_kernel);
         k.flat_g[c][f] = FNV_DEV_KERNEL(exhaustive_scan_grouped_kernel);
+        k.flat_r[c][f] = FNV_DEV_KERNEL(exhaustive_scan_kernel, , true);
+        k.flat_gr[c][f] = FNV_DEV_KERNEL(exhaustive_scan_grouped_kernel, , true);
       }
+    k.flat_mr = nullptr;  // the matrix engines' RANGE forms, as their others below
+    k.flat_mfr = k.flat_mf32r = nullptr;
+    k.flat_mgr = nullptr;
+    if constexpr (sizeof(FNV_DEV_T) == 1) {
+      k.flat_mr = exhaustive_scan_matrix_kernel<FNV_DEV_T, FNV_DEV_METRIC, true>;
+      k.flat_mgr = exhaustive_scan_matrix_grouped_kernel<FNV_DEV_T, FNV_DEV_METRIC, true>;
+    }
+    if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) {
+      k.flat_mfr = exhaustive_scan_matrix_f16_kernel<FNV_DEV_METRIC, true>;
+      k.flat_mgr = exhaustive_scan_matrix_f16_grouped_kernel<FNV_DEV_METRIC, true>;
+    }
+    if constexpr (std::is_same<FNV_DEV_T, float>::value) {
+      k.flat_mf32r = exhaustive_scan_matrix_f32_kernel<FNV_DEV_METRIC, true>;
+      k.flat_mgr = exhaustive_scan_matrix_f32_grouped_kernel<FNV_DEV_METRIC, true>;
+    }
     k.flat_m = nullptr;
     if constexpr (sizeof(FNV_DEV_T) == 1) k.flat_m = exhaustive_scan_matrix_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
     k.flat_mf = nullptr;
@@ -541,14 +558,17 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
 
   // -- shape: the vector scan's, or -- a call a matrix engine takes ("scan_matrix", "scan_matrix_float", "scan_matrix_float32"; a
   // grouped call: with "scan_matrix_grouped" as well) -- that engine's
-  const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
+  // A range search ("scan_radius" set; scan_select.hpp): the same steps with the kernels' RANGE forms, a counter per query in LDS
+  // and one word per (query, segment) behind the partial lists; the merge then reports the in-range total in out_ndist.
+  const bool range = scan_range_on(ix);
+  const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0, range);
   if (vector_shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
-  const ScanMatrixShape matrix = scan_matrix_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0);
+  const ScanMatrixShape matrix = scan_matrix_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0, range);
   const ScanShape shape = matrix.on ? static_cast<const ScanShape&>(matrix) : vector_shape;
   const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
   // -- workspace
-  rc = ix->ws.scan.grow(scan_partial_bytes(nq, shape, K));
+  rc = ix->ws.scan.grow(scan_partial_bytes(nq, shape, K) + scan_count_bytes(nq, shape, range));
   if (!rc && grouped) rc = grow_filter_rows(ix, *filter);
   if (!rc && grouped) rc = ix->ws.group.grow(ga.bytes);
   if (!rc && listed) rc = ix->d_nodebits.grow((size_t)node_words(ix) * 4);
@@ -560,6 +580,10 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   GroupedScanParams gp;
   memset(&gp, 0, sizeof(gp));
   gp.s = scan_params(ix, g, d_queries, nq, K, out, opt, shape, live);
+  if (range) {
+    gp.s.range_counts = reinterpret_cast<uint32_t*>(gp.s.partial + (uint64_t)nq * shape.segments * (uint64_t)K);
+    gp.s.range_bound = scan_range_bound((uint32_t)ix->scan_radius);
+  }
   // (the status word: this path never sets it; the scan's kernels zero no block, so the next search launch memsets its own)
   uint32_t* const block = ix->last_block;
   HIP_TRY(hipMemsetAsync(block, 0, 16 * sizeof(uint32_t), stream));
@@ -573,7 +597,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   HIP_TRY(hipEventRecord(ix->ev0, stream));
   if (grouped) {
     const KernelTable& table = kernel_table(ix->dtype, ix->metric);
-    const scan_grouped_fn kern = matrix.on ? table.flat_mg : table.flat_g[g.cfg][g.full];
+    const scan_grouped_fn kern = range ? (matrix.on ? table.flat_mgr : table.flat_gr[g.cfg][g.full]) : matrix.on ? table.flat_mg : table.flat_g[g.cfg][g.full];
     if (!kern) return fail(FNV_ERR_RUNTIME, "the grouped matrix scan kernel of this element type is missing from the build");
     gp.group_lanes = matrix.group_lanes;  // (the float forms: the rescoring groups, the two counters the memset above cleared)
     gp.counters = reinterpret_cast<unsigned long long*>(block + fnv_index_s::kScanCounterWord);
@@ -582,7 +606,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   } else {
     const KernelTable& table = kernel_table(ix->dtype, ix->metric);
     if (matrix.float_rows || matrix.float32_rows) {  // the float forms: the plain block, the rescoring groups, the two counters the memset above cleared
-      const scan_mf_fn kern = matrix.float32_rows ? table.flat_mf32 : table.flat_mf;
+      const scan_mf_fn kern = range ? (matrix.float32_rows ? table.flat_mf32r : table.flat_mfr) : matrix.float32_rows ? table.flat_mf32 : table.flat_mf;
       if (!kern) return fail(FNV_ERR_RUNTIME, "the float matrix scan kernel of this element type is missing from the build");
       ScanMatrixFloatParams fp;
       static_cast<ScanParams&>(fp) = gp.s;
@@ -591,7 +615,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
       HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
       hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, fp);
     } else {
-      const scan_fn kern = matrix.on ? table.flat_m : table.flat[g.cfg][g.full];
+      const scan_fn kern = range ? (matrix.on ? table.flat_mr : table.flat_r[g.cfg][g.full]) : matrix.on ? table.flat_m : table.flat[g.cfg][g.full];
       if (!kern) return fail(FNV_ERR_RUNTIME, "the matrix scan kernel of this element type is missing from the build");
       HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
       hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, gp.s);
@@ -604,9 +628,10 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
 
   // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
   // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments.  Modes 5 and 6: its float16 and
-  // float32 forms, likewise; a grouped call one of them took: the entries of its id queue where the grouped vector scan has its own)
+  // float32 forms, likewise; a grouped call one of them took: the entries of its id queue where the grouped vector scan has its own.
+  // The last field, 0 in every other launch: 1 = a range search, the kernels' RANGE forms ran)
   record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
-                !grouped ? 0 : matrix.on ? MATRIX_QUEUE_IDS : SCAN_QUEUE_IDS, grouped || matrix.on ? shape.segments : 0, matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, 0);
+                !grouped ? 0 : matrix.on ? MATRIX_QUEUE_IDS : SCAN_QUEUE_IDS, grouped || matrix.on ? shape.segments : 0, matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, range ? 1 : 0);
   return FNV_OK;
 }
 

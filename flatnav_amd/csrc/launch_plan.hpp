@@ -52,6 +52,7 @@ struct IndexOptions {
   int64_t scan_matrix_float = 0;  // ... on float16 indexes: the matrix prefilter with exact rescoring (scan_matrix_f16.hpp)
   int64_t scan_matrix_float32 = 0;  // ... on float32 indexes: the same on operands narrowed to bfloat16 (scan_matrix_f32.hpp)
   int64_t scan_matrix_grouped = 0;  // ... and, with the element type's own option, the grouped exhaustive call (scan_matrix_feed.hpp)
+  int64_t scan_radius = SCAN_RADIUS_OFF;  // exhaustive search: negative = off, else the float32 bits of a range search's radius (scan_select.hpp)
   // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
   // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
   int64_t filter_scan_max = 0, filter_scan_on_overflow = 0;
@@ -631,9 +632,13 @@ inline uint32_t scan_segments(const PlanInputs* ix, uint32_t tiles, uint64_t nq,
 }
 // `filter_rows` != 0: a grouped launch over that many filter rows -- the id queue comes out of the block's LDS budget, and
 // `tiles` is the bound on the data-dependent tile count that the launch covers (scan_select.hpp, group_tile_bound).
-inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows = 0) {
+// `range`: a range search (scan_range_on below; never the scan stage of a routed graph search, which ignores the radius): every
+// query of the tile keeps one more word of LDS, its in-range counter, behind everything else (scan.hpp, "Range search").
+inline bool scan_range_on(const PlanInputs* ix) { return ix->scan_radius >= 0; }
+inline ScanShape scan_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live, uint64_t filter_rows = 0,
+                            bool range = false) {
   ScanShape s;
-  const uint32_t per_query = g.q_chunks * 16u + (uint32_t)K * 8u;
+  const uint32_t per_query = g.q_chunks * 16u + (uint32_t)K * 8u + (range ? 4u : 0u);
   const uint32_t queue = filter_rows ? SCAN_QUEUE_IDS * 4u : 0u;
   s.tile = std::max(1u, std::min(kScanMaxTile, (kScanLdsBudget - queue) / per_query));
   s.tile = (uint32_t)std::min<uint64_t>(s.tile, nq);
@@ -675,8 +680,10 @@ struct ScanMatrixShape : ScanShape {
   bool float32_rows = false;  // the float32 form
   uint32_t group_lanes = 0;   // the float forms' rescoring groups: kCfgs[cfg].G
 };
+// `range`: as scan_shape's -- one more word per query; where the counters push 32 queries beyond a block's LDS the call keeps the
+// vector scan like any other shape that does not fit.
 inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live,
-                                         uint64_t filter_rows = 0) {
+                                         uint64_t filter_rows = 0, bool range = false) {
   ScanMatrixShape s;
   s.tile = s.tiles = s.segments = s.lds = 0;
   const bool bytes = ix->scan_matrix != 0 && (ix->dtype == FNV_DTYPE_UINT8 || ix->dtype == FNV_DTYPE_INT8);
@@ -685,7 +692,7 @@ inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry
   if ((!bytes && !halves && !floats) || nq == 0 || (filter_rows != 0 && ix->scan_matrix_grouped == 0)) return s;
   const uint32_t chunks_per_step = floats ? 4u : 2u;
   const uint32_t steps = (g.nchunks + g.tail_chunks + chunks_per_step - 1u) / chunks_per_step;
-  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + (bytes ? 4u : 8u);
+  const uint32_t per_query = steps * 32u + (uint32_t)K * 8u + (bytes ? 4u : 8u) + (range ? 4u : 0u);
   const uint32_t queue = filter_rows ? MATRIX_QUEUE_IDS * 4u : 0u;
   if (kScanMatrixN * per_query + queue > kScanMaxLds) return s;
   uint32_t subtiles = std::max(1u, std::min(kScanMatrixMaxTile, (kScanMatrixLdsBudget - queue) / per_query) / kScanMatrixN);
@@ -706,6 +713,9 @@ inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry
 // The partial lists of a launch: one sorted list of K keys per (query, segment); the merge's LDS: three such lists.
 inline size_t scan_partial_bytes(uint64_t nq, const ScanShape& s, int K) { return (size_t)nq * s.segments * (size_t)K * 8; }
 inline uint32_t scan_merge_lds(uint32_t K) { return 3u * K * 8u; }
+// A range search's in-range counts: one word per (query, segment), in the same buffer behind the partial lists (whose bytes are
+// a multiple of 8).  Without a radius: nothing.
+inline size_t scan_count_bytes(uint64_t nq, const ScanShape& s, bool range) { return range ? (size_t)nq * s.segments * 4 : 0; }
 
 // The grouping arrays of a grouped scan (scan.hpp's group_* kernels), as uint32 offsets into one buffer.
 // `routed` (the scan stage of a routed filtered graph search): nq route words and the overflow flag behind them as well.

@@ -345,6 +345,7 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
   void setExhaustiveMatrix(bool on, bool float_rows, bool float32_rows, bool grouped) {
     _index->setExhaustiveMatrix(on, float_rows, float32_rows, grouped);
   }
+  void setExhaustiveRadius(std::optional<float> radius) { _index->setExhaustiveRadius(radius); }
   uintptr_t deviceHandle() { return reinterpret_cast<uintptr_t>(_index->deviceHandle()); }
   uint64_t currentNumNodes() { return _index->currentNumNodes(); }
   // zero-copy view of the AoS node store (for tests: graph-equality checks against the oracle)
@@ -422,6 +423,11 @@ void bindIndex(py::module_& m, const char* name) {
            "With float32_rows=True float32 indexes do the same (their values are narrowed to bfloat16 for the matrix cores only).  "
            "With grouped=True search_exhaustive_grouped runs on whichever of these engines is on for the index's element type.  "
            "Every other index type, and search_exhaustive_grouped without it, run as before.")
+      .def("set_exhaustive_radius", &T::setExhaustiveRadius, py::arg("radius") = py::none(),
+           "Range search: with a radius, search_exhaustive and search_exhaustive_grouped return each query's K nearest among the "
+           "candidates whose distance is at most `radius` (+inf admits every number, a NaN distance is never within it), padded "
+           "as before; the device's per-query distance counter then holds how many candidates were within the radius, which may "
+           "exceed K.  None turns it off; a NaN radius raises ValueError.  Every other search ignores it.")
       .def("device_handle", &T::deviceHandle, "fnv_index_t of the device mirror as an integer.")
       .def("_raw_blob", &T::rawBlob)
       .def_property_readonly("_node_size_bytes", &T::nodeSizeBytes)

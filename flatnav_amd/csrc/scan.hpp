@@ -17,6 +17,9 @@
 // and flushing around a walk of the tile's filter row; its batches are scored by scan_score_batch, a copy of step 2's loop.
 // A routed filtered graph search (scan_select.hpp, "filter routing") runs that grouped form as its second stage, on the queries
 // whose route word is set: route_queries_kernel, group_rows_routed_kernel and exhaustive_merge_routed_kernel below.
+// Range search (option "scan_radius"): the two scan kernels and scan_score_batch have a RANGE form (a template parameter: the
+// forms without it are the code they were) that drops rows against min(K-th key, the radius's bound) and counts the in-range
+// ones; the merge adds the counts up -- "Range search" below.  The routed stage never runs it.
 #pragma once
 #include "distance.hpp"
 #include "heaps.hpp"
@@ -62,9 +65,23 @@ __device__ __forceinline__ void scan_flush_tile(const ScanParams& p, const uint6
   }
 }
 
+// Range search (scan_select.hpp, "scan_radius"): the kernels' RANGE forms keep, next to every list, how many of the query's
+// candidates in this segment were in range -- whether or not they also entered the list.  The counters are [tile] words of
+// LDS behind everything else the block keeps there; one lane adds to them, so no atomic is needed.  They start at zero (before
+// scan_stage_tile, whose barrier covers them) and go out beside the partial lists, one word per (query, segment): every
+// word of a launch is written, so the array is never cleared.  The merge adds a query's words up (scan_range_total).
+__device__ __forceinline__ void scan_clear_counts(uint32_t* counts, uint32_t nqb, int lane) {
+  for (uint32_t i = lane; i < nqb; i += WAVE) counts[i] = 0u;
+}
+template <typename F>
+__device__ __forceinline__ void scan_flush_counts(const ScanParams& p, const uint32_t* counts, uint32_t nqb, uint32_t seg, int lane, F query_of) {
+  wave_sync();
+  for (uint32_t qq = lane; qq < nqb; qq += WAVE) p.range_counts[(uint64_t)query_of(qq) * p.segments + seg] = counts[qq];
+}
+
 // One wavefront per (query tile, row segment): the tile's queries staged, the segment's candidates -- the live nodes, or the
 // compacted ids of the allowed ones -- scored VPW * PU at a time, by the kernel's own loop (see scan_score_batch below).
-template <typename T, int METRIC, int G, int CU, bool FULL>
+template <typename T, int METRIC, int G, int CU, bool FULL, bool RANGE = false>
 __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PU = passes<G, CU>();
@@ -83,6 +100,9 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
   const uint32_t q_chunks = p.q_chunks;
   const int nchunks = (int)p.nchunks;
   const auto query_of = [&](uint32_t qq) { return q0 + qq; };
+  [[maybe_unused]] uint32_t* const counts = reinterpret_cast<uint32_t*>(lists + (size_t)p.tile_queries * p.K);  // RANGE: [tile]
+  [[maybe_unused]] const uint64_t range_end = p.range_bound + 1u;  // RANGE: a key below it is in range
+  if constexpr (RANGE) scan_clear_counts(counts, nqb, lane);
   scan_stage_tile<T>(p, qlds, lists, nqb, lane, query_of);
 
   // this block's share of the candidates
@@ -149,11 +169,19 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
       }
       uint64_t* const list = lists + (size_t)qq * K;
       uint64_t kth = list[K - 1];  // one address for the wave: a broadcast read
+      [[maybe_unused]] uint32_t in_range = 0;  // RANGE: this query's in-range rows of the batch (wave-uniform)
 #pragma unroll
       for (int pu = 0; pu < PU; pu++) {
         const float d = D::finish(group_sum<G>(D::lane_sum(acc[pu], qacc)));
         const uint64_t key = scan_key(__float_as_uint(d), id[pu]);
-        unsigned long long pm = __ballot(g == 0 && val[pu] && scan_key_less(key, kth));
+        // RANGE: the one compare is against the radius's bound; only a batch with a row in range looks at the K-th key as well
+        unsigned long long pm = __ballot(g == 0 && val[pu] && scan_key_less(key, RANGE ? range_end : kth));
+        if constexpr (RANGE) {
+          if (pm) {
+            in_range += (uint32_t)__popcll(pm);
+            pm &= __ballot(scan_key_less(key, kth));
+          }
+        }
         while (pm) {  // rare: about K ln(n / K) rows per query ever get here
           const int i = __ffsll((long long)pm) - 1;
           pm &= pm - 1;
@@ -165,9 +193,13 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
           }
         }
       }
+      if constexpr (RANGE) {
+        if (in_range != 0u && lane == 0) counts[qq] += in_range;  // (one lane owns the counters: no atomic)
+      }
     }
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
+  if constexpr (RANGE) scan_flush_counts(p, counts, nqb, seg, lane, query_of);
 }
 
 // ---- grouped filters: one allowed set per query (fnv_search_batch_exhaustive_grouped) --------------------------------------
@@ -177,9 +209,9 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_kernel(const ScanParams 
 // (A copy, not a shared body: with the body shared, the plain scan's small launches -- a hundred queries on 1 % of the rows --
 // measured 0.7 % slower, profiles/exhaustive.md.  Only the GPU tests hold the two bodies to the same bits: ANY change to the
 // scoring of either must be made in both.)
-template <typename T, int METRIC, int G, int CU, bool FULL>
+template <typename T, int METRIC, int G, int CU, bool FULL, bool RANGE = false>
 __device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint4* qlds, uint64_t* lists, uint32_t nqb,
-                                                 const uint32_t* ids, uint32_t nvalid, int lane) {
+                                                 const uint32_t* ids, uint32_t nvalid, int lane, [[maybe_unused]] uint32_t* counts = nullptr) {
   constexpr int PU = passes<G, CU>();
   constexpr int VPW = WAVE / G;
   constexpr int SPAN = G * CU;
@@ -192,6 +224,7 @@ __device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint
   const int nchunks = (int)p.nchunks;
   const bool one_span = nchunks <= SPAN;
   const uint32_t tc = p.tail_chunks;
+  [[maybe_unused]] const uint64_t range_end = p.range_bound + 1u;
   uint32_t id[PU];
   bool val[PU];
   const uint8_t* rowp[PU];
@@ -246,11 +279,18 @@ __device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint
     }
     uint64_t* const list = lists + (size_t)qq * K;
     uint64_t kth = list[K - 1];
+    [[maybe_unused]] uint32_t in_range = 0;
 #pragma unroll
     for (int pu = 0; pu < PU; pu++) {
       const float d = D::finish(group_sum<G>(D::lane_sum(acc[pu], qacc)));
       const uint64_t key = scan_key(__float_as_uint(d), id[pu]);
-      unsigned long long pm = __ballot(g == 0 && val[pu] && scan_key_less(key, kth));
+      unsigned long long pm = __ballot(g == 0 && val[pu] && scan_key_less(key, RANGE ? range_end : kth));
+      if constexpr (RANGE) {
+        if (pm) {
+          in_range += (uint32_t)__popcll(pm);
+          pm &= __ballot(scan_key_less(key, kth));
+        }
+      }
       while (pm) {
         const int i = __ffsll((long long)pm) - 1;
         pm &= pm - 1;
@@ -262,6 +302,9 @@ __device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint
         }
       }
     }
+    if constexpr (RANGE) {
+      if (in_range != 0u && lane == 0) counts[qq] += in_range;
+    }
   }
 }
 
@@ -271,7 +314,7 @@ __device__ __forceinline__ void scan_score_batch(const ScanParams& p, const uint
 // the lanes) are appended, full batches are scored, what is left moves to the queue's front, until the step's words are used
 // up.  The last short batch is scored after the last word.  Which batch a node falls into never shows: the order is total.
 // LDS: the plain scan's [tile][q_chunks] queries and [tile][K] lists, then SCAN_QUEUE_IDS ids.
-template <typename T, int METRIC, int G, int CU, bool FULL>
+template <typename T, int METRIC, int G, int CU, bool FULL, bool RANGE = false>
 __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const GroupedScanParams gp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr uint32_t BATCH = (uint32_t)(passes<G, CU>() * (WAVE / G));
@@ -287,6 +330,8 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const Gro
   uint32_t* const queue = reinterpret_cast<uint32_t*>(lists + (size_t)p.tile_queries * p.K);
   const uint32_t* const perm = gp.perm + t.first;
   const auto query_of = [&](uint32_t qq) { return perm[qq]; };
+  [[maybe_unused]] uint32_t* const counts = queue + SCAN_QUEUE_IDS;  // RANGE: [tile], behind the queue
+  if constexpr (RANGE) scan_clear_counts(counts, nqb, lane);
   scan_stage_tile<T>(p, qlds, lists, nqb, lane, query_of);
   const uint32_t* const bits = gp.node_bits + (uint64_t)t.row * gp.row_words;
   const uint32_t wlo = (uint32_t)((uint64_t)gp.live_words * seg / p.segments);
@@ -316,7 +361,7 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const Gro
       wave_sync();
       uint32_t head = 0;
       for (; count - head >= BATCH; head += BATCH)
-        scan_score_batch<T, METRIC, G, CU, FULL>(p, qlds, lists, nqb, queue + head, BATCH, lane);
+        scan_score_batch<T, METRIC, G, CU, FULL, RANGE>(p, qlds, lists, nqb, queue + head, BATCH, lane, counts);
       if (head) {  // the leftovers (fewer than a batch) to the front
         const uint32_t rem = count - head;
         uint32_t keep = 0;
@@ -328,8 +373,9 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_grouped_kernel(const Gro
       }
     }
   }
-  if (count) scan_score_batch<T, METRIC, G, CU, FULL>(p, qlds, lists, nqb, queue, count, lane);
+  if (count) scan_score_batch<T, METRIC, G, CU, FULL, RANGE>(p, qlds, lists, nqb, queue, count, lane, counts);
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
+  if constexpr (RANGE) scan_flush_counts(p, counts, nqb, seg, lane, query_of);
 }
 
 #ifndef FNV_INST_FAMILY  // (the kernels below are not templates: launch.hip alone emits them, not kernel_inst.hip's units)
@@ -394,14 +440,27 @@ __device__ __forceinline__ void scan_merge_query(const ScanParams& p, unsigned c
     if (p.out_ndist) p.out_ndist[q] = ncand;
   }
 }
+// Range search: the block's query had this many candidates in range -- its segments' counters added up by the whole wave.
+// That, not the candidate count, is then what out_ndist reports and what out_count is cut from (it may exceed K).
+__device__ __forceinline__ uint64_t scan_range_total(const ScanParams& p) {
+  const uint32_t* const c = p.range_counts + (uint64_t)blockIdx.x * p.segments;
+  uint64_t sum = 0;
+  for (uint32_t s = threadIdx.x; s < p.segments; s += WAVE) sum += c[s];
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)sum, off, WAVE), hi = (uint32_t)__shfl_xor((int)(uint32_t)(sum >> 32), off, WAVE);
+    sum += ((uint64_t)hi << 32) | lo;
+  }
+  return sum;
+}
 static __global__ __launch_bounds__(WAVE) void exhaustive_merge_kernel(const ScanParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  scan_merge_query(p, smem, [&] { return p.cand_ids ? (uint64_t)*p.cand_count : p.n_live; });
+  scan_merge_query(p, smem, [&] { return p.range_counts ? scan_range_total(p) : p.cand_ids ? (uint64_t)*p.cand_count : p.n_live; });
 }
 // ... of a grouped launch: the candidates of a query are the nodes set in its filter row.
 static __global__ __launch_bounds__(WAVE) void exhaustive_merge_grouped_kernel(const GroupedScanParams gp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  scan_merge_query(gp.s, smem, [&] { return (uint64_t)gp.row_count[gp.query_row[blockIdx.x]]; });
+  scan_merge_query(gp.s, smem, [&] { return gp.s.range_counts ? scan_range_total(gp.s) : (uint64_t)gp.row_count[gp.query_row[blockIdx.x]]; });
 }
 // ... of a routed filtered graph search (scan_select.hpp, "filter routing"): one block per query of the call; only a query whose
 // route word is set has partial lists, and its n_hops = 0 tells its row from a graph search's.

@@ -51,7 +51,7 @@ constexpr int MS_N = 32;    // the MFMA's N: queries per sub-tile (and its M: ro
 constexpr int MS_SPAN = 4;  // MFMA steps (32 bytes of a row each) a lane keeps in registers: rows of up to 128 bytes whole
 
 // One kernel template for both kinds of call.  GROUPED: the parameter block is the grouped launch's, `gp` points at it.
-template <typename T, int METRIC, bool GROUPED>
+template <typename T, int METRIC, bool GROUPED, bool RANGE = false>
 __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_any_kernel(const std::conditional_t<GROUPED, GroupedScanParams, ScanParams> kp) {
   const ScanParams& p = matrix_scan_params(kp);
   [[maybe_unused]] const GroupedScanParams* const gp = matrix_grouped_params(kp);
@@ -78,6 +78,12 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_any_kernel(const 
     if constexpr (GROUPED) return gp->perm[gt.first + qq];
     else return q0 + qq;
   };
+  // RANGE (scan.hpp, "Range search"): the tile's in-range counters, behind everything else; the radius as the float the lanes
+  // compare with -- d <= radius is the key order's "in range" for the numbers an integer sum gives (never a NaN)
+  [[maybe_unused]] uint32_t* const counts =
+      reinterpret_cast<uint32_t*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u + 4u) + (GROUPED ? MATRIX_QUEUE_IDS * 4u : 0u));
+  [[maybe_unused]] const float radius = __uint_as_float(scan_key_dist_bits(p.range_bound));
+  if constexpr (RANGE) scan_clear_counts(counts, nqb, lane);
 
   // ---- the tile's queries in operand order (zero beyond dim, flipped over the P elements the rows cover), their terms, the lists
   for (uint32_t i = lane; i < nsub * (uint32_t)S * 64u; i += WAVE) {
@@ -209,12 +215,15 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_any_kernel(const 
         return kth == SCAN_PAD ? std::numeric_limits<float>::infinity() : __uint_as_float(scan_key_dist_bits(kth));
       };
       float kd = kth_dist();
+      if constexpr (RANGE) kd = min(kd, radius);  // a list entry is in range as well
+      [[maybe_unused]] uint32_t in_range = 0;  // RANGE: this lane's in-range pairs of the tile, all of one query
 #pragma unroll
       for (int v = 0; v < 16; v++) {
         uint32_t s = (uint32_t)acc[v];
         if (L2) s = (uint32_t)rv[v] + (uint32_t)qt - 2u * s;
         else if (FLIP) s += (uint32_t)rv[v] + (uint32_t)qt;
         const float d = D::finish((int)s);
+        if constexpr (RANGE) in_range += (d <= radius && qq < nqb && (uint32_t)(8 * (v / 4) + (v % 4) + 4 * half) < nrows) ? 1u : 0u;
         unsigned long long pm = __ballot(d <= kd);  // (ties pass: the key decides)
         while (pm) {
           const int i = __ffsll((long long)pm) - 1;
@@ -226,8 +235,14 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_any_kernel(const 
           uint64_t* const list = lists + (size_t)(t * MS_N + (uint32_t)(i & 31)) * K;
           if (scan_key_less(key, list[K - 1])) {
             scan_insert(list, K, key, lane);
-            if (col == (i & 31)) kd = kth_dist();
+            if (col == (i & 31)) kd = RANGE ? min(kth_dist(), radius) : kth_dist();
           }
+        }
+      }
+      if constexpr (RANGE) {  // the query's two lanes together; the lower one owns its counter
+        if (__ballot(in_range != 0u)) {
+          in_range += (uint32_t)__shfl_xor((int)in_range, 32, WAVE);
+          if (half == 0 && in_range != 0u) counts[qq] += in_range;
         }
       }
     }
@@ -269,11 +284,12 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_any_kernel(const 
     }
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
+  if constexpr (RANGE) scan_flush_counts(p, counts, nqb, seg, lane, query_of);
 }
 
-template <typename T, int METRIC>
-constexpr scan_fn exhaustive_scan_matrix_kernel = exhaustive_scan_matrix_any_kernel<T, METRIC, false>;
-template <typename T, int METRIC>
-constexpr scan_grouped_fn exhaustive_scan_matrix_grouped_kernel = exhaustive_scan_matrix_any_kernel<T, METRIC, true>;
+template <typename T, int METRIC, bool RANGE = false>
+constexpr scan_fn exhaustive_scan_matrix_kernel = exhaustive_scan_matrix_any_kernel<T, METRIC, false, RANGE>;
+template <typename T, int METRIC, bool RANGE = false>
+constexpr scan_grouped_fn exhaustive_scan_matrix_grouped_kernel = exhaustive_scan_matrix_any_kernel<T, METRIC, true, RANGE>;
 
 }  // namespace fnv_dev

@@ -60,9 +60,11 @@ __device__ __forceinline__ uint32_t mf_row(int v, int half) { return (uint32_t)(
 // The survivors of one (row tile, sub-tile) -- bit v of `mine`: this lane's query against row mf_row(v, lane / 32) -- scored
 // exactly and offered to their lists.  `qsub`: the sub-tile's queries in operand order, `sublists`: its lists, `id`: the row
 // tile's node ids (lane l: row l % 32).  Returns how many there were.
-template <int METRIC, int G>
+// RANGE (scan.hpp, "Range search"): a survivor whose exact key is in range is counted in `subcounts` (the sub-tile's counters; lane 0
+// owns them), whether or not it then enters its list; one out of range is neither.
+template <int METRIC, int G, bool RANGE = false>
 __device__ __forceinline__ uint32_t mf_rescore(const ScanParams& p, const uint4* qsub, uint64_t* sublists, uint32_t mine,
-                                               uint32_t id, int lane) {
+                                               uint32_t id, int lane, [[maybe_unused]] uint32_t* subcounts = nullptr) {
   typedef Dist<_Float16, METRIC> D;
   constexpr int VPW = WAVE / G;
   const uint32_t g = (uint32_t)(lane % G);
@@ -93,8 +95,16 @@ __device__ __forceinline__ uint32_t mf_rescore(const ScanParams& p, const uint4*
       for (int k = 0; k < cnt; k++) {  // (wave-uniform)
         const uint64_t key = scan_key((uint32_t)__builtin_amdgcn_readlane(__float_as_int(d), k * G),
                                       (uint32_t)__builtin_amdgcn_readlane((int)node, k * G));
-        uint64_t* const list = sublists + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)j, k * G) * K;
-        if (scan_key_less(key, list[K - 1])) scan_insert(list, K, key, lane);
+        const uint32_t jk = (uint32_t)__builtin_amdgcn_readlane((int)j, k * G);
+        uint64_t* const list = sublists + (size_t)jk * K;
+        if constexpr (RANGE) {
+          if (scan_in_range(key, p.range_bound)) {  // (wave-uniform)
+            if (lane == 0) subcounts[jk] += 1u;
+            if (scan_key_less(key, list[K - 1])) scan_insert(list, K, key, lane);
+          }
+        } else {
+          if (scan_key_less(key, list[K - 1])) scan_insert(list, K, key, lane);
+        }
         pm &= pm - 1;
       }
     }
@@ -103,7 +113,7 @@ __device__ __forceinline__ uint32_t mf_rescore(const ScanParams& p, const uint4*
 }
 
 // One kernel template for both kinds of call.  GROUPED: the parameter block is the grouped launch's, `gp` points at it.
-template <int METRIC, bool GROUPED>
+template <int METRIC, bool GROUPED, bool RANGE = false>
 __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_any_kernel(const std::conditional_t<GROUPED, GroupedScanParams, ScanMatrixFloatParams> kp) {
   const ScanParams& p = matrix_scan_params(kp);
   [[maybe_unused]] const GroupedScanParams* const gp = matrix_grouped_params(kp);
@@ -128,6 +138,12 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_any_kernel(co
     if constexpr (GROUPED) return gp->perm[gt.first + qq];
     else return q0 + qq;
   };
+
+  // RANGE (scan.hpp, "Range search"): the tile's in-range counters, behind everything else, and the radius the prefilter drops by
+  [[maybe_unused]] uint32_t* const counts =
+      reinterpret_cast<uint32_t*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u + 8u) + (GROUPED ? MATRIX_QUEUE_IDS * 4u : 0u));
+  [[maybe_unused]] const float radius = __uint_as_float(scan_key_dist_bits(p.range_bound));
+  if constexpr (RANGE) scan_clear_counts(counts, nqb, lane);
 
   // ---- the tile's queries in operand order (zero beyond dim and beyond the tile), their norms and margin terms, the lists
   for (uint32_t i = lane; i < nsub * (uint32_t)S * 64u; i += WAVE) {
@@ -249,6 +265,9 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_any_kernel(co
         const uint64_t kth = lists[(size_t)qq * K + (K - 1)];
         if (kth != SCAN_PAD) kd = __uint_as_float(scan_key_dist_bits(kth));
       }
+      // RANGE: a pair that may lie within the radius is rescored to be counted, even where it cannot enter the list -- so the
+      // radius, not the K-th distance, is what a pair is dropped by (scan_select.hpp, where the margin is derived)
+      if constexpr (RANGE) kd = radius;
       uint32_t mine = 0;  // bit v: the pair (this lane's query, row mf_row(v, half)) survives
 #pragma unroll
       for (int v = 0; v < 16; v++) {
@@ -262,10 +281,10 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_any_kernel(co
         uint64_t* const sublists = lists + (size_t)t * MF_N * K;
         uint32_t n = 0;
         switch (kp.group_lanes) {  // the row configurations of float16 rows (search_types.h, kCfgs)
-          case 8: n = mf_rescore<METRIC, 8>(p, qsub, sublists, mine, id, lane); break;
-          case 16: n = mf_rescore<METRIC, 16>(p, qsub, sublists, mine, id, lane); break;
-          case 32: n = mf_rescore<METRIC, 32>(p, qsub, sublists, mine, id, lane); break;
-          default: n = mf_rescore<METRIC, 64>(p, qsub, sublists, mine, id, lane); break;
+          case 8: n = mf_rescore<METRIC, 8, RANGE>(p, qsub, sublists, mine, id, lane, counts + t * MF_N); break;
+          case 16: n = mf_rescore<METRIC, 16, RANGE>(p, qsub, sublists, mine, id, lane, counts + t * MF_N); break;
+          case 32: n = mf_rescore<METRIC, 32, RANGE>(p, qsub, sublists, mine, id, lane, counts + t * MF_N); break;
+          default: n = mf_rescore<METRIC, 64, RANGE>(p, qsub, sublists, mine, id, lane, counts + t * MF_N); break;
         }
         rescored += n;
       }
@@ -312,11 +331,12 @@ __global__ __launch_bounds__(WAVE) void exhaustive_scan_matrix_f16_any_kernel(co
     atomicAdd(kp.counters + 1, rescored);
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
+  if constexpr (RANGE) scan_flush_counts(p, counts, nqb, seg, lane, query_of);
 }
 
-template <int METRIC>
-constexpr scan_mf_fn exhaustive_scan_matrix_f16_kernel = exhaustive_scan_matrix_f16_any_kernel<METRIC, false>;
-template <int METRIC>
-constexpr scan_grouped_fn exhaustive_scan_matrix_f16_grouped_kernel = exhaustive_scan_matrix_f16_any_kernel<METRIC, true>;
+template <int METRIC, bool RANGE = false>
+constexpr scan_mf_fn exhaustive_scan_matrix_f16_kernel = exhaustive_scan_matrix_f16_any_kernel<METRIC, false, RANGE>;
+template <int METRIC, bool RANGE = false>
+constexpr scan_grouped_fn exhaustive_scan_matrix_f16_grouped_kernel = exhaustive_scan_matrix_f16_any_kernel<METRIC, true, RANGE>;
 
 }  // namespace fnv_dev

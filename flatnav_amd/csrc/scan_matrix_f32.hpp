@@ -78,8 +78,11 @@ __device__ __forceinline__ uint32_t mf32_row(int v, int half) { return (uint32_t
 // The survivors of one (row tile, sub-tile) -- bit v of `mine`: this lane's query against row mf32_row(v, lane / 32) -- scored
 // exactly and offered to their lists.  `query_at(j)`: the float32 query of the sub-tile's column j in p.queries, `sublists`: its
 // lists, `id`: the row tile's node ids (lane l: row l % 32).  Returns how many there were.
-template <int METRIC, int G, typename F>
-__device__ __forceinline__ uint32_t mf32_rescore(const ScanParams& p, F query_at, uint64_t* sublists, uint32_t mine, uint32_t id, int lane) {
+// RANGE (scan.hpp, "Range search"): a survivor whose exact key is in range is counted in `subcounts` (the sub-tile's counters; lane 0
+// owns them), whether or not it then enters its list; one out of range is neither.
+template <int METRIC, int G, bool RANGE = false, typename F>
+__device__ __forceinline__ uint32_t mf32_rescore(const ScanParams& p, F query_at, uint64_t* sublists, uint32_t mine, uint32_t id, int lane,
+                                                 [[maybe_unused]] uint32_t* subcounts = nullptr) {
   typedef Dist<float, METRIC> D;
   constexpr int VPW = WAVE / G;
   const uint32_t g = (uint32_t)(lane % G);
@@ -114,8 +117,16 @@ __device__ __forceinline__ uint32_t mf32_rescore(const ScanParams& p, F query_at
       for (int k = 0; k < cnt; k++) {  // (wave-uniform)
         const uint64_t key = scan_key((uint32_t)__builtin_amdgcn_readlane(__float_as_int(d), k * G),
                                       (uint32_t)__builtin_amdgcn_readlane((int)node, k * G));
-        uint64_t* const list = sublists + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)j, k * G) * K;
-        if (scan_key_less(key, list[K - 1])) scan_insert(list, K, key, lane);
+        const uint32_t jk = (uint32_t)__builtin_amdgcn_readlane((int)j, k * G);
+        uint64_t* const list = sublists + (size_t)jk * K;
+        if constexpr (RANGE) {
+          if (scan_in_range(key, p.range_bound)) {  // (wave-uniform)
+            if (lane == 0) subcounts[jk] += 1u;
+            if (scan_key_less(key, list[K - 1])) scan_insert(list, K, key, lane);
+          }
+        } else {
+          if (scan_key_less(key, list[K - 1])) scan_insert(list, K, key, lane);
+        }
         pm &= pm - 1;
       }
     }
@@ -125,7 +136,7 @@ __device__ __forceinline__ uint32_t mf32_rescore(const ScanParams& p, F query_at
 
 // (two wavefronts per SIMD: 256 registers each -- raw 64, narrowed 32, accumulators 16, row terms 32)
 // One kernel template for both kinds of call.  GROUPED: the parameter block is the grouped launch's, `gp` points at it.
-template <int METRIC, bool GROUPED>
+template <int METRIC, bool GROUPED, bool RANGE = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void exhaustive_scan_matrix_f32_any_kernel(
     const std::conditional_t<GROUPED, GroupedScanParams, ScanMatrixFloatParams> kp) {
   const ScanParams& p = matrix_scan_params(kp);
@@ -157,6 +168,12 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
     if constexpr (GROUPED) return reinterpret_cast<const float*>(p.queries) + (uint64_t)gp->perm[gt.first + qq] * dim;
     else return queries + (uint64_t)qq * dim;
   };
+
+  // RANGE (scan.hpp, "Range search"): the tile's in-range counters, behind everything else, and the radius the prefilter drops by
+  [[maybe_unused]] uint32_t* const counts =
+      reinterpret_cast<uint32_t*>(smem + (size_t)p.tile_queries * ((uint32_t)S * 32u + p.K * 8u + 8u) + (GROUPED ? MATRIX_QUEUE_IDS * 4u : 0u));
+  [[maybe_unused]] const float radius = __uint_as_float(scan_key_dist_bits(p.range_bound));
+  if constexpr (RANGE) scan_clear_counts(counts, nqb, lane);
 
   // ---- the tile's queries narrowed into operand order (zero beyond dim and beyond the tile), their norms and margin terms
   // from the float32 values, the lists
@@ -301,6 +318,9 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
         const uint64_t kth = lists[(size_t)qq * K + (K - 1)];
         if (kth != SCAN_PAD) kd = __uint_as_float(scan_key_dist_bits(kth));
       }
+      // RANGE: a pair that may lie within the radius is rescored to be counted, even where it cannot enter the list -- so the
+      // radius, not the K-th distance, is what a pair is dropped by (scan_select.hpp, where the margin is derived)
+      if constexpr (RANGE) kd = radius;
       uint32_t mine = 0;  // bit v: the pair (this lane's query, row mf32_row(v, half)) survives
 #pragma unroll
       for (int v = 0; v < 16; v++) {
@@ -320,10 +340,10 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
         };
         uint32_t n = 0;
         switch (kp.group_lanes) {  // the row configurations of float32 rows (search_types.h, kCfgs)
-          case 8: n = mf32_rescore<METRIC, 8>(p, query_at, sublists, mine, id, lane); break;
-          case 16: n = mf32_rescore<METRIC, 16>(p, query_at, sublists, mine, id, lane); break;
-          case 32: n = mf32_rescore<METRIC, 32>(p, query_at, sublists, mine, id, lane); break;
-          default: n = mf32_rescore<METRIC, 64>(p, query_at, sublists, mine, id, lane); break;
+          case 8: n = mf32_rescore<METRIC, 8, RANGE>(p, query_at, sublists, mine, id, lane, counts + t * MF32_N); break;
+          case 16: n = mf32_rescore<METRIC, 16, RANGE>(p, query_at, sublists, mine, id, lane, counts + t * MF32_N); break;
+          case 32: n = mf32_rescore<METRIC, 32, RANGE>(p, query_at, sublists, mine, id, lane, counts + t * MF32_N); break;
+          default: n = mf32_rescore<METRIC, 64, RANGE>(p, query_at, sublists, mine, id, lane, counts + t * MF32_N); break;
         }
         rescored += n;
       }
@@ -334,10 +354,11 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2))) void 
     atomicAdd(kp.counters + 1, rescored);
   }
   scan_flush_tile(p, lists, nqb, seg, lane, query_of);
+  if constexpr (RANGE) scan_flush_counts(p, counts, nqb, seg, lane, query_of);
 }
-template <int METRIC>
-constexpr scan_mf_fn exhaustive_scan_matrix_f32_kernel = exhaustive_scan_matrix_f32_any_kernel<METRIC, false>;
-template <int METRIC>
-constexpr scan_grouped_fn exhaustive_scan_matrix_f32_grouped_kernel = exhaustive_scan_matrix_f32_any_kernel<METRIC, true>;
+template <int METRIC, bool RANGE = false>
+constexpr scan_mf_fn exhaustive_scan_matrix_f32_kernel = exhaustive_scan_matrix_f32_any_kernel<METRIC, false, RANGE>;
+template <int METRIC, bool RANGE = false>
+constexpr scan_grouped_fn exhaustive_scan_matrix_f32_grouped_kernel = exhaustive_scan_matrix_f32_any_kernel<METRIC, true, RANGE>;
 
 }  // namespace fnv_dev

@@ -43,6 +43,25 @@ FNV_SCAN_HD inline uint32_t scan_key_node(uint64_t key) { return (uint32_t)key; 
 // a ranks before b
 FNV_SCAN_HD inline bool scan_key_less(uint64_t a, uint64_t b) { return a < b; }
 
+// ---- range search (option "scan_radius"): the K nearest among the candidates within distance r, and how many there were ------
+// The radius as a bound on the key: the largest key any (d <= r, node id) pair can have, so that
+//     a pair is IN RANGE  iff  !scan_key_less(scan_range_bound(r), its key)
+// in every engine -- the order the selection already uses decides, not a float compare of its own.  It follows that order:
+// a NaN distance (SCAN_NAN_ORD, above +inf's) is in no range, r = +inf admits every number, -0 and +0 are one radius and one
+// distance, and an inner-product radius may be negative.  A NaN radius is no radius: fnv_set_option refuses it, and here it
+// gives a bound below every key.  A list entry must beat  min(list[K - 1], bound + 1):  it is in range AND before the K-th.
+constexpr int64_t SCAN_RADIUS_OFF = -1;  // the option's "no radius" (any negative value); 0 .. 2^32 - 1: the radius's float32 bits
+FNV_SCAN_HD inline uint64_t scan_range_bound(uint32_t radius_bits) {
+  const uint32_t ord = scan_dist_ord(radius_bits);
+  if (ord == SCAN_NAN_ORD) return 0ull;  // (no real key is 0: the smallest ord, -inf's, is 0x007FFFFF)
+  return ((uint64_t)ord << 32) | 0xFFFFFFFFull;
+}
+FNV_SCAN_HD inline bool scan_in_range(uint64_t key, uint64_t bound) { return !scan_key_less(bound, key); }
+// The option's value: off, a radius, or neither (FNV_ERR_INVALID: beyond 32 bits, or the bits of a NaN).
+FNV_SCAN_HD inline bool scan_radius_valid(int64_t value) {
+  return value < 0 || (value <= 0xFFFFFFFFll && scan_dist_ord((uint32_t)value) != SCAN_NAN_ORD);
+}
+
 // Entries of the sorted list[0, n) that rank before `key` / that do not rank after it.
 FNV_SCAN_HD inline uint32_t scan_lower_bound(const uint64_t* list, uint32_t n, uint64_t key) {
   uint32_t lo = 0, hi = n;
@@ -101,6 +120,9 @@ struct ScanParams {
   uint32_t segments;           // row segments: block b scans segment b / tiles for query tile b % tiles
   uint32_t tile_queries;       // queries staged in LDS per block: that many share one load of a row
   uint32_t tiles;              // ceil(nq / tile_queries)
+  // Range search (the kernels' RANGE forms and the merge; a launch without a radius leaves both zero and runs the other forms):
+  uint32_t* range_counts;      // [nq][segments]: every (query, segment)'s in-range candidates, behind the partial lists; null: no radius
+  uint64_t range_bound;        // scan_range_bound(radius)
 };
 
 // ---- the float16 matrix engine's prefilter (scan_matrix_f16.hpp, option "scan_matrix_float") ---------------------------------
@@ -131,6 +153,10 @@ struct ScanParams {
 // for (d), four times the bound, plus 2^-21 for the rounding of 1 - s.  A margin too wide costs rescored pairs; one too narrow
 // costs a wrong result, so none of these constants is tuned against a test.  NaN and infinite norms give a NaN or infinite
 // margin, which the kernel's compare lets pass (tests/test_scan_matrix_f16_plan.py holds the finite case on the CPU).
+// Range search ("scan_radius") asks nothing more of the margin: |s~ - d| <= margin bounds the score's distance from the vector
+// scan's d whatever d is compared with, so  s~ - margin > r  implies  d > r  just as it implied d > the K-th distance: the pair
+// is out of range and may go unscored and uncounted.  The engines' RANGE forms drop by r INSTEAD of the K-th distance -- a pair
+// that may lie within r must be rescored to be counted, even where it cannot enter the list.  The same holds for scan_margin_f32.
 constexpr float kScanMarginKappa = 16.0f;
 FNV_SCAN_HD inline float scan_margin_term(uint32_t P, float n) {  // one side's share: the kernel forms it once per row and per query
   return kScanMarginKappa * (float)(P + 4u) * 0x1p-23f * n + 0x1p-11f * sqrtf((float)P * n);

@@ -580,6 +580,8 @@ class DeviceIndex:
                          "exhaustive_scan_matrix_float", "exhaustive_scan_matrix_float32"][int(g[6])]
         out["kernel_mode"] = int(g[6])  # fnv_last_launch_geometry's own ordinal (4: the exhaustive search's matrix engine, 5: its float16 form, 6: its float32 form)
         out["tail_exact"] = int(g[7])
+        if int(g[6]) in (3, 4, 5, 6):  # an exhaustive search: the last field says whether it was a range search ("scan_radius")
+            out["range"] = int(g[7])
         if int(g[6]) in (4, 5, 6):
             out["tile_queries"], out["segments"] = int(g[3]), int(g[5])
             if int(g[4]):  # a grouped call ("scan_matrix_grouped"): the engine's id queue

@@ -93,6 +93,7 @@ class DeviceMirror {
   bool _filter_scan_on_overflow = false;
   bool _exhaustive_matrix = false, _exhaustive_matrix_float = false, _exhaustive_matrix_float32 = false,
        _exhaustive_matrix_grouped = false;  // setExhaustiveMatrix: likewise
+  int64_t _exhaustive_radius = -1;          // setExhaustiveRadius: likewise (option "scan_radius": -1 = off, else the radius's float32 bits)
   // several GPUs: the mirror on _ordinal is the primary; replicas of it live on the other devices of _devices (filled by peer
   // copies, refreshed whenever the primary changes); batches are sharded over all of them
   int _ordinal = 0;
@@ -152,6 +153,7 @@ class DeviceMirror {
     }
     if (_filter_scan_max != 0 || _filter_scan_on_overflow) applyFilterRouting();  // (a new handle starts with the library's defaults)
     if (_exhaustive_matrix) applyExhaustiveMatrix();
+    if (_exhaustive_radius >= 0) throwOnDeviceError(fnv_set_option(_handle, "scan_radius", _exhaustive_radius));
   }
 
   // The GPUs this index spreads its batches over: setDevices(), else the FLATNAV_DEVICES environment variable
@@ -299,6 +301,12 @@ class DeviceMirror {
     _exhaustive_matrix_float32 = on && float32_rows;
     _exhaustive_matrix_grouped = on && grouped;
     if (_handle) applyExhaustiveMatrix();
+  }
+  // Range search (option "scan_radius"; `bits`: -1 = off, else the float32 bits of a radius that is not a NaN -- the caller has
+  // checked): now if there is a mirror, and on every mirror made later.
+  void setExhaustiveRadius(int64_t bits) {
+    _exhaustive_radius = bits;
+    if (_handle) throwOnDeviceError(fnv_set_option(_handle, "scan_radius", bits));
   }
 
  private:

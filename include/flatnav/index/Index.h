@@ -30,6 +30,7 @@
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -381,6 +382,22 @@ class Index {
   void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false) {
     std::lock_guard<std::mutex> g(_mirror.mutex());
     _mirror.setExhaustiveMatrix(on, float_rows, float32_rows, grouped);
+  }
+  // Range search (flatnav_hip.h, option "scan_radius"): with a radius r, searchBatchExhaustive and searchBatchExhaustiveGrouped
+  // return each query's K nearest among the candidates whose distance is at most r (a NaN distance never is; r = +inf admits
+  // every number), and their per-query distance counter becomes the number of candidates within r -- which may exceed K.
+  // std::nullopt turns it off again; a NaN radius is refused.  Every other search ignores it.  Applies to the device mirror now
+  // if there is one, and to every mirror made later.
+  void setExhaustiveRadius(std::optional<float> radius) {
+    int64_t bits = -1;
+    if (radius) {
+      if (*radius != *radius) throw std::invalid_argument("setExhaustiveRadius: the radius must not be a NaN");
+      uint32_t b;
+      std::memcpy(&b, &*radius, sizeof(b));
+      bits = static_cast<int64_t>(b);
+    }
+    std::lock_guard<std::mutex> g(_mirror.mutex());
+    _mirror.setExhaustiveRadius(bits);
   }
   // The C-ABI handle of the device mirror (valid until the next mutation); for callers that drive
   // fnv_search_batch_device on their own buffers / streams.

@@ -268,6 +268,12 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *                     index's element type as well, PROVIDED that engine's own option above is on too (see
  *                     fnv_search_batch_exhaustive, "Grouped calls"; default 0 = off: a grouped call keeps the vector scan
  *                     whatever the three options say).  Same bytes.  Read per launch; keeps what fnv_tune measured.
+ *   "scan_radius"     exhaustive search: range search (see fnv_search_batch_exhaustive, "Range search").  Any value < 0 (default
+ *                     -1; the one option besides the two -1 defaults that takes negative values) = off; 0 .. 2^32 - 1 = the
+ *                     IEEE-754 bits of the float32 radius r (inner-product distances can be negative, so the sign bit is a legal
+ *                     bit): fnv_search_batch_exhaustive[_grouped][_device] then return the K nearest among the candidates with
+ *                     distance <= r, and out_ndist[q] = how many candidates were that near.  Bits that decode to a NaN, and values
+ *                     >= 2^32, are FNV_ERR_INVALID.  Every other call ignores it.  Read per launch; keeps what fnv_tune measured.
  *   "filter_scan_max"  filter routing (see "Filter routing" below; default 0 = off): in fnv_search_batch_filtered[_grouped][_device] a
  *                     query whose filter allows at most this many live nodes is answered by the exhaustive scan instead of
  *                     the graph search.  Keeps what fnv_tune / the adaptive choice measured, as the next one does.
@@ -417,6 +423,24 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     keeps the vector scan; the scan stage of a routed filtered graph search keeps it under every option.
  *     fnv_last_launch_geometry reports {grid_blocks, 64, lds_bytes, queries per tile, entries of the id queue, row segments,
  *     kernel = 4, 5 or 6, 0}; fnv_last_replayed_queries the pairs after kernels 5 and 6.
+ *   Range search (option "scan_radius" = the float32 bits of a radius r): which items lie within r of a query, and how many.
+ *     A candidate (a live node, allowed by the query's filter if it has one) is IN RANGE iff the float32 distance d the scan
+ *     reports for the pair satisfies d <= r; a NaN distance never is, r = +inf admits every number, -0 and +0 are one radius.
+ *     Each query's row holds its K nearest IN-RANGE candidates, ordered and padded as above; out_count[q] = the entries written.
+ *     CHANGED MEANING: out_ndist[q] = the number of in-range candidates, which may exceed K -- so out_ndist[q] > out_count[q]
+ *     says the row was cut at K and by how much.  (Without a radius out_ndist stays the candidate count.)  The result is exact
+ *     and the same for every engine, row layout, segmentation and tiling: "in range" is decided on the 64-bit key the selection
+ *     orders by (csrc/scan_select.hpp, scan_range_bound).  On the device the radius bounds every list from the first row: the
+ *     vector scan drops a row with one compare against min(K-th key, bound) and counts the in-range ones per (query, segment) with
+ *     a ballot; the int8 matrix engine counts from the accumulator tile; the float16 / float32 engines drop -- uncounted -- a pair
+ *     whose score less its margin is above r, rescore every other pair exactly, count it iff its exact d <= r and insert it iff it
+ *     also beats the K-th entry (fnv_last_replayed_queries keeps reporting the pairs rescored).  The merge adds the segments'
+ *     counts.  Temporary HBM: nq x S x 4 bytes more.  The option never makes a valid call invalid: where the counters (4 bytes of
+ *     LDS per query of a tile) push a matrix engine's 32 queries beyond a block's LDS the call runs the vector scan.  Applies to
+ *     these two calls and fnv_search_batch_exhaustive_grouped[_device] ONLY: the scan stage of a routed filtered graph search
+ *     ignores the radius, as does every graph search.  fnv_last_launch_geometry reports the same kernel ids (3 to 6) and layouts,
+ *     with its LAST field -- 0 after every launch without a radius -- set to 1.  With the option off (the default) every byte,
+ *     launch and workspace size is what it was.
  * fnv_search_batch_exhaustive: host buffers (allowed_bits included); thread safety and lanes as fnv_search_batch.
  * fnv_search_batch_exhaustive_device: every buffer, allowed_bits included, in the index's device memory, enqueued on `hip_stream`
  *   without synchronising; one launch in flight per handle, as fnv_search_batch_device.

@@ -22,7 +22,12 @@ for byte at every fraction.
 With --grouped N_FILTERS[,N_FILTERS...] the call is search_exhaustive_grouped instead ("scan_matrix_grouped" = 1 on top of the
 engine's option against the grouped vector scan, csrc/scan_matrix_feed.hpp): for every filter count and every share of
 --allowed SHARE[,SHARE...] a table of that many random filters, each allowing that share of the labels, the queries spread evenly
-over the filters (query q uses filter q % N_FILTERS).  The line's candidates are then the mean per query, and --fractions is not read."""
+over the filters (query q uses filter q % N_FILTERS).  The line's candidates are then the mean per query, and --fractions is not read.
+
+With --radius ROWS[,ROWS...] the comparison is the range search's (option "scan_radius"): for every target, a radius that admits
+about that many rows per query; per engine, the unfiltered call with the radius against the same call without it, alternating in
+every round -- medians, min and max, the ratio, whether the range call is slower by more than the other's own max - min, the mean
+number of rows in range (out_ndist) and the share of pairs a float engine rescored in either call.  --fractions is not read."""
 import argparse
 import ctypes
 import json
@@ -52,6 +57,7 @@ ap.add_argument("--dtype", default="uint8", choices=["uint8", "float16", "float3
 ap.add_argument("--dim", type=int, default=128)
 ap.add_argument("--grouped", default="", help="filter counts of grouped calls, comma separated")
 ap.add_argument("--allowed", default="0.5", help="grouped calls: the share of the labels a filter allows, comma separated")
+ap.add_argument("--radius", default="", help="range search: rows per query the radius should admit, comma separated (e.g. 10,10000)")
 args = ap.parse_args()
 
 HALVES = args.dtype != "uint8"  # a float engine: Gaussian rows, a prefilter with rescoring
@@ -113,8 +119,64 @@ def filter_table(n_filters, share):
     return table, counts
 
 
+def radius_lines():
+    """--radius: the unfiltered call with option "scan_radius" against the same call without it, per engine, alternating in every
+    round.  The radius that admits `rows` rows per query on average: bisected on the scan's own out_ndist, between the smallest
+    distance of the radius-off call and a radius that admits enough."""
+    empty = torch.zeros(1, dtype=torch.uint8, device=dev_t)
+
+    def mean_in_range(r):
+        scan.set_option("scan_radius", int(np.array([r], np.float32).view(np.uint32)[0]))
+        launch(1, empty, 0)
+        torch.cuda.synchronize()
+        return out[1][3].double().mean().item()
+
+    scan.set_option("scan_radius", -1)
+    launch(1, empty, 0)
+    torch.cuda.synchronize()
+    nearest, kth = float(out[1][0].min().item()), float(out[1][0][:, -1].max().item())
+    found = []
+    for rows in [int(x) for x in args.radius.split(",")]:
+        lo, hi = nearest, kth
+        while mean_in_range(hi) < rows:
+            hi = lo + 2.0 * (hi - lo)
+        for _ in range(16):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if mean_in_range(mid) < rows else (lo, mid)
+        r = hi
+        for e in (0, 1):
+            def call(radius_on, e=e, r=r):
+                scan.set_option("scan_radius", int(np.array([r], np.float32).view(np.uint32)[0]) if radius_on else -1)
+                launch(e, empty, 0)
+            shares, ms = {}, {False: [], True: []}
+            for on in (False, True):  # warm-up; the kernel that ran, the in-range rows, the pairs rescored
+                once(lambda: call(on), 1)
+                scan.status()
+                g, rs = scan.launch_geometry(), scan.scan_rescored()
+                assert g["kernel_mode"] == (MODE if e else 3) and g["range"] == int(on), g
+                shares[on] = rs["rescored"] / max(1, rs["scored"])
+            in_range = out[e][3].double().mean().item()
+            for _ in range(args.rounds):
+                for on in (False, True):
+                    ms[on].append(once(lambda: call(on), args.steps))
+            med = {on: statistics.median(ms[on]) for on in ms}
+            spread = max(ms[False]) - min(ms[False])
+            found.append(dict(dtype=args.dtype, dim=DIM, engine="matrix" if e else "vector", target_rows=rows, radius=r, in_range_mean=in_range,
+                              off_ms=ms[False], range_ms=ms[True], off_median=med[False], range_median=med[True],
+                              ratio=med[False] / med[True], off_spread=spread, slower_beyond_spread=bool(med[True] - med[False] > spread),
+                              rescored_share_off=shares[False], rescored_share_range=shares[True]))
+            print("radius %-12g (target %d rows, %.1f in range) %-6s | off %9.3f ms [%9.3f .. %9.3f] | range %9.3f ms [%9.3f .. %9.3f] | "
+                  "off / range %5.2fx  slower beyond spread: %s | rescored %.5f -> %.5f of the pairs"
+                  % (r, rows, in_range, found[-1]["engine"], med[False], min(ms[False]), max(ms[False]), med[True], min(ms[True]), max(ms[True]),
+                     found[-1]["ratio"], found[-1]["slower_beyond_spread"], shares[False], shares[True]), flush=True)
+    scan.set_option("scan_radius", -1)
+    return found
+
+
 GROUPED = [int(x) for x in args.grouped.split(",") if x]
 CASES = [(f, g) for g in GROUPED for f in [float(x) for x in args.allowed.split(",")]] if GROUPED else [(float(x), 0) for x in args.fractions.split(",")]
+if args.radius:  # (the range search's own comparison; no fractions, no grouped calls)
+    CASES = []
 scan.set_option(OPTION, 1 if GROUPED else 0)  # (grouped calls: the engine's own option stays on, "scan_matrix_grouped" alternates)
 lines = []
 for f, n_filters in CASES:
@@ -159,6 +221,8 @@ for f, n_filters in CASES:
           % (n_filters, f, len(rows), med[0], min(ms[0]), max(ms[0]), med[1], min(ms[1]), max(ms[1]), line["ratio"], line["beats_by_more_than_spread"],
              geom[1]["grid_blocks"], geom[1]["lds_bytes"], tile, geom[1]["segments"], line["matrix_tops"], line["matrix_of_peak"],
              line["matrix_row_bytes"], line["rescored_share"]), flush=True)
+if args.radius:
+    lines = radius_lines()
 scan.set_option(OPTION, 0)
 scan.set_option("scan_matrix_grouped", 0)
 if args.json:
