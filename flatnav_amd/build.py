@@ -4,7 +4,7 @@ hipcc cross-compiles for gfx950 without a GPU, so this runs in the dev container
 The kernels are templates over <element type, metric, row configuration>; their instantiations are compiled as 104
 objects (kernel_inst.hip: 13 kernel families x 4 element types x 2 metrics) in parallel, eighteen more for float32 queries on
 half-width mirror rows (HALF_ROWS_FAMILIES x 2 metrics), four for the exhaustive search's matrix engine (MATRIX_FAMILY x uint8 / int8
-x 2 metrics), two for its float16 form (MATRIX_FLOAT_FAMILY x 2 metrics) and two for its float32 form (MATRIX_FLOAT32_FAMILY x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
+x 2 metrics), two for its float16 form (MATRIX_FLOAT_FAMILY x 2 metrics) and two for its float32 form (MATRIX_FLOAT32_FAMILY x 2 metrics), four for the block form of those two (MATRIX_BLOCK_FAMILY x float16 / float32 x 2 metrics), plus the host units behind csrc/runtime.hpp (HOST_UNITS: host code,
 C ABI, the non-template kernels), one object each in the same pool, and linked into libflatnav_hip.so.  Objects are cached in csrc/_obj and rebuilt
 when a source they include is newer.  The .so stays in-tree (git-ignored, but shipped by gpurun)."""
 from __future__ import annotations
@@ -22,13 +22,14 @@ LIB = os.path.join(HERE, "libflatnav_hip.so")
 HEADERS = [os.path.join(CSRC, f) for f in ("search_types.h", "search_params.h", "kernel_table.h", "heaps.hpp", "distance.hpp",
                                            "visited.hpp", "kernels.hpp", "wire.hpp", "merged_beam.hpp", "runtime.hpp",
                                            "launch_plan.hpp", "measurements.hpp", "half_rows.hpp", "scan.hpp", "scan_select.hpp",
-                                           "scan_matrix.hpp", "scan_matrix_f16.hpp", "scan_matrix_f32.hpp", "scan_matrix_feed.hpp")] + [
+                                           "scan_matrix.hpp", "scan_matrix_f16.hpp", "scan_matrix_f32.hpp", "scan_matrix_feed.hpp",
+                                           "scan_matrix_block.hpp")] + [
     os.path.join(ROOT, "include", "flatnav", "util", "StlExact.h"), os.path.join(ROOT, "include", "flatnav_hip.h")]
 # The host units behind runtime.hpp, which brings launch_plan.hpp with measurements.hpp (kernel units include none) and, through kernel_table.h,
 # the device headers that say what a launch passes.  Each unit with the kernel headers it includes on top of those (launch.hip:
 # scan.hpp for its non-template kernels; the others in developer builds, where it instantiates the search kernels itself).
 HOST_HEADERS = ("runtime.hpp", "launch_plan.hpp", "measurements.hpp")
-KERNEL_HEADERS = ("scan.hpp", "kernels.hpp", "merged_beam.hpp", "visited.hpp")
+KERNEL_HEADERS = ("scan.hpp", "kernels.hpp", "merged_beam.hpp", "visited.hpp", "scan_matrix_block.hpp")
 HOST_UNITS = {"index.hip": (), "launch.hip": KERNEL_HEADERS, "host_search.hip": (), "multi.hip": (), "tune.hip": (),
               "device_build.hip": ()}
 INST = os.path.join(CSRC, "kernel_inst.hip")
@@ -53,11 +54,14 @@ MATRIX_FLOAT_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops
 # ... and its float32 form (csrc/scan_matrix_f32.hpp; FNV_FOR_EACH_MATRIX_FLOAT32_METRIC): new code as well, same flags -- the norms
 # and the rescoring are per-element fma chains there too.
 MATRIX_FLOAT32_FAMILY = (17, "scan_mf32")
-# The units of these three families also hold their engine's grouped kernel (option "scan_matrix_grouped"): the same body fed from a
+# ... and the block form of those two (csrc/scan_matrix_block.hpp; FNV_FOR_EACH_MATRIX_BLOCK_TYPE_METRIC): float16 and float32 x the
+# metrics, same flags.  It reuses their rescoring, so its units include their headers.
+MATRIX_BLOCK_FAMILY = (18, "scan_mb")
+# The units of the three families before it also hold their engine's grouped kernel (option "scan_matrix_grouped"): the same body fed from a
 # filter row's bitmap by csrc/scan_matrix_feed.hpp, which all three include.
 # headers that only some families' units include (a change to them leaves every other object current)
-FAMILY_HEADERS = {"scan_matrix.hpp": ("scan_m",), "scan_matrix_f16.hpp": ("scan_mf",), "scan_matrix_f32.hpp": ("scan_mf32",),
-                  "scan_matrix_feed.hpp": ("scan_m", "scan_mf", "scan_mf32")}
+FAMILY_HEADERS = {"scan_matrix.hpp": ("scan_m",), "scan_matrix_f16.hpp": ("scan_mf", "scan_mb"), "scan_matrix_f32.hpp": ("scan_mf32", "scan_mb"),
+                  "scan_matrix_feed.hpp": ("scan_m", "scan_mf", "scan_mf32", "scan_mb"), "scan_matrix_block.hpp": ("scan_mb",)}
 
 
 def hipcc() -> str:
@@ -76,7 +80,9 @@ def _units(defines):
                                                                                  ["-DFNV_INST_HALF_ROWS"])] + [
                                                                                      (t, [MATRIX_FAMILY], []) for t in MATRIX_TYPES] + [
                                                                                          (TYPES[3], [MATRIX_FLOAT_FAMILY], MATRIX_FLOAT_FLAGS),
-                                                                                         (TYPES[0], [MATRIX_FLOAT32_FAMILY], MATRIX_FLOAT_FLAGS)]:
+                                                                                         (TYPES[0], [MATRIX_FLOAT32_FAMILY], MATRIX_FLOAT_FLAGS),
+                                                                                         (TYPES[3], [MATRIX_BLOCK_FAMILY], MATRIX_FLOAT_FLAGS),
+                                                                                         (TYPES[0], [MATRIX_BLOCK_FAMILY], MATRIX_FLOAT_FLAGS)]:
         for metric, mtag in METRICS:
             for fam, fname in families:
                 units.append((os.path.join(OBJ, "inst_%s_%s_%s.o" % (fname, tag, mtag)), INST,

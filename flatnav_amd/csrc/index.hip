@@ -611,6 +611,10 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   else if (n == "scan_matrix_float") ix->scan_matrix_float = value != 0;  // (likewise)
   else if (n == "scan_matrix_float32") ix->scan_matrix_float32 = value != 0;  // (likewise)
   else if (n == "scan_matrix_grouped") ix->scan_matrix_grouped = value != 0;  // (likewise)
+  else if (n == "scan_matrix_block") {  // (likewise)
+    if (value != 0 && value != 1) return fail(FNV_ERR_INVALID, "scan_matrix_block must be 0 or 1");
+    ix->scan_matrix_block = value;
+  }
   else if (n == "scan_radius") {  // (read per exhaustive launch; scan_select.hpp, "range search")
     if (!scan_radius_valid(value)) return fail(FNV_ERR_INVALID, "scan_radius must be negative (off) or the bits of a float32 radius that is not a NaN");
     ix->scan_radius = value < 0 ? SCAN_RADIUS_OFF : value;
@@ -623,7 +627,7 @@ int fnv_set_option(fnv_index_t ix, const char* name, int64_t value) {
   // What fnv_tune measured (kernel variant, LDS layout) stays valid across options that change neither the launch plan
   // nor the kernel choice: Index.h::addBatchDevice flips output_node_ids around every device build, and a tune costs
   // dozens of launches.  (output_node_ids is read per launch; shadow_exact per launch; tune_layout by fnv_tune itself.)
-  const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows" || n == "scan_matrix" || n == "scan_matrix_float" || n == "scan_matrix_float32" || n == "scan_matrix_grouped" || n == "scan_radius" ||
+  const bool keeps_tuning = n == "output_node_ids" || n == "shadow_exact" || n == "tune_layout" || n == "visited_direct" || n == "host_zero_copy" || n == "scan_segment_rows" || n == "scan_matrix" || n == "scan_matrix_float" || n == "scan_matrix_float32" || n == "scan_matrix_grouped" || n == "scan_matrix_block" || n == "scan_radius" ||
                             n == "filter_scan_max" || n == "filter_scan_on_overflow" || n == "launch_timing";  // (filtered launches never touch the measurements)
   // (either way the epoch goes up: the hidden lanes of the host entry point re-copy options and measurements)
   if (keeps_tuning) ix->measured.touch();

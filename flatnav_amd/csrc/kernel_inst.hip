@@ -6,7 +6,8 @@
 // the exact family (without the entry scan) and the merged-beam families with their DIRECT forms, for the row configurations
 // a mirror exists for -- four for family 15 (scan_m: the exhaustive search's matrix engine, uint8 / int8 x the metrics), two
 // for family 16 (scan_mf: that engine's float16 form, scan_matrix_f16.hpp) and two for family 17 (scan_mf32: its float32 form,
-// scan_matrix_f32.hpp); each of those eight holds the engine's ungrouped and its grouped kernel.
+// scan_matrix_f32.hpp); each of those eight holds the engine's ungrouped and its grouped kernel -- and four for family 18
+// (scan_mb: the block form of the two float engines, scan_matrix_block.hpp; float16 / float32 x the metrics).
 #include <hip/hip_runtime.h>
 
 #include "kernel_table.h"
@@ -19,6 +20,8 @@
 #include "scan_matrix_f16.hpp"
 #elif FNV_INST_FAMILY == 17
 #include "scan_matrix_f32.hpp"
+#elif FNV_INST_FAMILY == 18
+#include "scan_matrix_block.hpp"
 #endif
 #include "wire.hpp"
 
@@ -71,6 +74,10 @@ void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTab
   t.flat_mg = exhaustive_scan_matrix_f32_grouped_kernel<METRIC>;
   t.flat_mf32r = exhaustive_scan_matrix_f32_kernel<METRIC, true>;
   t.flat_mgr = exhaustive_scan_matrix_f32_grouped_kernel<METRIC, true>;
+}
+#elif FNV_INST_FAMILY == 18  // ... and the block form of the two float forms
+void FNV_CAT(fill_, FNV_INST_FNAME, _, FNV_INST_TAG, _, FNV_INST_MTAG)(KernelTable& t) {
+  t.flat_mb = exhaustive_scan_matrix_block_kernel<T, METRIC>;
 }
 #else
 template <bool FULL>

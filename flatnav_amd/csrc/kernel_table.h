@@ -14,6 +14,7 @@ typedef void (*wire_fn)(const WireParams);
 typedef void (*scan_fn)(const ScanParams);
 typedef void (*scan_grouped_fn)(const GroupedScanParams);
 typedef void (*scan_mf_fn)(const ScanMatrixFloatParams);
+typedef void (*scan_mb_fn)(const ScanMatrixBlockParams);
 
 // All kernels for one (element type, metric): [row configuration][FULL rows].
 struct KernelTable {
@@ -36,6 +37,7 @@ struct KernelTable {
   scan_fn flat_mr;
   scan_mf_fn flat_mfr, flat_mf32r;
   scan_grouped_fn flat_mgr;
+  scan_mb_fn flat_mb;                  // exhaustive_scan_matrix_block_kernel (scan_matrix_block.hpp; float16 and float32 only, else null): the block form of flat_mf / flat_mf32
 };
 
 // X(element type, type tag, metric ordinal, metric tag)
@@ -72,6 +74,9 @@ struct KernelTable {
 // Family 17, its float32 form (scan_matrix_f32.hpp: the same prefilter on operands narrowed to bfloat16 in registers): one kernel
 // per metric, for float32 indexes only.  X(metric ordinal, metric tag)
 #define FNV_FOR_EACH_MATRIX_FLOAT32_METRIC(X) X(0, l2) X(1, ip)
+// Family 18, the block form of families 16 and 17 (scan_matrix_block.hpp: several wavefronts share every row tile through LDS):
+// one kernel per (float element type, metric).  X(element type, type tag, metric ordinal, metric tag)
+#define FNV_FOR_EACH_MATRIX_BLOCK_TYPE_METRIC(X) X(_Float16, f16, 0, l2) X(_Float16, f16, 1, ip) X(float, f32, 0, l2) X(float, f32, 1, ip)
 
 #define FNV_DECLARE_FILLER(ordinal, family, tag, mtag) void fill_##family##_##tag##_##mtag(KernelTable& t);
 #define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_FOR_EACH_FAMILY(FNV_DECLARE_FILLER, tag, mtag)
@@ -88,6 +93,9 @@ FNV_FOR_EACH_MATRIX_FLOAT_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #define FNV_DECLARE_FILLERS(M, mtag) FNV_DECLARE_FILLER(17, scan_mf32, f32, mtag)
 FNV_FOR_EACH_MATRIX_FLOAT32_METRIC(FNV_DECLARE_FILLERS)
+#undef FNV_DECLARE_FILLERS
+#define FNV_DECLARE_FILLERS(T, tag, M, mtag) FNV_DECLARE_FILLER(18, scan_mb, tag, mtag)
+FNV_FOR_EACH_MATRIX_BLOCK_TYPE_METRIC(FNV_DECLARE_FILLERS)
 #undef FNV_DECLARE_FILLERS
 #undef FNV_DECLARE_FILLER
 

@@ -12,6 +12,7 @@
 #ifdef FNV_DEV_FAST_BUILD
 #include "scan_matrix.hpp"
 #include "scan_matrix_f16.hpp"
+#include "scan_matrix_block.hpp"
 #include "scan_matrix_f32.hpp"
 #endif
 
@@ -147,6 +148,9 @@ const KernelTable& kernel_table(int, int, bool = false) {
     if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) k.flat_mf = exhaustive_scan_matrix_f16_kernel<FNV_DEV_METRIC>;
     k.flat_mf32 = nullptr;
     if constexpr (std::is_same<FNV_DEV_T, float>::value) k.flat_mf32 = exhaustive_scan_matrix_f32_kernel<FNV_DEV_METRIC>;
+    k.flat_mb = nullptr;  // ... the block form of the two float forms
+    if constexpr (std::is_same<FNV_DEV_T, _Float16>::value || std::is_same<FNV_DEV_T, float>::value)
+      k.flat_mb = exhaustive_scan_matrix_block_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
     k.flat_mg = nullptr;  // ... and the grouped form of whichever the element type has
     if constexpr (sizeof(FNV_DEV_T) == 1) k.flat_mg = exhaustive_scan_matrix_grouped_kernel<FNV_DEV_T, FNV_DEV_METRIC>;
     if constexpr (std::is_same<FNV_DEV_T, _Float16>::value) k.flat_mg = exhaustive_scan_matrix_f16_grouped_kernel<FNV_DEV_METRIC>;
@@ -192,6 +196,10 @@ const KernelTable& kernel_table(int dtype, int metric, bool half_rows = false) {
     i = 0;
 #define FNV_FILL(M, mtag) fill_scan_mf32_f32_##mtag(tables[i++]);
     FNV_FOR_EACH_MATRIX_FLOAT32_METRIC(FNV_FILL)
+#undef FNV_FILL
+    // ... and the block form of those two: the float16 tables, then the float32 tables
+#define FNV_FILL(T, tag, M, mtag) fill_scan_mb_##tag##_##mtag(tables[std::is_same<T, float>::value ? M : 6 + M]);
+    FNV_FOR_EACH_MATRIX_BLOCK_TYPE_METRIC(FNV_FILL)
 #undef FNV_FILL
   });
   if (half_rows) return tables[8 + (metric == FNV_METRIC_IP ? 1 : 0)];
@@ -563,7 +571,7 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   const bool range = scan_range_on(ix);
   const ScanShape vector_shape = scan_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0, range);
   if (vector_shape.lds > kScanMaxLds) return fail(FNV_ERR_INVALID, "rows are too long for an exhaustive search (one query and its list must fit in LDS)");
-  const ScanMatrixShape matrix = scan_matrix_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0, range);
+  const ScanMatrixShape matrix = scan_matrix_shape(ix, g, nq, K, live, grouped ? filter->rows() : 0, range, listed);
   const ScanShape shape = matrix.on ? static_cast<const ScanShape&>(matrix) : vector_shape;
   const GroupArrays ga(nq, grouped ? filter->rows() : 0, shape.tiles);
 
@@ -608,12 +616,20 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
     if (matrix.float_rows || matrix.float32_rows) {  // the float forms: the plain block, the rescoring groups, the two counters the memset above cleared
       const scan_mf_fn kern = range ? (matrix.float32_rows ? table.flat_mf32r : table.flat_mfr) : matrix.float32_rows ? table.flat_mf32 : table.flat_mf;
       if (!kern) return fail(FNV_ERR_RUNTIME, "the float matrix scan kernel of this element type is missing from the build");
-      ScanMatrixFloatParams fp;
+      ScanMatrixBlockParams fp;
       static_cast<ScanParams&>(fp) = gp.s;
       fp.group_lanes = matrix.group_lanes;
       fp.counters = reinterpret_cast<unsigned long long*>(block + fnv_index_s::kScanCounterWord);
-      HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
-      hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, fp);
+      fp.waves = matrix.waves;
+      fp.wave_subtiles = matrix.wave_subtiles;
+      if (matrix.waves) {  // the block form ("scan_matrix_block"; scan_block_shape): several wavefronts per (query tile, row segment)
+        if (!table.flat_mb) return fail(FNV_ERR_RUNTIME, "the block form of the float matrix scan kernel is missing from the build");
+        HIP_TRY(raise_lds_limit((const void*)table.flat_mb, ix->device, shape.lds));
+        hipLaunchKernelGGL(table.flat_mb, dim3(shape.tiles * shape.segments), dim3(matrix.block), shape.lds, stream, fp);
+      } else {
+        HIP_TRY(raise_lds_limit((const void*)kern, ix->device, shape.lds));
+        hipLaunchKernelGGL(kern, dim3(shape.tiles * shape.segments), dim3(WAVE), shape.lds, stream, static_cast<const ScanMatrixFloatParams&>(fp));
+      }
     } else {
       const scan_fn kern = range ? (matrix.on ? table.flat_mr : table.flat_r[g.cfg][g.full]) : matrix.on ? table.flat_m : table.flat[g.cfg][g.full];
       if (!kern) return fail(FNV_ERR_RUNTIME, "the matrix scan kernel of this element type is missing from the build");
@@ -629,9 +645,11 @@ static int scan_device_impl(fnv_index_t ix, const void* d_queries, uint64_t nq, 
   // -- record (mode 3 of fnv_last_launch_geometry: the exhaustive scan; its grouped form: queries per tile, entries of the id
   // queue, row segments.  Mode 4: the matrix engine's scan; queries per tile and row segments.  Modes 5 and 6: its float16 and
   // float32 forms, likewise; a grouped call one of them took: the entries of its id queue where the grouped vector scan has its own.
+  // Modes 7 and 8: the block form of 5 and 6, block_threads = 64 x its wavefronts.
   // The last field, 0 in every other launch: 1 = a range search, the kernels' RANGE forms ran)
-  record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
-                !grouped ? 0 : matrix.on ? MATRIX_QUEUE_IDS : SCAN_QUEUE_IDS, grouped || matrix.on ? shape.segments : 0, matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, range ? 1 : 0);
+  record_launch(ix, stream, block, -1, true, (uint64_t)shape.tiles * shape.segments, matrix.waves ? matrix.block : WAVE, shape.lds, grouped || matrix.on ? shape.tile : 0,
+                !grouped ? 0 : matrix.on ? MATRIX_QUEUE_IDS : SCAN_QUEUE_IDS, grouped || matrix.on ? shape.segments : 0,
+                matrix.waves ? (matrix.float32_rows ? 8 : 7) : matrix.float32_rows ? 6 : matrix.float_rows ? 5 : matrix.on ? 4 : 3, range ? 1 : 0);
   return FNV_OK;
 }
 

@@ -52,6 +52,7 @@ struct IndexOptions {
   int64_t scan_matrix_float = 0;  // ... on float16 indexes: the matrix prefilter with exact rescoring (scan_matrix_f16.hpp)
   int64_t scan_matrix_float32 = 0;  // ... on float32 indexes: the same on operands narrowed to bfloat16 (scan_matrix_f32.hpp)
   int64_t scan_matrix_grouped = 0;  // ... and, with the element type's own option, the grouped exhaustive call (scan_matrix_feed.hpp)
+  int64_t scan_matrix_block = 0;  // ... and, with a float element type's own option, the ungrouped call in workgroups that share row tiles (scan_matrix_block.hpp)
   int64_t scan_radius = SCAN_RADIUS_OFF;  // exhaustive search: negative = off, else the float32 bits of a range search's radius (scan_select.hpp)
   // Filter routing (filtered graph searches; scan_select.hpp): a query whose filter allows at most filter_scan_max live nodes
   // (0: off), or whose candidates heap overflows (filter_scan_on_overflow != 0), is answered by the exhaustive scan.
@@ -679,11 +680,52 @@ struct ScanMatrixShape : ScanShape {
   bool float_rows = false;    // the float16 form
   bool float32_rows = false;  // the float32 form
   uint32_t group_lanes = 0;   // the float forms' rescoring groups: kCfgs[cfg].G
+  uint32_t waves = 0, wave_subtiles = 0;  // the float forms' BLOCK form (scan_block_shape): wavefronts per block, sub-tiles each; 0: the wave form
 };
+// The BLOCK FORM of the two float forms (scan_matrix_block.hpp, exhaustive_scan_matrix_block_kernel; option "scan_matrix_block"
+// on top of the element type's own): W wavefronts per block share every 32-row tile through a ring in LDS and each scores it
+// against its own sub-tiles, so the tile is W times as wide for one read of the rows.  It takes an UNGROUPED call with ONE
+// FILTER (`listed`: its candidates are an id list) and without a radius, on rows of at most kScanBlockSpanSteps MFMA steps,
+// that has at least two sub-tiles of queries, where at least two fit:
+//   LDS = queries x (steps x 32 + 8 K + 8) + kScanBlockRing x scan_block_buffer_bytes(steps);
+//   budget: kScanBlockLdsBudget, which keeps two blocks on a CU, and kScanMaxLds where that holds fewer than two sub-tiles
+//   (long lists);
+//   W = min(kScanBlockMaxWaves, the call's sub-tiles, the sub-tiles that fit); sub-tiles per wavefront = what the call needs
+//   (ceil(sub-tiles / W)), at most kScanBlockMaxWaveSubtiles and what fits;
+//   segments: scan_segments with the blocks a CU holds by this LDS, at most kScanMatrixWavesPerCu wavefronts' worth.
+// Everything else keeps the wave form's shape: `s` as scan_matrix_shape made it is returned unchanged.  (Routed scans and 1-byte
+// indexes never get here.)
+// The class it takes is the one where it MEASURED faster (profiles/scan_matrix_block.md; 1M rows, the wave form in the same rounds).
+// Unfiltered calls (8 - 11 % slower at 128-d) and longer rows (768-d: slower in five of six lines) were built, measured and taken
+// out of the kernel again; it serves neither.  The planner cannot see how many rows a filter allows (the count is device
+// memory): where the filtered class stops paying is in the profile.
+constexpr uint32_t kScanBlockLdsBudget = 80u << 10;
+inline bool scan_block_pays(uint32_t steps, bool listed) { return listed && steps <= kScanBlockSpanSteps; }
+inline ScanMatrixShape scan_block_shape(const PlanInputs* ix, ScanMatrixShape s, uint32_t steps, uint32_t per_query, uint64_t nq, int K, uint64_t live) {
+  // (the caller has asked scan_block_pays: steps <= kScanBlockSpanSteps)
+  const uint32_t ring = kScanBlockRing * scan_block_buffer_bytes(steps), sub_bytes = kScanMatrixN * per_query;
+  const uint64_t call_subtiles = (nq + kScanMatrixN - 1) / kScanMatrixN;
+  if (call_subtiles < 2) return s;
+  uint32_t fit = (kScanBlockLdsBudget - ring) / sub_bytes;  // (the ring of at most kScanBlockSpanSteps steps: 16.75 KB)
+  if (fit < 2) fit = (kScanMaxLds - ring) / sub_bytes;
+  if (fit < 2) return s;
+  const uint32_t waves = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(kScanBlockMaxWaves, fit), call_subtiles);
+  const uint32_t each = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(kScanBlockMaxWaveSubtiles, fit / waves), (call_subtiles + waves - 1) / waves);
+  s.waves = waves;
+  s.wave_subtiles = each;
+  s.block = WAVE * waves;
+  s.tile = waves * each * kScanMatrixN;
+  s.lds = s.tile * per_query + ring;
+  s.tiles = (uint32_t)((nq + s.tile - 1) / s.tile);
+  const uint64_t per_cu = std::min<uint64_t>(std::max<uint32_t>(1u, kScanMatrixWavesPerCu / waves), kLdsPerCu / lds_allocated(s.lds));
+  s.segments = scan_segments(ix, s.tiles, nq, K, live, (uint64_t)std::max(1, ix->num_cus) * per_cu / s.tiles);
+  return s;
+}
 // `range`: as scan_shape's -- one more word per query; where the counters push 32 queries beyond a block's LDS the call keeps the
 // vector scan like any other shape that does not fit.
+// `listed`: an ungrouped call with one filter (its candidates are an id list): what the block form takes (scan_block_pays).
 inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry& g, uint64_t nq, int K, uint64_t live,
-                                         uint64_t filter_rows = 0, bool range = false) {
+                                         uint64_t filter_rows = 0, bool range = false, bool listed = false) {
   ScanMatrixShape s;
   s.tile = s.tiles = s.segments = s.lds = 0;
   const bool bytes = ix->scan_matrix != 0 && (ix->dtype == FNV_DTYPE_UINT8 || ix->dtype == FNV_DTYPE_INT8);
@@ -708,6 +750,7 @@ inline ScanMatrixShape scan_matrix_shape(const PlanInputs* ix, const RowGeometry
   s.tiles = (uint32_t)(filter_rows ? group_tile_bound(nq, filter_rows, s.tile) : (nq + s.tile - 1) / s.tile);
   const uint64_t per_cu = std::min<uint64_t>(kScanMatrixWavesPerCu, kLdsPerCu / lds_allocated(s.lds));
   s.segments = scan_segments(ix, s.tiles, nq, K, live, (uint64_t)std::max(1, ix->num_cus) * per_cu / s.tiles);
+  if (ix->scan_matrix_block != 0 && (halves || floats) && filter_rows == 0 && !range && scan_block_pays(steps, listed)) return scan_block_shape(ix, s, steps, per_query, nq, K, live);
   return s;
 }
 // The partial lists of a launch: one sorted list of K keys per (query, segment); the merge's LDS: three such lists.

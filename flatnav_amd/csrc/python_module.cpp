@@ -342,8 +342,8 @@ class PyIndex : public std::enable_shared_from_this<PyIndex<dist_t, kType>> {
   std::vector<int> devices() { return _index->devices(); }
   void syncDevice() { _index->syncDevice(); }
   void setFilterRouting(int64_t scan_max_allowed, bool scan_on_overflow) { _index->setFilterRouting(scan_max_allowed, scan_on_overflow); }
-  void setExhaustiveMatrix(bool on, bool float_rows, bool float32_rows, bool grouped) {
-    _index->setExhaustiveMatrix(on, float_rows, float32_rows, grouped);
+  void setExhaustiveMatrix(bool on, bool float_rows, bool float32_rows, bool grouped, bool block) {
+    _index->setExhaustiveMatrix(on, float_rows, float32_rows, grouped, block);
   }
   void setExhaustiveRadius(std::optional<float> radius) { _index->setExhaustiveRadius(radius); }
   uintptr_t deviceHandle() { return reinterpret_cast<uintptr_t>(_index->deviceHandle()); }
@@ -416,12 +416,14 @@ void bindIndex(py::module_& m, const char* name) {
            "nodes (0 = off), and with scan_on_overflow one whose search runs out of candidate room (instead of the call "
            "raising), is answered by the exhaustive scan -- that row is search_exhaustive's.")
       .def("set_exhaustive_matrix", &T::setExhaustiveMatrix, py::arg("on") = true, py::arg("float_rows") = false, py::arg("float32_rows") = false,
-           py::arg("grouped") = false,
+           py::arg("grouped") = false, py::arg("block") = false,
            "search_exhaustive on uint8 / int8 indexes (unfiltered or with one `allowed` set) scores rows on the matrix cores: "
            "the same results, byte for byte.  With float_rows=True float16 indexes take part as well: the matrix cores discard "
            "rows that provably cannot reach a query's K-th distance, the rest is scored as before -- the same bytes again.  "
            "With float32_rows=True float32 indexes do the same (their values are narrowed to bfloat16 for the matrix cores only).  "
            "With grouped=True search_exhaustive_grouped runs on whichever of these engines is on for the index's element type.  "
+           "With block=True the float16 and float32 engines answer calls with an `allowed` set and more than 32 queries, on rows "
+           "of up to 128 elements, in workgroups that share every row tile -- fewer reads of the table, the same bytes.  "
            "Every other index type, and search_exhaustive_grouped without it, run as before.")
       .def("set_exhaustive_radius", &T::setExhaustiveRadius, py::arg("radius") = py::none(),
            "Range search: with a radius, search_exhaustive and search_exhaustive_grouped return each query's K nearest among the "

@@ -214,6 +214,19 @@ struct ScanMatrixFloatParams : ScanParams {
   uint32_t group_lanes;
   unsigned long long* counters;
 };
+// The float engines' BLOCK form (scan_matrix_block.hpp, option "scan_matrix_block"): `waves` wavefronts per block, each owning
+// `wave_subtiles` 32-query sub-tiles of the tile (tile_queries = 32 waves wave_subtiles), share every 32-row tile through a ring
+// of kScanBlockRing buffers in LDS behind the wavefronts' queries and lists.  One buffer: a span of at most kScanBlockSpanSteps
+// MFMA steps of the 32 rows in operand order (1 KB a step, 16-bit operands for both element types), the rows' {norm, margin
+// term} pairs, their node ids.  The planner (launch_plan.hpp, scan_block_shape) and the kernel size it by this one function.
+constexpr uint32_t kScanBlockRing = 2, kScanBlockSpanSteps = 8, kScanBlockMaxWaves = 4, kScanBlockMaxWaveSubtiles = 4;
+FNV_SCAN_HD inline uint32_t scan_block_buffer_bytes(uint32_t steps) {
+  return (steps < kScanBlockSpanSteps ? steps : kScanBlockSpanSteps) * 1024u + 32u * 8u + 32u * 4u;
+}
+struct ScanMatrixBlockParams : ScanMatrixFloatParams {
+  uint32_t waves;
+  uint32_t wave_subtiles;
+};
 
 // ---- grouped filters (fnv_search_batch_*_grouped): one allowed set per query ---------------------------------------------
 // A grouped launch keeps n_filters + 2 node bitmaps ("filter rows"): row f < n_filters is filter f, row n_filters holds every

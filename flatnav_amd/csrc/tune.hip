@@ -363,7 +363,7 @@ int fnv_last_replayed_queries(fnv_index_t ix, uint64_t out[5]) {
   bool matrix_float;
   {
     std::lock_guard<std::mutex> lock(ix->mu);
-    matrix_float = ix->geom[6] == 5 || ix->geom[6] == 6;
+    matrix_float = ix->geom[6] >= 5 && ix->geom[6] <= 8;  // (7, 8: their block form)
   }
   if (matrix_float) {  // a float matrix engine's scan (scan_matrix_f16.hpp, scan_matrix_f32.hpp): {pairs scored, pairs rescored} behind the words above
     uint64_t c[2];

@@ -559,7 +559,7 @@ class DeviceIndex:
         exactly; zeros when another engine ran."""
         r = (C.c_uint64 * 5)()
         check(lib().fnv_last_replayed_queries(self._h, r))
-        on = self.launch_geometry()["kernel_mode"] in (5, 6)
+        on = self.launch_geometry()["kernel_mode"] in (5, 6, 7, 8)
         return {"scored": int(r[1]) if on else 0, "rescored": int(r[0]) if on else 0}
 
     def handover_stats(self) -> dict:
@@ -577,12 +577,15 @@ class DeviceIndex:
         keys = ["grid_blocks", "block_threads", "lds_bytes", "blocks_per_cu", "visited_slots", "cand_slots"]
         out = {k: int(g[i]) for i, k in enumerate(keys)}
         out["kernel"] = ["two_heaps", "merged_beam_registers", "merged_beam_lds", "exhaustive_scan", "exhaustive_scan_matrix",
-                         "exhaustive_scan_matrix_float", "exhaustive_scan_matrix_float32"][int(g[6])]
-        out["kernel_mode"] = int(g[6])  # fnv_last_launch_geometry's own ordinal (4: the exhaustive search's matrix engine, 5: its float16 form, 6: its float32 form)
+                         "exhaustive_scan_matrix_float", "exhaustive_scan_matrix_float32", "exhaustive_scan_matrix_float_block",
+                         "exhaustive_scan_matrix_float32_block"][int(g[6])]
+        # fnv_last_launch_geometry's own ordinal (4: the exhaustive search's matrix engine, 5: its float16 form, 6: its float32 form,
+        # 7 and 8: the block form of 5 and 6 ("scan_matrix_block"), block_threads = 64 x the block's wavefronts)
+        out["kernel_mode"] = int(g[6])
         out["tail_exact"] = int(g[7])
-        if int(g[6]) in (3, 4, 5, 6):  # an exhaustive search: the last field says whether it was a range search ("scan_radius")
+        if int(g[6]) in (3, 4, 5, 6, 7, 8):  # an exhaustive search: the last field says whether it was a range search ("scan_radius")
             out["range"] = int(g[7])
-        if int(g[6]) in (4, 5, 6):
+        if int(g[6]) in (4, 5, 6, 7, 8):
             out["tile_queries"], out["segments"] = int(g[3]), int(g[5])
             if int(g[4]):  # a grouped call ("scan_matrix_grouped"): the engine's id queue
                 out["queue_ids"] = int(g[4])

@@ -92,7 +92,7 @@ class DeviceMirror {
   int64_t _filter_scan_max = 0;  // setFilterRouting: re-applied whenever the mirror is created anew
   bool _filter_scan_on_overflow = false;
   bool _exhaustive_matrix = false, _exhaustive_matrix_float = false, _exhaustive_matrix_float32 = false,
-       _exhaustive_matrix_grouped = false;  // setExhaustiveMatrix: likewise
+       _exhaustive_matrix_grouped = false, _exhaustive_matrix_block = false;  // setExhaustiveMatrix: likewise
   int64_t _exhaustive_radius = -1;          // setExhaustiveRadius: likewise (option "scan_radius": -1 = off, else the radius's float32 bits)
   // several GPUs: the mirror on _ordinal is the primary; replicas of it live on the other devices of _devices (filled by peer
   // copies, refreshed whenever the primary changes); batches are sharded over all of them
@@ -294,12 +294,14 @@ class DeviceMirror {
   }
   // The exhaustive search's matrix engines (options "scan_matrix" and, with `float_rows`, "scan_matrix_float", with
   // `float32_rows`, "scan_matrix_float32"; with `grouped`, "scan_matrix_grouped": the grouped exhaustive search takes the engines
-  // that are on): now if there is a mirror, and on every mirror made later.
-  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false) {
+  // that are on; with `block`, "scan_matrix_block": the float engines' single-filter calls on short rows run in workgroups that share row tiles):
+  // now if there is a mirror, and on every mirror made later.
+  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false, bool block = false) {
     _exhaustive_matrix = on;
     _exhaustive_matrix_float = on && float_rows;
     _exhaustive_matrix_float32 = on && float32_rows;
     _exhaustive_matrix_grouped = on && grouped;
+    _exhaustive_matrix_block = on && block;
     if (_handle) applyExhaustiveMatrix();
   }
   // Range search (option "scan_radius"; `bits`: -1 = off, else the float32 bits of a radius that is not a NaN -- the caller has
@@ -315,6 +317,7 @@ class DeviceMirror {
     throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_float", _exhaustive_matrix_float ? 1 : 0));
     throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_float32", _exhaustive_matrix_float32 ? 1 : 0));
     throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_grouped", _exhaustive_matrix_grouped ? 1 : 0));
+    throwOnDeviceError(fnv_set_option(_handle, "scan_matrix_block", _exhaustive_matrix_block ? 1 : 0));
   }
 };
 

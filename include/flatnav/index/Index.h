@@ -378,10 +378,12 @@ class Index {
   // bytes.  With `float32_rows` (option "scan_matrix_float32") float32 indexes do the same, their operands narrowed to bfloat16
   // for the matrix cores only.  With `grouped` (option "scan_matrix_grouped") searchBatchExhaustiveGrouped runs on whichever of these
   // engines is on for the index's element type, its rows fed from each filter's node bitmap -- the same bytes once more.
+  // With `block` (option "scan_matrix_block") the float16 and float32 engines answer single-filter calls of more than 32 queries,
+  // on rows of up to 128 elements, in workgroups whose wavefronts share every row tile through LDS -- the same bytes.
   // Applies to the device mirror now if there is one, and to every mirror made later.
-  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false) {
+  void setExhaustiveMatrix(bool on, bool float_rows = false, bool float32_rows = false, bool grouped = false, bool block = false) {
     std::lock_guard<std::mutex> g(_mirror.mutex());
-    _mirror.setExhaustiveMatrix(on, float_rows, float32_rows, grouped);
+    _mirror.setExhaustiveMatrix(on, float_rows, float32_rows, grouped, block);
   }
   // Range search (flatnav_hip.h, option "scan_radius"): with a radius r, searchBatchExhaustive and searchBatchExhaustiveGrouped
   // return each query's K nearest among the candidates whose distance is at most r (a NaN distance never is; r = +inf admits

@@ -268,6 +268,12 @@ int fnv_index_read_links(fnv_index_t index, uint64_t first_node, uint64_t count,
  *                     index's element type as well, PROVIDED that engine's own option above is on too (see
  *                     fnv_search_batch_exhaustive, "Grouped calls"; default 0 = off: a grouped call keeps the vector scan
  *                     whatever the three options say).  Same bytes.  Read per launch; keeps what fnv_tune measured.
+ *   "scan_matrix_block"  exhaustive search: 1 = the BLOCK FORM of the float16 and float32 matrix engines, PROVIDED the element type's
+ *                     own option ("scan_matrix_float" / "scan_matrix_float32") is on too (see fnv_search_batch_exhaustive, "Block
+ *                     form"; default 0 = off; any value but 0 and 1 is FNV_ERR_INVALID): a call with ONE FILTER and more than 32 queries,
+ *                     on rows of at most 8 MFMA steps (128-d), runs in workgroups of up to four wavefronts that read every row
+ *                     once and share it through LDS.  Unfiltered and grouped calls, longer rows, range searches, 1-byte indexes
+ *                     and shapes it does not fit keep their engine.  Same bytes.  Read per launch; keeps what fnv_tune measured.
  *   "scan_radius"     exhaustive search: range search (see fnv_search_batch_exhaustive, "Range search").  Any value < 0 (default
  *                     -1; the one option besides the two -1 defaults that takes negative values) = off; 0 .. 2^32 - 1 = the
  *                     IEEE-754 bits of the float32 radius r (inner-product distances can be negative, so the sign bit is a legal
@@ -423,6 +429,17 @@ int fnv_search_batch_filtered_device(fnv_index_t index, const void* d_queries, u
  *     keeps the vector scan; the scan stage of a routed filtered graph search keeps it under every option.
  *     fnv_last_launch_geometry reports {grid_blocks, 64, lds_bytes, queries per tile, entries of the id queue, row segments,
  *     kernel = 4, 5 or 6, 0}; fnv_last_replayed_queries the pairs after kernels 5 and 6.
+ *   Block form (option "scan_matrix_block" = 1 AND "scan_matrix_float" / "scan_matrix_float32"): the single-filter call (allowed_bits
+ *     given) on rows of at most 8 MFMA steps -- 128 float16 or float32 elements, a float32 split row included -- runs one
+ *     workgroup of W <= 4 wavefronts per (query tile, row segment) instead of one wavefront.  Each wavefront owns a
+ *     run of the tile's 32-query sub-tiles with their lists; every 32-row tile is read from memory once per workgroup, by one
+ *     wavefront in turn, which zeroes absent chunks, forms the rows' norms and margin terms, narrows float32 to bfloat16 and
+ *     hands the tile over in an LDS ring; all wavefronts score it against their own queries.  Prefilter, margins and rescoring
+ *     are the wave engines' own, so the bytes are theirs.  Taken when such a call has at least two sub-tiles of queries and two
+ *     fit a block's LDS next to the ring; never for unfiltered calls or longer rows (both measured slower than the wave engine),
+ *     grouped calls, range searches, routed scans or 1-byte indexes: those never report kernel 7 / 8.  The option never makes a
+ *     valid call invalid.  It pays below about half of the rows allowed (1.04 x at 50 %, 1.5 x at 1 %, 0.95 x at 90 %).  fnv_last_launch_geometry reports {grid_blocks, 64 W, lds_bytes, queries per tile, 0, row
+ *     segments, kernel = 7 (float16) or 8 (float32), 0}; fnv_last_replayed_queries the pairs as for kernels 5 and 6.
  *   Range search (option "scan_radius" = the float32 bits of a radius r): which items lie within r of a query, and how many.
  *     A candidate (a live node, allowed by the query's filter if it has one) is IN RANGE iff the float32 distance d the scan
  *     reports for the pair satisfies d <= r; a NaN distance never is, r = +inf admits every number, -0 and +0 are one radius.
@@ -576,7 +593,7 @@ int fnv_last_replayed_queries(fnv_index_t index, uint64_t out[5]);
 
 /* Launch geometry of the most recent search: geom[8] = {grid_blocks, block_threads, lds_bytes,
  * blocks_per_cu, visited_slots, cand_slots (LDS entries of the exact search's candidates heap), kernel: 0 = two-heap
- * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, 5 = its float16 form, 6 = its float32 form, tail_exact: the last that-many queries of the launch
+ * kernel, 1 = merged-beam kernel with the beam in registers, 2 = with the beam in LDS, 3 = the exhaustive scan, 4 = the exhaustive scan's matrix engine, 5 = its float16 form, 6 = its float32 form, 7 and 8 = the block form of 5 and 6 (block_threads = 64 x the block's wavefronts), tail_exact: the last that-many queries of the launch
  * went straight to the exact search (merged-beam kernel, see the "sorted_tail_exact_pct" option)}.
  * blocks_per_cu = the query slots a CU keeps resident = the grid's share per CU (round 5; gfx950 hands LDS out in 1280-byte
  * granules, so this is min(what the HIP occupancy API counts, 163840 / (ceil(lds_bytes / 1280) * 1280)); rounds 1-4 launched the

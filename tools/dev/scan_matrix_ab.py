@@ -27,7 +27,12 @@ over the filters (query q uses filter q % N_FILTERS).  The line's candidates are
 With --radius ROWS[,ROWS...] the comparison is the range search's (option "scan_radius"): for every target, a radius that admits
 about that many rows per query; per engine, the unfiltered call with the radius against the same call without it, alternating in
 every round -- medians, min and max, the ratio, whether the range call is slower by more than the other's own max - min, the mean
-number of rows in range (out_ndist) and the share of pairs a float engine rescored in either call.  --fractions is not read."""
+number of rows in range (out_ndist) and the share of pairs a float engine rescored in either call.  --fractions is not read.
+
+With --block (float16 / float32, ungrouped, no radius) a THIRD engine runs in every round on the same handle: the block form of the
+float engine ("scan_matrix_block" = 1 on top of its option, csrc/scan_matrix_block.hpp).  Its bytes are compared with the vector
+scan's at every line, and the line carries its median, min and max, its launch shape, the row bytes it moves, its rescored share
+and whether it beats the WAVE engine's median by more than the wave engine's own max - min."""
 import argparse
 import ctypes
 import json
@@ -58,6 +63,7 @@ ap.add_argument("--dim", type=int, default=128)
 ap.add_argument("--grouped", default="", help="filter counts of grouped calls, comma separated")
 ap.add_argument("--allowed", default="0.5", help="grouped calls: the share of the labels a filter allows, comma separated")
 ap.add_argument("--radius", default="", help="range search: rows per query the radius should admit, comma separated (e.g. 10,10000)")
+ap.add_argument("--block", action="store_true", help="float engines: the block form as a third engine in every round")
 args = ap.parse_args()
 
 HALVES = args.dtype != "uint8"  # a float engine: Gaussian rows, a prefilter with rescoring
@@ -77,7 +83,9 @@ index.allocate_nodes(X.astype(NP_T))
 scan = hip.DeviceIndex(ctypes.c_void_p(index.device_handle()), owned=False)
 tq = torch.from_numpy(Q.astype(NP_T)).to(dev_t)
 out = {e: (torch.empty((NQ, K), dtype=torch.float32, device=dev_t), torch.empty((NQ, K), dtype=torch.int32, device=dev_t),
-           torch.empty(NQ, dtype=torch.int32, device=dev_t), torch.empty(NQ, dtype=torch.int64, device=dev_t)) for e in (0, 1)}
+           torch.empty(NQ, dtype=torch.int32, device=dev_t), torch.empty(NQ, dtype=torch.int64, device=dev_t)) for e in (0, 1, 2)}
+ENGINES = (0, 1, 2) if args.block else (0, 1)  # the vector scan, the (wave) matrix engine, the float engines' block form
+assert not args.block or (args.dtype != "uint8" and not args.grouped and not args.radius), "--block: a float engine's ungrouped call"
 stream = torch.cuda.current_stream()
 rng = np.random.default_rng(1)
 
@@ -89,7 +97,8 @@ def launch(engine, bits, n_bits, qf=None):
         scan.search_device_exhaustive_grouped(tq.data_ptr(), NQ, K, bits.data_ptr(), bits.shape[0], bits.shape[1], n_bits, qf.data_ptr(),
                                               d.data_ptr(), l.data_ptr(), c.data_ptr(), nd.data_ptr(), stream=stream.cuda_stream)
         return
-    scan.set_option(OPTION, engine)
+    scan.set_option(OPTION, int(engine != 0))
+    scan.set_option("scan_matrix_block", int(engine == 2))
     scan.search_device_exhaustive(tq.data_ptr(), NQ, K, d.data_ptr(), l.data_ptr(), c.data_ptr(), nd.data_ptr(),
                                   bits_ptr=bits.data_ptr() if n_bits else 0, n_bits=n_bits, use_filter=n_bits > 0,
                                   stream=stream.cuda_stream)
@@ -191,22 +200,25 @@ for f, n_filters in CASES:
         b, n_bits = hip.pack_allowed(rows) if f < 1 else (np.zeros(1, np.uint8), 0)
         bits = torch.from_numpy(b).to(dev_t)
         per_query = torch.full((NQ,), len(rows), dtype=torch.int64, device=dev_t)
-    geom = {}
-    for e in (0, 1):  # warm-up, the launch shapes, and the same bytes from both engines
+    geom, pairs = {}, {}
+    for e in ENGINES:  # warm-up, the launch shapes, and the same bytes from every engine
         once(lambda: launch(e, bits, n_bits, qf), 1)
         scan.status()
         geom[e] = scan.launch_geometry()
-    rescored = scan.scan_rescored() if HALVES else {"scored": 0, "rescored": 0}
+        pairs[e] = scan.scan_rescored() if HALVES else {"scored": 0, "rescored": 0}
+    rescored = pairs[1]
     assert geom[0]["kernel_mode"] == 3 and geom[1]["kernel_mode"] == MODE and ("queue_ids" in geom[1]) == bool(n_filters), geom
-    assert not HALVES or rescored["scored"] == int(per_query.sum().item()), rescored
-    for x, y in zip(out[0], out[1]):
-        assert torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y), f
-    assert torch.equal(out[1][3], per_query)
-    ms = {0: [], 1: []}
+    assert not args.block or geom[2]["kernel_mode"] in (MODE, MODE + 2), geom  # (MODE: the planner declined the shape)
+    for e in ENGINES[1:]:
+        assert not HALVES or pairs[e]["scored"] == int(per_query.sum().item()), pairs
+        for x, y in zip(out[0], out[e]):
+            assert torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y), (f, e)
+        assert torch.equal(out[e][3], per_query)
+    ms = {e: [] for e in ENGINES}
     for _ in range(args.rounds):
-        for e in (0, 1):
+        for e in ENGINES:
             ms[e].append(once(lambda: launch(e, bits, n_bits, qf), args.steps))
-    med = {e: statistics.median(ms[e]) for e in (0, 1)}
+    med = {e: statistics.median(ms[e]) for e in ENGINES}
     spread = max(ms[0]) - min(ms[0])
     tile = geom[1]["tile_queries"]
     ops = 2.0 * NQ * len(rows) * DIM
@@ -215,15 +227,28 @@ for f, n_filters in CASES:
                 vector_geometry=geom[0], matrix_geometry=geom[1], matrix_tops=ops / (med[1] * 1e-3) / 1e12,
                 matrix_of_peak=ops / (med[1] * 1e-3) / 1e12 / PEAK_TOPS, matrix_row_bytes=math.ceil(NQ / tile) * len(rows) * ROW_BYTES,
                 rescored_share=rescored["rescored"] / max(1, rescored["scored"]), dtype=args.dtype, dim=DIM)
+    if args.block:  # the block form against the WAVE engine of the same rounds
+        wave_spread = max(ms[1]) - min(ms[1])
+        line.update(block_ms=ms[2], block_median=med[2], block_geometry=geom[2], wave_spread=wave_spread, block_over_wave=med[1] / med[2],
+                    block_beats_wave_by_more_than_spread=bool(med[1] - med[2] > wave_spread),
+                    block_row_bytes=math.ceil(NQ / geom[2]["tile_queries"]) * len(rows) * ROW_BYTES,
+                    block_rescored_share=pairs[2]["rescored"] / max(1, pairs[2]["scored"]))
     lines.append(line)
     print("filters %-5d f=%-6g cand %8d | vector %9.3f ms [%9.3f .. %9.3f] | matrix %9.3f ms [%9.3f .. %9.3f] | %6.2fx  beats spread: %s | "
           "matrix grid %d lds %d tile %d segments %d | %.1f TOP/s (%.4f of peak), row bytes %.3e | rescored %.4f of the pairs"
           % (n_filters, f, len(rows), med[0], min(ms[0]), max(ms[0]), med[1], min(ms[1]), max(ms[1]), line["ratio"], line["beats_by_more_than_spread"],
              geom[1]["grid_blocks"], geom[1]["lds_bytes"], tile, geom[1]["segments"], line["matrix_tops"], line["matrix_of_peak"],
              line["matrix_row_bytes"], line["rescored_share"]), flush=True)
+    if args.block:
+        print("        block  %9.3f ms [%9.3f .. %9.3f] | wave / block %5.2fx  beats the wave engine's spread (%.3f ms): %s | mode %d threads %d "
+              "grid %d lds %d tile %d segments %d | row bytes %.3e | rescored %.4f of the pairs"
+              % (med[2], min(ms[2]), max(ms[2]), line["block_over_wave"], line["wave_spread"], line["block_beats_wave_by_more_than_spread"],
+                 geom[2]["kernel_mode"], geom[2]["block_threads"], geom[2]["grid_blocks"], geom[2]["lds_bytes"], geom[2]["tile_queries"],
+                 geom[2]["segments"], line["block_row_bytes"], line["block_rescored_share"]), flush=True)
 if args.radius:
     lines = radius_lines()
 scan.set_option(OPTION, 0)
 scan.set_option("scan_matrix_grouped", 0)
+scan.set_option("scan_matrix_block", 0)
 if args.json:
     json.dump(lines, open(args.json, "w"), indent=1)
