@@ -13,16 +13,22 @@ MAX_LDS = 160 << 10  # kScanMaxLds
 _LIB = []
 
 
-def shape(dtype, dim, nq, K, live=1_000_000, own=1, block=1, grouped=0, filter_rows=0, radius=0, segment_rows=0, listed=1) -> dict:
-    """`listed`: the call has one filter -- the class the block form takes (unfiltered calls are declined by measurement)."""
+def lib():
+    """The harness, compiled once per process (tests/exhaustive_sequences.py calls it with inputs of its own)."""
     if not _LIB:
         out = os.path.join(tempfile.mkdtemp(prefix="flatnav_scan_matrix_block_"), "harness.so")
         src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "scan_matrix_block_harness.cpp")
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-fPIC", "-shared", src, "-o", out])
         _LIB.append(C.CDLL(out))
+        _LIB[0].smb_vector_lds.restype = C.c_int64
+    return _LIB[0]
+
+
+def shape(dtype, dim, nq, K, live=1_000_000, own=1, block=1, grouped=0, filter_rows=0, radius=0, segment_rows=0, listed=1) -> dict:
+    """`listed`: the call has one filter -- the class the block form takes (unfiltered calls are declined by measurement)."""
     res = (C.c_int64 * len(FIELDS))()
     options = (1 if dtype == U8 else 0, own if dtype == F16 else 0, own if dtype == F32 else 0, grouped, block)
-    _LIB[0].smb_shape((C.c_int64 * 16)(dtype, dim, live, 256, segment_rows, *options, nq, K, live, filter_rows, radius, listed and not filter_rows), res)
+    lib().smb_shape((C.c_int64 * 16)(dtype, dim, live, 256, segment_rows, *options, nq, K, live, filter_rows, radius, listed and not filter_rows), res)
     return dict(zip(FIELDS, (int(v) for v in res)))
 
 
